@@ -25,6 +25,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s peak (spec)
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together, .npy headers included, stay below 64 MB
 
 
 def parse():
@@ -49,7 +50,12 @@ def parse():
     ap.add_argument("--coherent", type=int, default=0, help="also time the spatially coherent 100k / 2M graph with and without the two-level preconditioner (not a BASELINE config)")
     ap.add_argument("--tree-init", type=int, default=1, help="also solve from the maximum-spanning-tree initialisation of SURVEY 8(d)")
     ap.add_argument("--weak-leg", type=int, default=1, help="N > 1, --scaling strong: also time the weak-scaling point (cams x N, edges x N) and report it as `weak_scaling` on the same line")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step (rotations, costs) to DIR/<name>.npy, to compare two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def kernel_source_sha16():
@@ -389,12 +395,32 @@ def main():
             el = float(t.item())
         return el, sweeps_, summ_, rot_
 
+    def dump_outputs(rot_, summ_):
+        """--dump-outputs DIR (rank 0): the rotations (caller's camera numbering) and the costs a caller of the timed path received from its last
+        step, as float64 .npy files.  Rotations beyond DUMP_BUDGET_BYTES are a fixed sample of cameras (seed 0), whose numbers go beside them.
+        Called again by every variant that takes over `ms_per_step`, so the files always belong to the line."""
+        if args.dump_outputs is None or rank != 0:
+            return
+        rot_ = np.ascontiguousarray(part.gather(rot_) if part is not None else rot_, dtype=np.float64)
+        files = {"cost": np.array([summ_["initial_cost"], summ_["final_cost"]], dtype=np.float64)}
+        row_bytes = rot_[0].nbytes
+        if rot_.nbytes > DUMP_BUDGET_BYTES - 4096:
+            k = (DUMP_BUDGET_BYTES - 4096) // (row_bytes + 8)
+            cams = np.sort(np.random.default_rng(0).choice(rot_.shape[0], k, replace=False))
+            rot_ = rot_[cams]
+            files["rotations_cameras"] = cams.astype(np.float64)
+        files["rotations"] = rot_
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in files.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
     # N > 1 with the native RCCL communicator: the PCG chunks would be captured into hipGraphs TOGETHER with their all-gathers (the library's
     # default).  That path has never run on more than one GPU, so the contract line is first measured with plain launches (pcg_hip_graph = 0)
     # and the captured variant is tried afterwards, under its own watchdog, which prints the plain-launch line if the capture hangs.
     sharded_capture = part is not None and getattr(comm, "backend", "") == "rccl-native" and os.environ.get("GSFM_PCG_GRAPH_COLLECTIVES", "1") != "0"
     base_opts = dict(pcg_hip_graph=0) if sharded_capture else {}
     elapsed, sweeps, summ, rot = timed_solves(args.warmup, args.steps, **base_opts)
+    dump_outputs(rot, summ)
     el_h, sw_h, _, rot_h = timed_solves(1, args.steps, resident=False, **base_opts)   # (every rank: the sharded solve is a collective)
     host_leg = {"what": "gsfm_rot_solve: host arrays in and out (the reference's calling convention), PCIe-inclusive -- reported, never `value`",
                 "ms_per_step": 1e3 * el_h / args.steps, "value": n_edges * sw_h / el_h, "same_rotations_as_value": bool(np.array_equal(rot, rot_h))}
@@ -627,8 +653,9 @@ def main():
             crash_lib.gsfm_crash_line_arm(ctypes.c_int(real_stdout if rank == 0 else -1), line0, ctypes.c_size_t(len(line0)), ctypes.c_size_t(max(off, 0)))
         except OSError:
             crash_lib = None
-        if os.environ.get("GSFM_BENCH_TEST_CRASH") == "1":   # (test hook: what a GPU fault does)
-            os.abort()
+        if os.environ.get("GSFM_BENCH_TEST_CRASH") == "1" and crash_lib is not None:
+            # (test hook: the armed handler entered as a SIGABRT from the runtime would enter it; no signal is raised, nothing aborts)
+            crash_lib.gsfm_crash_line_fire(ctypes.c_int(6))
     if sharded_capture:
         # The library's default for the native communicator: PCG chunks replayed as hipGraphs WITH their all-gathers.  Tried only now that the
         # plain-launch line exists; if it does not come back in time, rank 0 prints that line and every rank leaves with status 0.
@@ -644,8 +671,9 @@ def main():
         wd = threading.Timer(limit, _fall_back)
         wd.daemon = True
         wd.start()
-        el_c, sw_c, s_c, _ = timed_solves(args.warmup, args.steps)
+        el_c, sw_c, s_c, rot_c = timed_solves(args.warmup, args.steps)
         wd.cancel()
+        dump_outputs(rot_c, s_c)
         if rank == 0:
             out["plain_launches"] = {"value": out["value"], "ms_per_step": out["ms_per_step"], "pcg_chunks_replayed_as_hipgraphs": out["pcg_chunks_replayed_as_hipgraphs"]}
             out["hipgraph_with_collectives"] = {"status": "ok", "value": n_edges * sw_c / el_c, "ms_per_step": 1e3 * el_c / args.steps, "pcg_chunks_replayed_as_hipgraphs": s_c["num_graph_launches"],
@@ -673,7 +701,7 @@ def main():
         try:
             prob_p, _ = sharding.make_sharded_problem(g, error_type, loss=loss_ctor(), part=part, exchange="peer")
             if prob_p._comm.backend.startswith("peer-store"):
-                el_p, sw_p, s_p, _ = timed_solves(args.warmup, args.steps, problem=prob_p)
+                el_p, sw_p, s_p, rot_p = timed_solves(args.warmup, args.steps, problem=prob_p)
                 bad = prob_p._comm.error()
                 info = {"status": "ok" if not bad else "a wait for a peer's flag ran into its bound: result discarded", "backend": prob_p._comm.backend,
                         "value": n_edges * sw_p / el_p, "ms_per_step": 1e3 * el_p / args.steps, "pcg_chunks_replayed_as_hipgraphs": s_p["num_graph_launches"],
@@ -685,6 +713,7 @@ def main():
                         out["value"], out["ms_per_step"] = info["value"], info["ms_per_step"]
                         out["config"]["collectives"] = prob_p._comm.backend
                         out["pcg_chunks_replayed_as_hipgraphs"] = info["pcg_chunks_replayed_as_hipgraphs"]
+                        dump_outputs(rot_p, s_p)
             prob_p.close()
             prob_p._comm.close()
         except Exception as e:  # noqa: BLE001  (the extra variant never takes the line down with it)

@@ -30,6 +30,14 @@ int gsfm_crash_line_arm(int fd, const char* line, size_t len, size_t sig_off) {
   for (int k = 0; k < 4; ++k) signal(sigs[k], crash_handler);
   return 0;
 }
+/* Test entry (bench.py's GSFM_BENCH_TEST_CRASH): enters the handler exactly as a delivered `sig` would, provided it is the installed disposition
+ * of `sig` -- without raising a signal, so the process never aborts.  Returns 1 (and does nothing) when the handler is not installed. */
+int gsfm_crash_line_fire(int sig) {
+  struct sigaction cur;
+  if (sigaction(sig, NULL, &cur) != 0 || cur.sa_handler != crash_handler) return 1;
+  crash_handler(sig);
+  return 0;
+}
 void gsfm_crash_line_disarm(void) {
   static const int sigs[4] = {SIGABRT, SIGSEGV, SIGBUS, SIGFPE};
   for (int k = 0; k < 4; ++k) signal(sigs[k], SIG_DFL);

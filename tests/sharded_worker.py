@@ -239,7 +239,7 @@ def main():
     if case.startswith("random"):
         return random_case(int(case.split(":")[1]), out, len(sys.argv) > 3 and sys.argv[3] == "native", big=case.startswith("randomcoarse"))
     g = synth.make_graph(1203, 40000, seed=23, outlier_frac=0.3)
-    if case == "isolated":   # the last cameras carry no edge at all: with 8 ranks the last slice holds nothing but isolated cameras
+    if case == "isolated":   # the last cameras carry no edge at all: the partition below gives the last rank nothing but isolated cameras
         keep = (g["edge_i"] < 1100) & (g["edge_j"] < 1100)
         for k in ("edge_i", "edge_j", "rel_aa", "cov6", "inlier_weight"):
             g[k] = g[k][keep]

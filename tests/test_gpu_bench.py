@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -18,11 +19,13 @@ def _json_line(stdout):
     return json.loads(lines[0])
 
 
-def test_bench_single_gpu_contract_line():
+def test_bench_single_gpu_contract_line(tmp_path):
     # (with the cpu_baseline leg: the oracle solves the same graph, so the line carries a device-vs-CPU comparison that is asserted below)
     small = [a for a in SMALL]
     small[small.index("--cpu-baseline") + 1] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + small + ["--cpu-single-cams", "0"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + small + ["--cpu-single-cams", "0", "--dump-outputs", str(dump)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = _json_line(r.stdout)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
@@ -45,6 +48,10 @@ def test_bench_single_gpu_contract_line():
     its = out["iters_to_1e-6_by_schedule"]
     assert its["default"] == its["exact"] == out["iters_to_1e-6"] and its["lm_iterations_default"] == its["lm_iterations_exact"], its
     assert "init" in out["config"] and "spanning" in out["config"]["init"]
+    # --dump-outputs: the timed path's last result, every camera (20k rows are far below the size budget), the line's final cost
+    rot, cost = np.load(dump / "rotations.npy"), np.load(dump / "cost.npy")
+    assert rot.dtype == np.float64 and rot.shape == (out["config"]["cams"], 3) and np.isfinite(rot).all()
+    assert cost.dtype == np.float64 and cost[1] == out["final_cost"] and not (dump / "rotations_cameras.npy").exists()
 
 
 def test_bench_two_ranks_on_one_gpu_over_gloo():
@@ -107,7 +114,8 @@ def test_bench_falls_back_to_the_plain_launch_line_when_the_captured_variant_doe
 
 def test_bench_prints_the_plain_launch_line_even_if_a_later_variant_kills_the_process():
     """A GPU fault in one of the never-measured multi-rank variants ends the process through abort(); the armed C-level handler writes the
-    line measured with plain launches, marked with a `crashed_variant` field carrying the signal number (test hook: the process aborts itself right after arming)."""
+    line measured with plain launches, marked with a `crashed_variant` field carrying the signal number (test hook: right after arming, bench.py enters the installed SIGABRT
+    handler directly -- no signal is raised, so nothing aborts; libgsfm_benchguard.so refuses when the handler is not the installed disposition)."""
     env = dict(os.environ, GSFM_FORCE_SHARD="1", HSA_ENABLE_IPC_MODE_LEGACY="0", GSFM_BENCH_TEST_CRASH="1")
     port = 29970 + os.getpid() % 9
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),

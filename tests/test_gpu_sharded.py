@@ -6,6 +6,7 @@ to rounding in the cost all-reduce only."""
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -15,6 +16,8 @@ from globalsfmpy_amd.loss_functions import MAGSACWeightBasedLoss
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# The test process holds the GPU as well: at most 5 ranks keep the box at 6 processes with the device open, the most a shared test machine allows.
+MAX_RANKS = 5
 
 
 def _reference(case="default"):
@@ -30,15 +33,38 @@ def _reference(case="default"):
     return rot, s, p.trace()
 
 
-def _launch(nproc, backend, out, extra_env=None, mode="torch", case="default"):
+def _launch(nproc, backend, out, extra_env=None, mode="torch", case="default", timeout=600):
+    """Starts the nproc ranks of tests/sharded_worker.py with the environment torch.distributed.run gives its workers, but without that
+    launcher: it calls torch.cuda.is_available() and so would hold the GPU as one more process.  The first rank that fails ends the others."""
+    assert nproc <= MAX_RANKS, nproc
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    env.setdefault("OMP_NUM_THREADS", "1")   # (torch.distributed.run's default for several workers per node)
     env.update(extra_env or {})
     port = 29600 + (os.getpid() % 300) + (0 if backend == "gloo" else 1)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "tests", "sharded_worker.py"), backend, out, mode, case]
-    r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(nproc), LOCAL_WORLD_SIZE=str(nproc))
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "sharded_worker.py"), backend, out, mode, case]
+    logs = [out + ".rank%d.log" % r for r in range(nproc)]
+    procs = []
+    try:
+        for r in range(nproc):
+            with open(logs[r], "w") as f:
+                procs.append(subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), cwd=ROOT, stdout=f, stderr=subprocess.STDOUT))
+        deadline = time.monotonic() + timeout
+        while any(p.poll() is None for p in procs) and not any(p.returncode for p in procs) and time.monotonic() < deadline:
+            time.sleep(0.1)
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+            p.wait()
+    rcs = [p.returncode for p in procs]
+    if any(rcs):
+        tails = []
+        for r, path in enumerate(logs):
+            with open(path) as f:
+                tails.append("---- rank %d (rc %d)\n%s" % (r, rcs[r], f.read()[-2000:]))
+        raise AssertionError("\n".join(tails))
     return np.load(out)
 
 
@@ -50,7 +76,7 @@ def _compare(res, ref):
     assert synth.angular_distance(synth.align_rotations(res["rot"], rot), rot).mean() <= 1e-6
 
 
-@pytest.mark.parametrize("world", [2, 3, 8])
+@pytest.mark.parametrize("world", [2, 3, MAX_RANKS])
 def test_ranks_share_one_gpu_over_gloo(tmp_path, world):
     """1203 cameras cut into slices of equal directed-entry counts (unequal camera counts: every slice but the widest is padded)."""
     res = _launch(world, "gloo", str(tmp_path / ("gloo%d.npz" % world)))
@@ -60,9 +86,9 @@ def test_ranks_share_one_gpu_over_gloo(tmp_path, world):
 
 
 def test_a_rank_that_holds_only_isolated_cameras(tmp_path):
-    """8 ranks, the last 103 cameras without any edge and a partition that gives exactly those to the last rank: it holds no edge at all, still
+    """MAX_RANKS ranks, the last 103 cameras without any edge and a partition that gives exactly those to the last rank: it holds no edge at all, still
     has to take part in every collective (problem creation with zero local edges), and the isolated cameras keep their input rotation."""
-    res = _launch(8, "gloo", str(tmp_path / "iso.npz"), case="isolated")
+    res = _launch(MAX_RANKS, "gloo", str(tmp_path / "iso.npz"), case="isolated")
     ref = _reference("isolated")
     _compare(res, ref)
     g0 = synth.make_graph(1203, 40000, seed=23, outlier_frac=0.3)
@@ -178,7 +204,7 @@ def test_host_staged_collectives_fall_back_to_plain_launches_when_capture_is_req
     assert int(res["graph_launches"]) == 0
 
 
-@pytest.mark.parametrize("world,seed", [(3, 102), (5, 103), (8, 104), (6, 106), (7, 222)])
+@pytest.mark.parametrize("world,seed", [(3, 102), (5, 103), (4, 104), (3, 106), (2, 222)])
 def test_random_graph_random_partition_equals_the_single_gpu_solve(tmp_path, world, seed):
     """Random size, error type (the non-Laplacian 9-residual functor included), loss, PCG variant and a random partition -- arbitrary cut points,
     so slices of very different widths and ranks that own no camera at all: same LM and PCG iteration counts, same cost, same rotations."""
@@ -204,7 +230,7 @@ def test_two_level_preconditioner_on_a_sharded_coherent_graph(tmp_path, world):
     assert synth.angular_distance(res["rot"], res["ref_rot"]).max() < 1e-8
 
 
-@pytest.mark.parametrize("world", [2, 3, 8])
+@pytest.mark.parametrize("world", [2, 3, MAX_RANKS])
 def test_peer_store_exchange_equals_the_host_staged_collectives_bit_for_bit(tmp_path, world):
     """csrc/gsfm_peer.hip: every rank writes its slice into the other ranks' IPC-mapped mailboxes and a flag says it has arrived -- the
     all-gather of every PCG iteration and of every linearisation, and the scalar all-reduces, without a collective-library call.  N processes
@@ -222,7 +248,14 @@ def test_peer_store_exchange_equals_the_host_staged_collectives_bit_for_bit(tmp_
     else:            # the cost all-reduce: gloo adds the ranks' shares in its ring's order, the mailbox in rank order -- last-bit differences in the
         #              costs, which the trust-region radius law feeds back into the steps
         assert synth.angular_distance(a["rot"], b["rot"]).max() <= 1e-12 and abs(float(a["cost"]) - float(b["cost"])) <= 1e-13 * float(b["cost"])
-        assert np.allclose(a["trace"], b["trace"], rtol=1e-9, atol=0.0)
+        # every trace column to 1e-9; cost_change and relative_decrease (columns 2 and 5) are differences of two costs and carry the costs'
+        # last-bit differences in absolute terms (4 ranks: one ulp of a 3e5 candidate cost is 1.2e-9 of a 0.047 change), so those two may
+        # also differ by what the cost bound above allows
+        ta, tb = a["trace"], b["trace"]
+        tol = 1e-9 * np.abs(tb)
+        tol[:, 2] = np.maximum(tol[:, 2], 1e-13 * tb[:, 1])
+        tol[:, 5] = np.maximum(tol[:, 5], 1e-13 * tb[:, 1] * np.abs(tb[:, 5]) / np.maximum(np.abs(tb[:, 2]), 1e-300))
+        assert (np.abs(ta - tb) <= tol).all(), np.abs(ta - tb) / np.maximum(tol, 1e-300)
     _compare(a, _reference())
 
 
