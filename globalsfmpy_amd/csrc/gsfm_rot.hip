@@ -9,6 +9,7 @@
 #include "solver_components.hpp"
 #include "solver_lm.hpp"
 #include "problem_create.hpp"
+#include "spanning_tree.hpp"
 
 // =============================================================================================
 extern "C" {
@@ -370,6 +371,17 @@ gsfm_status gsfm_rot_edge_sq_norms(uint32_t n_cams, uint64_t n_edges, const uint
   if (kernel_ms) *kernel_ms = ms;
   if (n_kept) *n_kept = keep_out ? (uint64_t)cnt : n_edges;
   return GSFM_OK;
+}
+
+gsfm_status gsfm_rot_init_spanning_tree(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j, const double* rel_aa,
+                                        const int32_t* weight, double* rot_aa_out, int64_t* parent_edge_out, uint32_t* root_out,
+                                        uint32_t* n_tree_cams_out, uint32_t* depth_out, double* kernel_ms) {
+  // (host vectors of O(E) / O(n) and host threads: an exception must not cross the C boundary)
+  try {
+    return init_spanning_tree_impl(n_cams, n_edges, edge_i, edge_j, rel_aa, weight, rot_aa_out, parent_edge_out, root_out, n_tree_cams_out, depth_out, kernel_ms);
+  } catch (const std::exception& e) {
+    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("spanning-tree initialisation ran out of host resources: ") + e.what());
+  }
 }
 
 int64_t gsfm_rot_count_components(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j) {

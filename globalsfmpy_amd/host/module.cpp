@@ -416,6 +416,7 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
     return d;
   });
   m.def("OrientationsFromMaximumSpanningTree", [](const ViewGraph& vg, OrientationMap* o) { return OrientationsFromMaximumSpanningTree(vg, o); });
+  m.def("OrientationsFromMaximumSpanningTreeOnDevice", [](const ViewGraph& vg, OrientationMap* o) { return OrientationsFromMaximumSpanningTreeOnDevice(vg, o); });
   m.def("FilterViewPairsFromOrientation", &FilterViewPairsFromOrientation);
   // bind :658, src/compare_reconstructions.cpp:617-647: (view_graph, reconstruction_to_eval, covariances, residuals) -- fills `residuals`
   m.def("residuals_of_relative_rot", [](const ViewGraph& vg, const Reconstruction& rec, const CovarianceMap& cov, std::vector<double>& residuals) {

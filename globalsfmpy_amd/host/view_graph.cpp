@@ -173,6 +173,38 @@ bool OrientationsFromMaximumSpanningTree(const ViewGraph& view_graph, std::unord
   return true;
 }
 
+bool OrientationsFromMaximumSpanningTreeOnDevice(const ViewGraph& view_graph, std::unordered_map<ViewId, Eigen::Vector3d>* orientations) {
+  if (!orientations) return false;
+  std::vector<ViewId> ids;
+  ids.reserve(view_graph.NumViews());
+  for (ViewId v : view_graph.ViewIds()) ids.push_back(v);
+  std::sort(ids.begin(), ids.end());
+  std::vector<ViewIdPair> keys;
+  keys.reserve(view_graph.NumEdges());
+  for (const auto& e : view_graph.GetAllEdges()) keys.push_back(e.first);
+  std::sort(keys.begin(), keys.end());
+  if (keys.empty()) return false;
+  auto rank = [&ids](ViewId v) { return (uint32_t)(std::lower_bound(ids.begin(), ids.end(), v) - ids.begin()); };
+  std::vector<uint32_t> ei(keys.size()), ej(keys.size());
+  std::vector<int32_t> w(keys.size());
+  std::vector<double> rel(3 * keys.size());
+  for (size_t e = 0; e < keys.size(); ++e) {
+    const TwoViewInfo& info = *view_graph.GetEdge(keys[e].first, keys[e].second);
+    ei[e] = rank(keys[e].first); ej[e] = rank(keys[e].second); w[e] = info.num_verified_matches;
+    for (int k = 0; k < 3; ++k) rel[3 * e + k] = info.rotation_2[k];
+  }
+  std::vector<double> rot(3 * ids.size());
+  std::vector<int64_t> parent(ids.size());
+  uint32_t root = 0, n_tree = 0;
+  const gsfm_status st = gsfm_rot_init_spanning_tree((uint32_t)ids.size(), keys.size(), ei.data(), ej.data(), rel.data(), w.data(), rot.data(), parent.data(),
+                                                     &root, &n_tree, nullptr, nullptr);
+  if (st == GSFM_ERR_EMPTY) return false;
+  if (st != GSFM_OK) throw std::runtime_error(std::string("OrientationsFromMaximumSpanningTreeOnDevice: ") + gsfm_last_error());
+  for (size_t v = 0; v < ids.size(); ++v)
+    if (v == root || parent[v] >= 0) (*orientations)[ids[v]] = Eigen::Vector3d(rot[3 * v], rot[3 * v + 1], rot[3 * v + 2]);
+  return true;
+}
+
 namespace {
 // edges whose two views have an orientation, in ViewIdPair order, flattened for the C-ABI (dense camera index = rank of the ViewId)
 struct FlatEdges {

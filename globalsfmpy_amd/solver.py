@@ -327,3 +327,29 @@ def edge_sq_norms(n_cams, edge_i, edge_j, rel_aa, rot_aa, cov6=None, max_sq_norm
     if st != 0:
         raise SolverError("gsfm_rot_edge_sq_norms failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
     return {"s": s, "keep": None if keep is None else keep.astype(bool), "n_kept": int(kept.value), "kernel_ms": ms.value}
+
+
+def orientations_from_maximum_spanning_tree(n_cams, edge_i, edge_j, rel_aa, weight=None):
+    """gsfm_rot_init_spanning_tree: theia's OrientationsFromMaximumSpanningTree on flat arrays, on the device.  The maximum spanning
+    tree of the largest connected component under (weight desc, edge index asc), rooted at the component's smallest camera, rotations
+    composed down it (R_j = R_ij R_i across edge (i, j)).  weight: per-edge num_verified_matches (int32), None = all equal.
+    Returns dict(rot_aa (n_cams x 3, zeros outside the component), parent_edge (int64 per camera, -1 for the root and outside),
+    root, n_tree_cams, depth, kernel_ms)."""
+    lib = _abi.load_library()
+    ei, ej, rel, _, _, n_edges = _prep_edges(n_cams, edge_i, edge_j, rel_aa, None, None)
+    wt = None
+    if weight is not None:
+        wt = np.ascontiguousarray(weight, dtype=np.int32).reshape(-1)
+        if wt.shape[0] != n_edges:
+            raise ValueError("weight disagrees with the edges in length")
+    n = int(n_cams)
+    rot = np.empty((n, 3))
+    parent = np.empty(n, dtype=np.int64)
+    root, n_tree, depth, ms = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_double(0)
+    st = lib.gsfm_rot_init_spanning_tree(n, int(n_edges), _u32p(ei), _u32p(ej), _dp(rel),
+                                         None if wt is None else wt.ctypes.data_as(C.POINTER(C.c_int32)), _dp(rot),
+                                         parent.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(root), C.byref(n_tree), C.byref(depth), C.byref(ms))
+    if st != 0:
+        raise SolverError("gsfm_rot_init_spanning_tree failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+    return {"rot_aa": rot, "parent_edge": parent, "root": int(root.value), "n_tree_cams": int(n_tree.value), "depth": int(depth.value),
+            "kernel_ms": ms.value}

@@ -59,6 +59,11 @@ class Reconstruction {
 
 // thirdparty/TheiaSfM/src/theia/sfm/view_graph/orientations_from_maximum_spanning_tree.cc:109-181
 bool OrientationsFromMaximumSpanningTree(const ViewGraph& view_graph, std::unordered_map<ViewId, Eigen::Vector3d>* orientations);
+// The same initialisation on the device (gsfm_rot_init_spanning_tree): the edges flattened in sorted ViewIdPair order with dense
+// index = rank of the ViewId, so that the device's tie-break (weight desc, edge index asc) is theia's (weight desc, first asc, second
+// asc) and both choose the same tree.  Fills the orientations of the tree component only, like the host function; returns false for
+// an empty graph; throws std::runtime_error when no device is usable (there is no CPU fallback) or the device call fails.
+bool OrientationsFromMaximumSpanningTreeOnDevice(const ViewGraph& view_graph, std::unordered_map<ViewId, Eigen::Vector3d>* orientations);
 
 // thirdparty/TheiaSfM/src/theia/sfm/filter_view_pairs_from_orientation.cc:55-122: drops the edges whose
 // relative rotation disagrees with the global orientations by more than the threshold (and the edges touching a view

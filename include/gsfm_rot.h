@@ -460,6 +460,37 @@ gsfm_status gsfm_rot_edge_sq_norms(uint32_t n_cams, uint64_t n_edges, const uint
                                    const double* rel_aa, const double* cov6, const double* rot_aa, double max_sq_norm,
                                    double* s_out, uint8_t* keep_out, uint64_t* n_kept, double* kernel_ms);
 
+/* ------------------------------------------------------------------------- */
+/* The step before the solve: the maximum-spanning-tree initialisation         */
+/* ------------------------------------------------------------------------- */
+/* Theia OrientationsFromMaximumSpanningTree on flat arrays, on the device
+ * (orientations_from_maximum_spanning_tree.cc:62-181; the call the reference pipeline starts every solve from,
+ * GSfM_global_reconstruction_estimator.cpp:463-485).
+ *   Tree         the maximum spanning forest under a strict total order on the edges: a larger weight[e] wins; on equal weights
+ *                the smaller edge index wins.  Under that order the tree is unique: it depends on neither atomics order nor launch
+ *                shape.  weight == NULL: all weights equal (the tree is then pure index order).  theia sorts by (weight desc,
+ *                first asc, second asc): edges flattened in sorted ViewIdPair order give the same tree.  Duplicate pairs are
+ *                allowed; the index order breaks their ties.
+ *   Component    only the largest connected component is initialised; of two of equal size, the one holding the smallest camera
+ *                index (ViewGraph::GetLargestConnectedComponentIds).  A camera without an edge is a component of one.  The root is
+ *                the smallest camera index of the component: rot_aa_out[root] = 0.  Cameras outside the component get zeros.
+ *   Composition  the edge convention of this header: across edge e = (i, j), R_j = R_ij R_i and R_i = R_ij^T R_j (for i < j
+ *                exactly theia's source < neighbour rule).
+ *   rel_aa       3 per edge; only the n_c - 1 tree edges are read (gathered on the host once the tree is known).
+ *   Outputs      rot_aa_out: 3 per camera.  parent_edge_out (may be NULL): per camera, the index of the tree edge to its parent;
+ *                -1 for the root and for every camera outside the component.  root_out, n_tree_cams_out (n_c), depth_out (the
+ *                largest number of tree edges between the root and a camera) and kernel_ms (HIP-event time of the device kernels,
+ *                copies excluded) may each be NULL.
+ *   Errors       checked on the host before any device call: an edge index >= n_cams, a self-loop, a NULL edge_i / edge_j /
+ *                rel_aa (with n_edges > 0) or rot_aa_out, n_edges >= 2^32 or n_cams >= 2^31 - 1: GSFM_ERR_INVALID_ARG.  A largest
+ *                component of one camera (no edges at all): GSFM_ERR_EMPTY, outputs zero / -1.  No device: GSFM_ERR_NO_DEVICE
+ *                (no host fallback).
+ * Two calls on the same input return the same bytes (no float atomics; products grouped by the tree alone).                 */
+gsfm_status gsfm_rot_init_spanning_tree(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j,
+                                        const double* rel_aa, const int32_t* weight, double* rot_aa_out,
+                                        int64_t* parent_edge_out, uint32_t* root_out, uint32_t* n_tree_cams_out,
+                                        uint32_t* depth_out, double* kernel_ms);
+
 /* Host-only helper for partitioners: the locality relabelling gsfm_rot_problem_create would adopt for this graph on one GPU
  * (reverse Cuthill-McKee, kept only if it halves the mean index distance of the edges and brings it under 1024).
  * perm_out[c] = position of camera c in that order (the identity if nothing is to be gained).  Returns 1 if adopted, 0 if the
