@@ -320,11 +320,16 @@ struct ColLinArgs {
   LinArgs lin;              // streams (qr, w, col, eid: all in position order), q, loss, rho_ext, sigma, h0..h2 (out); row_base
   ColLayoutDev L;
   double* part;             // 9 planes of [n_wg * RB]
+  double* cost_part;        // COST instantiations: [n_wg], this workgroup's sum of 1/2 rho (k_sum_partials / k_trial_post add them in index order)
 };
-template <int F, int WM, int LM, bool FAST>
+// COST: the fused trial evaluation (solver_lm.hpp, evaluate_trial) -- the same blocks and row partials, bit for bit, plus the cost at q: every
+// edge has two entries, the one whose row camera is the edge's `first` (role bit 0) adds 1/2 rho(|r|^2) from the leaf K1's cost-only sweep
+// uses (loss_value).  Only the body-frame fast path has it (angle-axis family, FAST losses).
+template <int F, int WM, int LM, bool FAST, bool COST = false>
 __device__ __forceinline__ void lin_col_body(const ColLinArgs& a) {
   constexpr int RB = GSFM_COL_RB, SUB = GSFM_COL_SUB, T = GSFM_COLLIN_THREADS, RPL = RB / T;
   constexpr bool BODY = col_lin_body_frame(F, FAST);
+  static_assert(!COST || (BODY && LM != LM_PROGRAM && T == GSFM_BLOCK), "the fused cost: body-frame fast path, one GSFM_BLOCK-wide reduction");
   __shared__ double slots[9][SUB];
   __shared__ double2 qrow[2][RB];
   __shared__ uint32_t wtot[RPL][T / 64];
@@ -335,7 +340,7 @@ __device__ __forceinline__ void lin_col_body(const ColLinArgs& a) {
     const uint32_t k = min(a.lin.row_base + w.row0 + r, a.lin.row_base + a.lin.n_rows - 1);   // (a ragged last block re-reads its last row)
     qrow[0][r] = a.lin.q[2 * (size_t)k]; qrow[1][r] = a.lin.q[2 * (size_t)k + 1];
   }
-  double acc[RPL][9];
+  double acc[RPL][9], cost = 0.0;
 #pragma unroll
   for (int j = 0; j < RPL; ++j)
 #pragma unroll
@@ -378,7 +383,8 @@ __device__ __forceinline__ void lin_col_body(const ColLinArgs& a) {
         if (cr != GSFM_COL_PAD) {
           const uint32_t rl = col_rowl(mt[k].y);
           const double2 k0 = qrow[0][rl], k1 = qrow[1][rl];
-          lin_entry_body_aa<WM, LM>(a.lin, lv, d, cr, Quat{k0.x, k0.y, k1.x, k1.y}, qm[k], S[k], g3, B6);
+          const double sq = lin_entry_body_aa<WM, LM>(a.lin, lv, d, cr, Quat{k0.x, k0.y, k1.x, k1.y}, qm[k], S[k], g3, B6);
+          if constexpr (COST) { if (!(cr >> 31)) cost += 0.5 * loss_value<LM>(lv, sq); }
         }
 #pragma unroll
         for (int c = 0; c < 6; ++c) G6[c] = B6[c];
@@ -447,14 +453,18 @@ __device__ __forceinline__ void lin_col_body(const ColLinArgs& a) {
 #pragma unroll
     for (int c = 0; c < 9; ++c) a.part[(size_t)c * plane + o] = acc[j][c];
   }
+  if constexpr (COST) {   // (the loop's last barrier has passed: the slots are free for the reduction)
+    const double t = block_sum_bcast(cost, &slots[0][0]);
+    if (threadIdx.x == 0) a.cost_part[blockIdx.x] = t;
+  }
 }
 // Registers at the compiler's choice (~200-250: two waves per SIMD, two workgroups per CU): asking for three waves spills the eighteen
 // row accumulators (76 B of scratch per lane) and costs 1010 us against 785 at C5.
-template <int F, int WM, int LM, bool FAST>
+template <int F, int WM, int LM, bool FAST, bool COST = false>
 #ifndef GSFM_K2C_ATTR
 #define GSFM_K2C_ATTR
 #endif
-__global__ void __launch_bounds__(GSFM_COLLIN_THREADS) GSFM_K2C_ATTR k_lin_col(ColLinArgs a) { lin_col_body<F, WM, LM, FAST>(a); }
+__global__ void __launch_bounds__(GSFM_COLLIN_THREADS) GSFM_K2C_ATTR k_lin_col(ColLinArgs a) { lin_col_body<F, WM, LM, FAST, COST>(a); }
 
 // gD[k] = sum_{c < NCH} part[block(k) * NCH + c][k mod RB]  (nine values per camera)
 // q != null: the partial sums are in the rows' body frames (sum gb, sum B): g = R_k sum gb, D = R_k (sum B) R_k^T

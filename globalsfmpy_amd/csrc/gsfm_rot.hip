@@ -47,7 +47,7 @@ void gsfm_rot_problem_destroy(gsfm_rot_problem* P) {
   if (!P) return;
   DeviceGuard g(P->device);
   P->timer.destroy();
-  P->pcg_graph.reset(); P->pcg2_graph.reset();
+  P->reset_pcg_graphs();
   if (P->dense_graph) (void)hipGraphExecDestroy(P->dense_graph);
   P->comps.drop_graph(); P->comps.drop_side();
   if (P->own_stream && P->stream) (void)hipStreamDestroy(P->stream);
@@ -61,7 +61,7 @@ gsfm_status gsfm_rot_set_stream(gsfm_rot_problem* P, void* s) {
   if (!P) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL problem");
   DeviceGuard g(P->device);
   if (P->own_stream && P->stream) { (void)hipStreamSynchronize(P->stream); (void)hipStreamDestroy(P->stream); }
-  P->pcg_graph.reset(); P->pcg_graph.unusable = false; P->pcg2_graph.reset(); P->pcg2_graph.unusable = false;
+  P->reset_pcg_graphs(); P->pcg_graph.unusable = false; P->pcg2_graph.unusable = false;
   if (P->dense_graph) { (void)hipGraphExecDestroy(P->dense_graph); P->dense_graph = nullptr; }
   P->comps.drop_graph(); P->comps.drop_side();
   if (s) { P->stream = (hipStream_t)s; P->own_stream = false; }
@@ -493,6 +493,60 @@ gsfm_status gsfm_rot_time_sweep_variants(gsfm_rot_problem* P, const double* rot,
   }
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return (gsfm_status)st;
+}
+
+namespace {
+// flag |= 1 if the n 8-byte words of a and b differ anywhere (gsfm_rot_trial_lin_check)
+__global__ void __launch_bounds__(GSFM_BLOCK) k_words_differ(const unsigned long long* __restrict__ a, const unsigned long long* __restrict__ b, size_t n, unsigned int* flag) {
+  bool diff = false;
+  for (size_t k = (size_t)blockIdx.x * GSFM_BLOCK + threadIdx.x; k < n; k += (size_t)gridDim.x * GSFM_BLOCK) diff |= a[k] != b[k];
+  if (__any(diff) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
+}  // namespace
+
+gsfm_status gsfm_rot_trial_lin_check(gsfm_rot_problem* P, const double* rot, const double* rot_trial, double* cost_out, int32_t* same_out) {
+  if (!P || !rot || !rot_trial || !cost_out || !same_out) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
+  if (!trial_lin_supported(P)) return (gsfm_status)fail(GSFM_ERR_UNSUPPORTED, "this problem has no fused trial evaluation");
+  DeviceGuard g(P->device);
+  const size_t N = P->n_cams;
+  if (int st = upload_state(P, rot)) return (gsfm_status)st;
+  if (int st = launch_lin(P, P->q.p)) return (gsfm_status)st;
+  // the linearisation at rot_aa, kept aside
+  DevBuf<double2> s0, s1, s2, sq;
+  DevBuf<double> sgD;
+  DevBuf<unsigned int> flag;
+  if (s0.alloc(P->h0.n) != hipSuccess || s1.alloc(P->h1.n) != hipSuccess || s2.alloc(P->h2.n) != hipSuccess || sq.alloc(P->q.n) != hipSuccess ||
+      sgD.alloc(P->gD.n) != hipSuccess || flag.alloc(2, true) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc snapshot");
+  HIPCHK_S(hipMemcpyAsync(s0.p, P->h0.p, 16 * P->h0.n, hipMemcpyDeviceToDevice, P->stream));
+  HIPCHK_S(hipMemcpyAsync(s1.p, P->h1.p, 16 * P->h1.n, hipMemcpyDeviceToDevice, P->stream));
+  HIPCHK_S(hipMemcpyAsync(s2.p, P->h2.p, 16 * P->h2.n, hipMemcpyDeviceToDevice, P->stream));
+  HIPCHK_S(hipMemcpyAsync(sq.p, P->q.p, 16 * P->q.n, hipMemcpyDeviceToDevice, P->stream));
+  HIPCHK_S(hipMemcpyAsync(sgD.p, P->gD.p, 8 * P->gD.n, hipMemcpyDeviceToDevice, P->stream));
+  // the trial point: x_trial / q_trial, as k_cam_step leaves them
+  HIPCHK_S(hipMemcpyAsync(P->aa_io.p, to_internal(P, rot_trial, 3), 24 * N, hipMemcpyHostToDevice, P->stream));
+  if (P->param_dim == 3) { HIPCHK_S(hipMemcpyAsync(P->x_trial.p, P->aa_io.p, 24 * N, hipMemcpyDeviceToDevice, P->stream)); }
+  else hipLaunchKernelGGL(k_cam_cache, dim3(grid_for(N)), dim3(GSFM_BLOCK), 0, P->stream, P->aa_io.p, P->n_cams, 3, (double2*)P->x_trial.p);
+  launch_cache(P, P->x_trial.p, P->q_trial.p);
+  if (int st = launch_lin(P, P->q_trial.p, nullptr, true, true)) return (gsfm_status)st;
+  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(GSFM_BLOCK), 0, P->stream, (const double*)P->cs.cost_part.p, (int)P->cs.n_wg, P->scal.p + SC_TRIAL);
+  if (int st = launch_cost(P, P->q_trial.p, SC_COST)) return (gsfm_status)st;
+  auto differ = [&](const void* a, const void* b, size_t bytes, int slot) {
+    hipLaunchKernelGGL(k_words_differ, dim3(1024), dim3(GSFM_BLOCK), 0, P->stream, (const unsigned long long*)a, (const unsigned long long*)b, bytes / 8, flag.p + slot);
+  };
+  differ(s0.p, P->h0.p, 16 * P->h0.n, 1); differ(s1.p, P->h1.p, 16 * P->h1.n, 1); differ(s2.p, P->h2.p, 16 * P->h2.n, 1);
+  differ(sq.p, P->q.p, 16 * P->q.n, 1); differ(sgD.p, P->gD.p, 8 * P->gD.n, 1);
+  // launch_lin's own linearisation at the trial point, against the fused one
+  if (int st = launch_lin(P, P->q_trial.p)) return (gsfm_status)st;
+  differ(P->h0_b.p, P->h0.p, 16 * P->h0.n, 0); differ(P->h1_b.p, P->h1.p, 16 * P->h1.n, 0); differ(P->h2_b.p, P->h2.p, 16 * P->h2.n, 0);
+  differ(P->gD_b.p, P->gD.p, 8 * P->gD.n, 0);
+  double h[SC_N];
+  if (int st = read_scalars(P, h)) return (gsfm_status)st;
+  unsigned int f[2] = {1, 1};
+  HIPCHK_S(hipMemcpy(f, flag.p, sizeof(f), hipMemcpyDeviceToHost));
+  cost_out[0] = h[SC_COST]; cost_out[1] = h[SC_TRIAL];
+  same_out[0] = f[0] == 0; same_out[1] = f[1] == 0;
+  if (int st = launch_lin(P, P->q.p)) return (gsfm_status)st;
+  return (gsfm_status)sync_check(P, "trial_lin_check");
 }
 
 gsfm_status gsfm_rot_time_kernels(gsfm_rot_problem* P, const double* rot, int32_t reps, double* out_ms4) {

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <exception>
+#include <functional>
 #include <stdexcept>
 #include <chrono>
 #include <cmath>
@@ -246,8 +247,13 @@ struct gsfm_rot_problem {
     hipGraphExec_t exec = nullptr;
     double tol = 0; int max_iters = 0, stall = 0, chunk = 0, collectives = 0; uint32_t coarse = 0;
     bool unusable = false, lap = false;
+    const void* planes = nullptr;   // the block planes (h0) the captured mat-vecs read
     void reset() { if (exec) (void)hipGraphExecDestroy(exec); exec = nullptr; }
   } pcg_graph, pcg2_graph;
+  // ... and the same two chunks captured on the spare set of block planes (trial_lin below): a fused trial that is accepted swaps the sets, and
+  // each set keeps its own graphs instead of a capture per accepted step.  `unusable` lives in pcg_graph / pcg2_graph for both.
+  PcgGraph pcg_graph_b, pcg2_graph_b;
+  void reset_pcg_graphs() { pcg_graph.reset(); pcg2_graph.reset(); pcg_graph_b.reset(); pcg2_graph_b.reset(); }
 
   bool q3 = false;            // the measurement planes hold three quaternion components, 24 B (kernels.hpp qrel_three: W_MATRIX problems of >= 1 M edges)
   EdgePlanes cost;            // cost-owned edges
@@ -268,6 +274,12 @@ struct gsfm_rot_problem {
   uint32_t G = 16;
   DevBuf<double2> h0, h1, h2, h3;
   DevBuf<double> h4;
+  // Fused trial evaluation (solver_lm.hpp, evaluate_trial; column-sorted layout, unsharded): a second set of body-frame block planes and of gD
+  // that a trial point is linearised into while its cost is taken.  An accepted trial swaps the two sets (lin_set flips); a rejected one leaves
+  // the current linearisation as it was.  Allocated at create when they fit into free memory (problem_create.hpp); empty otherwise.
+  DevBuf<double2> h0_b, h1_b, h2_b;
+  DevBuf<double> gD_b;
+  int lin_set = 0;   // which physical set h0..h2 / gD currently are (0: the ones allocated first); selects the PCG graphs of that set
   std::vector<uint32_t> h_cost_eid;  // host copies for weight re-upload
 
   // cameras
@@ -305,6 +317,7 @@ struct gsfm_rot_problem {
     double graph_freeze = -1.0;
     hipGraphExec_t graph = nullptr;
     bool graph_lap = false;
+    const void* graph_planes = nullptr;   // the block planes (h0) the captured assembly reads
     void drop_graph() { if (graph) (void)hipGraphExecDestroy(graph); graph = nullptr; }
     // the factorisations run on a stream of their own, beside the PCG solve of the large components (fork / join by events)
     hipStream_t side = nullptr;
@@ -320,6 +333,7 @@ struct gsfm_rot_problem {
   uint64_t loss_epoch = 0;                // bumped whenever the loss (and with it the choice of kernels) changes
   hipGraphExec_t dense_graph = nullptr;   // zero + assemble + blocked Cholesky + solve, captured once
   bool dense_graph_lap = false;           // form of the blocks the captured assemble kernel expects
+  const void* dense_graph_planes = nullptr;   // ... and the block planes (h0) it reads
   int nb_mv = 1, mv_reps = 1;
   bool packed = false;        // sharded: no rank holds an edge that leaves its slice (whole components per rank): every rank runs its own PCG, no collective in the loop
   bool pcg_local = false;     //   ... set while such a PCG runs: the mat-vec does not gather
@@ -351,6 +365,7 @@ struct gsfm_rot_problem {
     DevBuf<uint16_t> kcnt;
     uint32_t cbits = 0, cmax = 0;
     DevBuf<double> part;      // 9 planes of [n_wg * RB] (K2c; K3c uses the first three)
+    DevBuf<double> cost_part; // [n_wg]: the fused trial evaluation's cost partials (allocated with the spare set)
     // K3c's 2-byte delta-coded record (colsort_kernels.hpp, ColLayoutDev::k16): built where its escapes are rare
     bool k16_active = false;
     DevBuf<uint16_t> k16;

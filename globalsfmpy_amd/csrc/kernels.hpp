@@ -1008,7 +1008,7 @@ __device__ __forceinline__ void lin_entry_eval(const LinArgs& a, const LossView<
 #define GSFM_K2C_SC true   // K2c's transcendental coefficients in scalar registers (frees ~60 VGPRs; A/B: -DGSFM_K2C_SC=false)
 #endif
 template <int WM, int LM>
-__device__ __forceinline__ void lin_entry_body_aa(const LinArgs& a, const LossView<LM>& lv, uint32_t d, uint32_t cr, const Quat& qk, const Quat& qm, LinStreams S, double* gb3, double* B6) {
+__device__ __forceinline__ double lin_entry_body_aa(const LinArgs& a, const LossView<LM>& lv, uint32_t d, uint32_t cr, const Quat& qk, const Quat& qm, LinStreams S, double* gb3, double* B6) {
   const Quat qr = qrel_quat<WM>(S.r0, S.r1);
   const bool row_is_second = (cr >> 31) != 0;
   const Quat qi = row_is_second ? qm : qk, qj = row_is_second ? qk : qm;
@@ -1025,13 +1025,15 @@ __device__ __forceinline__ void lin_entry_body_aa(const LinArgs& a, const LossVi
   qmat(qj, Rj);
   mat3_mul(Jm, Rj, JR);
   apply_w_mat<WM>(S.W, JR, A);
-  const double rho1 = loss_rho1<LM, GSFM_K2C_SC>(lv, r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  const double sq = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+  const double rho1 = loss_rho1<LM, GSFM_K2C_SC>(lv, sq);
   const double sg = row_is_second ? rho1 : -rho1;
 #pragma unroll
   for (int x = 0; x < 3; ++x) gb3[x] = sg * (A[x] * r[0] + A[3 + x] * r[1] + A[6 + x] * r[2]);
   B6[0] = rho1 * (A[0] * A[0] + A[3] * A[3] + A[6] * A[6]); B6[1] = rho1 * (A[0] * A[1] + A[3] * A[4] + A[6] * A[7]);
   B6[2] = rho1 * (A[0] * A[2] + A[3] * A[5] + A[6] * A[8]); B6[3] = rho1 * (A[1] * A[1] + A[4] * A[4] + A[7] * A[7]);
   B6[4] = rho1 * (A[1] * A[2] + A[4] * A[5] + A[7] * A[8]); B6[5] = rho1 * (A[2] * A[2] + A[5] * A[5] + A[8] * A[8]);
+  return sq;   // |r|^2: the fused trial evaluation of K2c adds 1/2 rho(sq) of the edge's first-camera entry to the cost
 }
 template <int F, int WM, int LM>
 __device__ __forceinline__ void lin_rows_fast(const LinArgs& a) {

@@ -716,6 +716,24 @@ static gsfm_status problem_create_impl(uint32_t n_cams, uint64_t n_edges, const 
     }
     if (packed) P->coarse_want = 0;   // (its coarse matrix is an all-reduce per LM step and its use a decision taken from the iteration counts, which now differ from rank to rank)
   }
+  {  // the spare set of the fused trial evaluation (solver_lm.hpp, evaluate_trial): one GPU, column-sorted layout, the instantiations that have
+     // the fused kernel -- and only if it leaves GSFM_TRIAL_LIN_RESERVE_MB (default 4096) of the device's memory free; otherwise every trial
+     // point is evaluated by K1, as before.  At C5 it is 0.96 GB.
+    const int w = (P->wmode == W_MATRIX && P->q3) ? W_MATRIX3 : P->wmode;
+    if (!P->sharded && P->cs.active && col_lin_cost_kernel(P->functor, w, LM_MAGSAC)) {
+      const char* e = getenv("GSFM_TRIAL_LIN_RESERVE_MB");
+      const double reserve = (e && *e ? atof(e) : 4096.0) * 1048576.0;
+      const size_t need = 3 * sizeof(double2) * nd_planes + 8 * (9 * NP + (size_t)P->cs.n_wg);
+      size_t free_b = 0, total_b = 0;
+      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)free_b >= (double)need + reserve) {
+        if (P->h0_b.alloc(nd_planes) != hipSuccess || P->h1_b.alloc(nd_planes) != hipSuccess || P->h2_b.alloc(nd_planes) != hipSuccess ||
+            P->gD_b.alloc(9 * NP, true) != hipSuccess || P->cs.cost_part.alloc(P->cs.n_wg) != hipSuccess) {
+          P->h0_b.release(); P->h1_b.release(); P->h2_b.release(); P->gD_b.release(); P->cs.cost_part.release();
+        }
+      }
+      (void)hipGetLastError();
+    }
+  }
   *live = nullptr;
   *out = P;
   return GSFM_OK;

@@ -157,10 +157,10 @@ int run_component_step(gsfm_rot_problem* P, const gsfm_rot_options& o, double to
   const bool beside = !C.all_dense && C.side_state == 1;
   const hipStream_t ds = beside ? C.side : P->stream;
   const int tk = P->timer.begin(T_CG);
-  if (C.graph && (C.graph_lap != P->lin_is_lap || C.graph_freeze != comp_freeze_below(P))) C.drop_graph();
+  if (C.graph && (C.graph_lap != P->lin_is_lap || C.graph_freeze != comp_freeze_below(P) || C.graph_planes != P->h0.p)) C.drop_graph();
   if (beside) { HIPCHK(hipEventRecord(C.ev_fork, P->stream)); HIPCHK(hipStreamWaitEvent(ds, C.ev_fork, 0)); }
   if (!C.graph && o.pcg_hip_graph && !P->pcg_graph.unusable) {
-    C.graph_lap = P->lin_is_lap; C.graph_freeze = comp_freeze_below(P);
+    C.graph_lap = P->lin_is_lap; C.graph_freeze = comp_freeze_below(P); C.graph_planes = P->h0.p;
     hipGraph_t captured = nullptr;
     if (hipStreamBeginCapture(ds, hipStreamCaptureModeThreadLocal) == hipSuccess) {
       comps_enqueue_dense(P, ds);

@@ -64,9 +64,9 @@ int run_dense(gsfm_rot_problem* P, bool* used, bool plain = false) {
     return 0;
   }
   const int tk = P->timer.begin(T_CG);
-  if (P->dense_graph && P->dense_graph_lap != P->lin_is_lap) { (void)hipGraphExecDestroy(P->dense_graph); P->dense_graph = nullptr; }
+  if (P->dense_graph && (P->dense_graph_lap != P->lin_is_lap || P->dense_graph_planes != P->h0.p)) { (void)hipGraphExecDestroy(P->dense_graph); P->dense_graph = nullptr; }
   if (!P->dense_graph && !P->pcg_graph.unusable) {   // one launch per 32 columns: replay them as one graph
-    P->dense_graph_lap = P->lin_is_lap;
+    P->dense_graph_lap = P->lin_is_lap; P->dense_graph_planes = P->h0.p;
     hipGraph_t captured = nullptr;
     if (hipStreamBeginCapture(P->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
       enqueue();

@@ -69,12 +69,17 @@ template <int F, int W, int L> struct LinLauncher {
     else hipLaunchKernelGGL((k_lin<F, W, L, false>), dim3(grid), dim3(GSFM_BLOCK), 0, s, a);
   }
 };
+// The fused trial evaluation (K2c with the cost, colsort_kernels.hpp) exists for the instantiations the C5 workload runs: angle-axis, scalar or
+// three-component covariance whitening, a single cheap leaf or the nu = 3 MAGSAC loss.  Everything else keeps K1's sweep.
+constexpr bool col_lin_cost_kernel(int f, int w, int l) { return f == F_AA && (w == W_SCALAR || w == W_MATRIX3) && (l == LM_SIMPLE || l == LM_MAGSAC); }
 template <int F, int W, int L> struct ColLinLauncher {   // K2c (column-sorted layout: Laplacian-capable functors only)
   static void go(const ColLinArgs& a, int grid, hipStream_t s) {
     if constexpr (F == F_AA || F == F_QCOS) {
       const dim3 g(grid), b(GSFM_COLLIN_THREADS);
       if constexpr (L != LM_PROGRAM) {
-        if (!a.lin.rho_ext && a.lin.fast_ok) hipLaunchKernelGGL((k_lin_col<F, W, L, true>), g, b, 0, s, a);
+        if (a.cost_part) {   // the fused trial evaluation: only the instantiations the host predicate (trial_lin_supported) lets through exist
+          if constexpr (col_lin_cost_kernel(F, W, L)) hipLaunchKernelGGL((k_lin_col<F, W, L, true, true>), g, b, 0, s, a);
+        } else if (!a.lin.rho_ext && a.lin.fast_ok) hipLaunchKernelGGL((k_lin_col<F, W, L, true>), g, b, 0, s, a);
         else hipLaunchKernelGGL((k_lin_col<F, W, L, false>), g, b, 0, s, a);
       } else hipLaunchKernelGGL((k_lin_col<F, W, L, false>), g, b, 0, s, a);
     }
@@ -187,7 +192,7 @@ int prepare_loss(gsfm_rot_problem* P, const gsfm_loss_node* prog, int n) {
 // exchange's, say), and a communicator that has just failed may answer differently from now on (csrc/gsfm_peer.hip: its fallback collectives) --
 // the next solve captures afresh, through the callbacks.
 int comm_failed(gsfm_rot_problem* P, const char* what) {
-  P->pcg_graph.reset(); P->pcg2_graph.reset();
+  P->reset_pcg_graphs();
   P->shard.flags &= ~GSFM_SHARD_CAPTURABLE;   // ... and whatever it falls back to (host-staged collectives, say) is not assumed to be capturable: plain launches from now on
   return fail(GSFM_ERR_COMM, what);
 }
@@ -280,7 +285,7 @@ int refresh_external_rho(gsfm_rot_problem* P, const double2* q) {
 // optional per-edge outputs of K1 (device pointers, problem edge order)
 struct CostOutputs { double2* srho = nullptr; double2* rho12 = nullptr; double* rho1 = nullptr; double* r = nullptr; };
 
-int launch_lin(gsfm_rot_problem* P, const double2* q, const double* go = nullptr);
+int launch_lin(gsfm_rot_problem* P, const double2* q, const double* go = nullptr, bool fused = false, bool spare = false);
 
 // K1: cost at quaternion cache q -> scal[slot] (all-reduced when sharded)
 // reduce = false: the caller sums the sweep's partials itself (k_lm_decide; unsharded problems only)
@@ -314,8 +319,22 @@ int launch_cost(gsfm_rot_problem* P, const double2* q, int slot, const CostOutpu
   return all_reduce(P, P->scal.p + slot, 1);
 }
 
+// The fused trial evaluation (K2c with the cost, colsort_kernels.hpp): possible for this problem and loss right now?  (Unsharded, column-sorted,
+// spare set allocated, a native loss on K2c's body-frame fast path with a fused instantiation, no sigma-consensus pass pending.)
+// GSFM_TRIAL_LIN=0 switches it off: K1 evaluates every trial point, as before (A/B, tests).  Read at every solve.
+bool trial_lin_supported(const gsfm_rot_problem* P) {
+  const char* e = getenv("GSFM_TRIAL_LIN");
+  if (e && *e && atoi(e) == 0) return false;
+  if (!P->h0_b.p || !P->cs.cost_part.p || P->sharded || P->cb || !P->cs.active || !P->lap || P->sigma_pending_cost || P->sigma_pending_lin || !k2_fast_path(P)) return false;
+  const int w = (P->wmode == W_MATRIX && P->q3) ? W_MATRIX3 : P->wmode;
+  return col_lin_cost_kernel(P->functor, w, loss_mode(P));
+}
+
 // K2: linearise at q -> gD (all-gathered), H blocks
-int launch_lin(gsfm_rot_problem* P, const double2* q, const double* go) {
+// fused (trial_lin_supported only): K2c also writes the cost partials of q to cs.cost_part (the caller sums them); spare: into the spare set
+// (h0_b..h2_b, gD_b) -- the current linearisation, q_lin and the blocks the captured graphs read stay as they are (accept_trial_lin swaps).
+int launch_lin(gsfm_rot_problem* P, const double2* q, const double* go, bool fused, bool spare) {
+  if (fused && !trial_lin_supported(P)) return fail(GSFM_ERR_UNSUPPORTED, "fused trial evaluation without its preconditions");
   if (P->cb) { if (int st = refresh_external_rho(P, q)) return st; }
   LinArgs a{};
   a.n_rows = P->n_rows; a.row_base = P->own_begin; a.G = P->G; a.row_ptr = P->row_ptr.p; a.col = P->col.p; a.eid = P->dir.eid.p;
@@ -324,20 +343,31 @@ int launch_lin(gsfm_rot_problem* P, const double2* q, const double* go) {
   if (P->sigma_pending_lin) { a.sigma = P->sigma; a.sigma.on = 1; P->sigma_pending_lin = false; }
   if (!P->lap && !P->h3.p && (P->h3.alloc(P->dir.n) != hipSuccess || P->h4.alloc(P->dir.n) != hipSuccess)) return fail(GSFM_ERR_HIP, "allocating the general normal-equation blocks failed");
   a.h0 = P->h0.p; a.h1 = P->h1.p; a.h2 = P->h2.p; a.h3 = P->h3.p; a.h4 = P->h4.p; a.gD = P->gD.p; a.lap = P->lap;
-  P->lin_is_lap = P->lap; P->q_lin = q;
+  if (spare) { a.h0 = P->h0_b.p; a.h1 = P->h1_b.p; a.h2 = P->h2_b.p; a.gD = P->gD_b.p; }
+  else { P->lin_is_lap = P->lap; P->q_lin = q; }
   const int tk = P->timer.begin(T_LIN);
   if (P->cs.active) {
     ColLinArgs ca{};
-    ca.lin = a; ca.L = P->cs.dev(); ca.part = P->cs.part.p;
+    ca.lin = a; ca.L = P->cs.dev(); ca.part = P->cs.part.p; ca.cost_part = fused ? P->cs.cost_part.p : nullptr;
     if (dispatch<ColLinArgs, ColLinLauncher>(P, ca, (int)P->cs.n_wg)) return fail(GSFM_ERR_UNSUPPORTED, "no kernel for this error type");
     // (the fast path of the angle-axis family sums in the rows' body frames: the finishing kernel rotates -- same predicate as ColLinLauncher's choice)
     const bool body = col_lin_body_frame(P->functor, loss_mode(P) != LM_PROGRAM && !a.rho_ext && a.fast_ok);
-    hipLaunchKernelGGL(k_lin_col_finish, dim3(grid_for(P->n_rows)), dim3(GSFM_BLOCK), 0, P->stream, P->n_rows, P->own_begin, P->cs.nch, P->cs.n_wg, (const double*)P->cs.part.p, P->gD.p,
+    hipLaunchKernelGGL(k_lin_col_finish, dim3(grid_for(P->n_rows)), dim3(GSFM_BLOCK), 0, P->stream, P->n_rows, P->own_begin, P->cs.nch, P->cs.n_wg, (const double*)P->cs.part.p, a.gD,
                        body ? q : (const double2*)nullptr);
   } else if (dispatch<LinArgs, LinLauncher>(P, a, grid_for((size_t)P->n_rows * P->G))) return fail(GSFM_ERR_UNSUPPORTED, "no kernel for this error type");
   P->timer.end(tk);
+  if (spare) return 0;   // (unsharded only: nothing to gather)
   P->have_lin = true;
   return all_gather(P, P->gD.p, (size_t)P->shard.slice_width * 9);
+}
+
+// An accepted trial point that was linearised into the spare set (launch_lin, spare): the sets swap roles.  The quaternions the blocks were
+// taken at are q_trial's values, which the caller has just copied into q -- the buffer every captured graph rotates with.
+void accept_trial_lin(gsfm_rot_problem* P) {
+  std::swap(P->h0.p, P->h0_b.p); std::swap(P->h1.p, P->h1_b.p); std::swap(P->h2.p, P->h2_b.p); std::swap(P->gD.p, P->gD_b.p);
+  P->lin_set ^= 1;
+  P->lin_is_lap = P->lap; P->q_lin = P->q.p;
+  P->have_lin = true;
 }
 
 void launch_prep(gsfm_rot_problem* P, const gsfm_rot_options& o, double radius, bool init_scale, const double* radius_dev = nullptr, bool reduce = true) {

@@ -56,7 +56,31 @@ int read_scalars(gsfm_rot_problem* P, double* h) {
 
 // The trial point of a host-controlled step: step, cost sweep and the look at the scalars.  With the mailbox (unsharded, native loss) the
 // three single-workgroup kernels behind the sweep -- two reductions and the post -- are one (k_trial_post).
-int evaluate_trial(gsfm_rot_problem* P, bool inexact, double* h) {
+// fuse_if (only where trial_lin_supported): the step's sums are looked at first, and if fuse_if(h) says the point will most likely be
+// accepted, it is evaluated by the fused K2c into the spare set (*fused = true) instead of by K1 -- the linearisation an accepted point needs
+// is then already done (accept_trial_lin).  One more look (~10 us) against K1's sweep (~150 us at C5).
+int evaluate_trial(gsfm_rot_problem* P, bool inexact, double* h, const std::function<bool(const double*)>& fuse_if = nullptr, bool* fused = nullptr) {
+  if (fused) *fused = false;
+  if (fuse_if && fused && trial_lin_supported(P)) {
+    launch_step(P, inexact);
+    if (int st = read_scalars(P, h)) return st;
+    const bool f = fuse_if(h);
+    const double* cpart = P->part_cost.p;
+    int ncp = P->nb_cost;
+    if (f) {
+      if (int st = launch_lin(P, P->q_trial.p, nullptr, true, true)) return st;
+      cpart = P->cs.cost_part.p; ncp = (int)P->cs.n_wg;
+      *fused = true;
+    } else if (int st = launch_cost(P, P->q_trial.p, SC_TRIAL, CostOutputs(), false)) return st;
+    if (mail_usable(P)) {   // (the step's sums again, from the same partials: the same bits in the same scalars)
+      hipLaunchKernelGGL(k_trial_post, dim3(1), dim3(GSFM_BLOCK), 0, P->stream, P->scal.p, (int)SC_STEP, (int)SC_TRIAL, (const double*)P->part_cam.p, P->nb_cam,
+                         cpart, ncp, (int)SC_N, P->mail_dev, P->mail_count.p, inexact ? (int)SC_ZL8 : -1);
+      P->mail_expected += 1.0;
+      return mail_wait(P, h, SC_N * sizeof(double));
+    }
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(GSFM_BLOCK), 0, P->stream, cpart, ncp, P->scal.p + SC_TRIAL);
+    return read_scalars(P, h);
+  }
   if (!P->sharded && !P->cb && !P->sigma_pending_cost && mail_usable(P)) {
     launch_step(P, inexact, false);
     if (int st = launch_cost(P, P->q_trial.p, SC_TRIAL, CostOutputs(), false)) return st;
@@ -191,8 +215,17 @@ int lm_solve(gsfm_rot_problem* P, const gsfm_rot_options& o_in, gsfm_rot_summary
   // Init + IterationZero
   hipLaunchKernelGGL(k_cam_norm, dim3(P->nb_cam), dim3(GSFM_BLOCK), 0, P->stream, P->x.p, P->active.p, P->n_cams, P->param_dim, P->part_cam.p);
   hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(GSFM_BLOCK), 0, P->stream, P->part_cam.p, P->nb_cam, P->scal.p + SC_XNORM2);
-  if (int st = launch_cost(P, P->q.p, SC_COST)) return st;
-  if (int st = launch_lin(P, P->q.p)) return st;
+  // Fused trial evaluations (solver_launch.hpp, trial_lin_supported): the start point's cost comes out of its linearisation, and a trial point
+  // that will most likely be accepted is evaluated by that linearisation too (evaluate_trial).  The summary still counts what Ceres counts:
+  // a cost evaluation at every trial point and a linearisation at every accepted one.
+  const bool trial_lin = trial_lin_supported(P);
+  if (trial_lin) {
+    if (int st = launch_lin(P, P->q.p, nullptr, true)) return st;
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(GSFM_BLOCK), 0, P->stream, (const double*)P->cs.cost_part.p, (int)P->cs.n_wg, P->scal.p + SC_COST);
+  } else {
+    if (int st = launch_cost(P, P->q.p, SC_COST)) return st;
+    if (int st = launch_lin(P, P->q.p)) return st;
+  }
   sum->num_residual_sweeps++; sum->num_linearizations++;
   launch_prep(P, o, radius, true);
   bool prep_valid = true;
@@ -257,6 +290,36 @@ int lm_solve(gsfm_rot_problem* P, const gsfm_rot_options& o_in, gsfm_rot_summary
   constexpr double contraction_max = 0.3;
   bool forcing_live = forcing, loose_applied = false;
   double prev_accepted_norm = -1.0;
+  // The tolerance an evaluated loose step of size sn (and block-Jacobi estimate zl8, k_cam_step's sixth sum) needs to stand (see the
+  // refinement loop below); *cams_ok: no camera is left too far from its exact step.
+  constexpr double zcap = 100.0;   // (10 and "off" gave the same 420 fuzz outcomes; 10 cost C5 13 iterations: profiles/r05_fuzz_forcing.txt)
+  auto loose_tau_need = [&](double sn, double zl8, double tau_now, bool* cams_ok) {
+    double tn = std::fmax(kappa * sn / sqrt_n, eps_rad / std::fmax(sn / sqrt_n, 1e-300));
+    // ... and no single camera may be left far from its exact step: block-Jacobi's estimate of what each camera's step still lacks
+    // (k_cam_step's sixth sum, a smooth maximum in radians) is held against 10 x the rms tolerance -- the energy norm does not see a
+    // camera whose weights have all but vanished (kernels.hpp, StepArgs::Minv)
+    const double zmax = std::pow(std::fmax(zl8, 0.0), 0.125) * (P->param_dim == 4 ? 2.0 : 1.0);
+    *cams_ok = zmax <= zcap * eps_rad;
+    if (!*cams_ok) tn = std::fmin(tn, 0.5 * tau_now * (zcap * eps_rad / zmax));
+    return tn;
+  };
+  // Speculation policy of the fused trial evaluation: a trial point is linearised while its cost is taken only where it will most likely be
+  // accepted and the run go on -- the previous step was accepted (or this is the first), the model decrease is well above the function-tolerance
+  // stop and the step above the parameter-tolerance stop, and a loose step is one the refinement below would let stand as it is.  The
+  // terminating trial and the trials behind a rejection keep K1's sweep; a wrong guess costs a linearisation, never a different answer.
+  bool prev_accepted = true;
+  bool trial_fused = false;   // the last evaluate_trial linearised its point into the spare set
+  int cg_now = 0; double tau_now = 0.0; bool loose_now = false;   // (what the fuse_if below judges a loose step by)
+  const std::function<bool(const double*)> fuse_if = [&](const double* hh) -> bool {
+    const double mcc = -0.5 * hh[SC_STEP] + 0.5 * hh[SC_STEP + 1] + 0.5 * hh[SC_STEP + 2];
+    const double sn = std::sqrt(hh[SC_STEP + 3]), pt = o.parameter_tolerance * (x_norm + o.parameter_tolerance);
+    if (!(std::isfinite(mcc) && mcc > 2.0 * o.function_tolerance * x_cost) || !(sn > 2.0 * pt)) return false;
+    if (!loose_now) return true;
+    if (o.pcg_forcing == 2 || (P->loss_staircase && cg_now > 64 && o.pcg_forcing != 3)) return false;
+    bool cams_ok = false;
+    const double tn = loose_tau_need(sn, hh[SC_ZL8], tau_now, &cams_ok);
+    return cams_ok && tau_now <= 1.5 * tn;
+  };
   while (true) {
     if (iteration >= o.max_num_iterations) return finish(GSFM_TERM_NO_CONVERGENCE);
     if (last_successful && !gmax_deferred && gmax <= o.gradient_tolerance) return finish(GSFM_TERM_GRADIENT_TOLERANCE);
@@ -422,7 +485,7 @@ int lm_solve(gsfm_rot_problem* P, const gsfm_rot_options& o_in, gsfm_rot_summary
           if (gmax <= o.gradient_tolerance) { --iteration; return finish(GSFM_TERM_GRADIENT_TOLERANCE); }
         }
         if (P->packed) { if (int st = packed_exchange(P)) return st; }
-        if (int st = evaluate_trial(P, false, h)) return st;
+        if (int st = evaluate_trial(P, false, h, nullptr, &trial_fused)) return st;
         int info = 0;
         std::memcpy(&info, &h[SC_DENSE_INFO], sizeof(int));
         if (P->packed) info = h[SC_COMPBAD] != 0.0;   // (any rank's: all of them take the fallback together)
@@ -445,7 +508,8 @@ int lm_solve(gsfm_rot_problem* P, const gsfm_rot_options& o_in, gsfm_rot_summary
         }
       }
       if (P->packed && !dense_used) { if (int st = packed_exchange(P)) return st; }
-      if (int st = evaluate_trial(P, !dense_used && loose, h)) return st;
+      loose_now = !dense_used && loose && cg_rel > o.cg_relative_tolerance; cg_now = cg; tau_now = tau;
+      if (int st = evaluate_trial(P, !dense_used && loose, h, trial_lin && prev_accepted ? fuse_if : nullptr, &trial_fused)) return st;
       if (P->packed && attempt == 0 && h[SC_COMPBAD] != 0.0) {   // another rank's component factorisation broke down: it solves this step again by PCG, and so does everybody (one more exchange on every rank)
         (void)hipMemsetAsync(P->scal.p + SC_COMPBAD, 0, sizeof(double), P->stream);
         cg_spent += cg; cg = 0;
@@ -481,14 +545,8 @@ int lm_solve(gsfm_rot_problem* P, const gsfm_rot_options& o_in, gsfm_rot_summary
           if (sn <= 0.5 * pt || std::fabs(cc) <= 0.5 * ft) { sum->num_inexact_steps++; break; }            // terminates, as the exact step would
           if (sn <= 2.0 * pt || std::fabs(cc) <= 2.0 * ft || cc / mcc <= std::fmax(o.min_relative_decrease, 0.25)) tight = true;
           else {
-            tau_need = std::fmax(kappa * sn / sqrt_n, eps_rad / std::fmax(sn / sqrt_n, 1e-300));
-            // ... and no single camera may be left far from its exact step: block-Jacobi's estimate of what each camera's step still lacks
-            // (k_cam_step's sixth sum, a smooth maximum in radians) is held against 10 x the rms tolerance -- the energy norm does not see a
-            // camera whose weights have all but vanished (kernels.hpp, StepArgs::Minv)
-            const double zmax = std::pow(std::fmax(h[SC_ZL8], 0.0), 0.125) * (P->param_dim == 4 ? 2.0 : 1.0);
-            constexpr double zcap = 100.0;   // (10 and "off" gave the same 420 fuzz outcomes; 10 cost C5 13 iterations: profiles/r05_fuzz_forcing.txt)
-            const bool cams_ok = zmax <= zcap * eps_rad;
-            if (!cams_ok) tau_need = std::fmin(tau_need, 0.5 * tau * (zcap * eps_rad / zmax));
+            bool cams_ok = false;
+            tau_need = loose_tau_need(sn, h[SC_ZL8], tau, &cams_ok);
             if (cams_ok && tau <= 1.5 * tau_need) { sum->num_inexact_steps++; break; }
             if (tau_need <= 4.0 * o.cg_relative_tolerance || pass == 3) tight = true;
           }
@@ -499,7 +557,8 @@ int lm_solve(gsfm_rot_problem* P, const gsfm_rot_options& o_in, gsfm_rot_summary
           if (int st = run_dense(P, &dense_used)) return st;
           if (dense_used) pcg_dearer_than_cholesky = true;
         }
-        if (int st = evaluate_trial(P, !dense_used && loose, h)) return st;
+        loose_now = !dense_used && loose && cg_rel > o.cg_relative_tolerance; cg_now = cg; tau_now = tau;
+        if (int st = evaluate_trial(P, !dense_used && loose, h, trial_lin && prev_accepted ? fuse_if : nullptr, &trial_fused)) return st;
         sum->num_forcing_refinements++;
         if (!loose) break;
       }
@@ -533,6 +592,7 @@ int lm_solve(gsfm_rot_problem* P, const gsfm_rot_options& o_in, gsfm_rot_summary
     const double model_cost_change = -0.5 * eta_g + 0.5 * eta_r + 0.5 * eta_L;
     const bool valid = std::isfinite(model_cost_change) && model_cost_change > 0.0;
     if (!valid) {  // HandleInvalidStep
+      prev_accepted = false;
       if (++num_invalid >= 5) return finish(GSFM_TERM_FAILURE);
       radius /= decrease_factor; decrease_factor *= 2.0;
       sum->num_unsuccessful_steps++;
@@ -574,8 +634,10 @@ int lm_solve(gsfm_rot_problem* P, const gsfm_rot_options& o_in, gsfm_rot_summary
       HIPCHK(hipMemcpyAsync(P->q.p, P->q_trial.p, 32 * (size_t)P->n_cams, hipMemcpyDeviceToDevice, P->stream));
       x_norm = std::sqrt(h[SC_STEP + 4]);
       x_cost = cand_cost;  // Ceres re-evaluates at the accepted point: same value
-      if (int st = launch_lin(P, P->q.p)) return st;
+      if (trial_fused) accept_trial_lin(P);   // (linearised while its cost was taken: the sets swap)
+      else if (int st = launch_lin(P, P->q.p)) return st;
       sum->num_residual_sweeps++; sum->num_linearizations++;
+      prev_accepted = true;
       radius = radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * rel_dec - 1.0, 3));   // (std::pow as Ceres' LevenbergMarquardtStrategy::StepAccepted and the oracle; k_lm_decide: the same value through lm_cube)
       radius = std::fmin(o.max_trust_region_radius, radius);
       decrease_factor = 2.0;
@@ -601,6 +663,7 @@ int lm_solve(gsfm_rot_problem* P, const gsfm_rot_options& o_in, gsfm_rot_summary
     } else {  // HandleUnsuccessfulStep
       radius /= decrease_factor; decrease_factor *= 2.0;
       sum->num_unsuccessful_steps++;
+      prev_accepted = false;
     }
     record(x_cost, cost_change, step_norm, rel_dec, cg);
   }

@@ -215,10 +215,10 @@ int run_pcg(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double e
     return 0;
   };
   // The chunk between two host checks as one hipGraph launch: 4 * chunk dependent kernels whose arguments never change.
-  auto& G = P->pcg_graph;
-  bool graph = o.pcg_hip_graph && (!P->sharded || P->pcg_local || graph_collectives_ok(P, o)) && chunk % 2 == 0 && !G.unusable;
+  auto& G = P->lin_set ? P->pcg_graph_b : P->pcg_graph;   // (the chunk captured on the block planes the current linearisation lives in)
+  bool graph = o.pcg_hip_graph && (!P->sharded || P->pcg_local || graph_collectives_ok(P, o)) && chunk % 2 == 0 && !P->pcg_graph.unusable;
   // (the tolerance is device-resident, CgScalars::tol: a captured chunk serves every tolerance)
-  if (graph && (!G.exec || G.max_iters != a.max_iters || G.stall != a.stall_limit || G.chunk != chunk || G.lap != P->lin_is_lap || G.coarse != a.coarse_n)) {
+  if (graph && (!G.exec || G.max_iters != a.max_iters || G.stall != a.stall_limit || G.chunk != chunk || G.lap != P->lin_is_lap || G.coarse != a.coarse_n || G.planes != P->h0.p)) {
     G.reset();
     hipGraph_t captured = nullptr;
     if (hipStreamBeginCapture(P->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
@@ -228,11 +228,11 @@ int run_pcg(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double e
       G.collectives = P->n_collectives - c0;            // captured, not issued: counted per replay below
       P->n_collectives = c0; P->n_pcg_collectives = p0;
       if (st == 0 && e == hipSuccess && captured && hipGraphInstantiate(&G.exec, captured, nullptr, nullptr, 0) == hipSuccess) {
-        G.tol = a.tol; G.max_iters = a.max_iters; G.stall = a.stall_limit; G.chunk = chunk; G.lap = P->lin_is_lap; G.coarse = a.coarse_n;
+        G.tol = a.tol; G.max_iters = a.max_iters; G.stall = a.stall_limit; G.chunk = chunk; G.lap = P->lin_is_lap; G.coarse = a.coarse_n; G.planes = P->h0.p;
       } else { G.exec = nullptr; }
       if (captured) (void)hipGraphDestroy(captured);
     }
-    if (!G.exec) { (void)hipGetLastError(); G.unusable = true; graph = false; }  // e.g. a stream that cannot be captured: plain launches
+    if (!G.exec) { (void)hipGetLastError(); P->pcg_graph.unusable = true; graph = false; }  // e.g. a stream that cannot be captured: plain launches
   }
   int launched = 0, chunks = 1;
   PcgStagnation stagnation;
@@ -341,9 +341,9 @@ int run_pcg2(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double 
     P->timer.end(tk);
   }
   const bool mail = mail_usable(P);
-  auto& G = P->pcg2_graph;
-  bool graph = o.pcg_hip_graph && (!P->sharded || graph_collectives_ok(P, o)) && chunk % 2 == 0 && !G.unusable && !P->pcg_graph.unusable;
-  if (graph && (!G.exec || G.max_iters != c.max_iters || G.chunk != chunk || G.lap != P->lin_is_lap)) {
+  auto& G = P->lin_set ? P->pcg2_graph_b : P->pcg2_graph;   // (as run_pcg)
+  bool graph = o.pcg_hip_graph && (!P->sharded || graph_collectives_ok(P, o)) && chunk % 2 == 0 && !P->pcg2_graph.unusable && !P->pcg_graph.unusable;
+  if (graph && (!G.exec || G.max_iters != c.max_iters || G.chunk != chunk || G.lap != P->lin_is_lap || G.planes != P->h0.p)) {
     G.reset();
     hipGraph_t captured = nullptr;
     if (hipStreamBeginCapture(P->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
@@ -355,11 +355,11 @@ int run_pcg2(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double 
       G.collectives = P->n_collectives - c0;
       P->n_collectives = c0; P->n_pcg_collectives = p0;
       if (st == 0 && e == hipSuccess && captured && hipGraphInstantiate(&G.exec, captured, nullptr, nullptr, 0) == hipSuccess) {
-        G.tol = c.tol; G.max_iters = c.max_iters; G.chunk = chunk; G.lap = P->lin_is_lap;
+        G.tol = c.tol; G.max_iters = c.max_iters; G.chunk = chunk; G.lap = P->lin_is_lap; G.planes = P->h0.p;
       } else { G.exec = nullptr; }
       if (captured) (void)hipGraphDestroy(captured);
     }
-    if (!G.exec) { (void)hipGetLastError(); G.unusable = true; graph = false; }
+    if (!G.exec) { (void)hipGetLastError(); P->pcg2_graph.unusable = true; graph = false; }
   }
   int chunks = 1;
   PcgStagnation stagnation;

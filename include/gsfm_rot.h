@@ -446,6 +446,12 @@ gsfm_status gsfm_rot_linearize(gsfm_rot_problem* p, const double* rot_aa,
                                double* gradient, double* diag_blocks, double* cost);
 /* y = (J~^T J~) v for the last linearisation (kernel K3), 3 per camera. */
 gsfm_status gsfm_rot_normal_matvec(gsfm_rot_problem* p, const double* v, double* y);
+/* Check of the fused trial evaluation (K2c with the cost; column-sorted layout, one GPU): linearises at rot_aa, then evaluates rot_trial
+ * the way an LM trial point is fused -- into the spare set of blocks -- and K1's way.  cost_out[0] = K1's cost at rot_trial,
+ * cost_out[1] = the fused one; same_out[0] = 1 if the fused blocks and gD equal launch_lin's at rot_trial bit for bit, same_out[1] = 1 if
+ * the linearisation at rot_aa (blocks, gD, quaternions) came through the (not accepted) trial unchanged.  Leaves the problem linearised
+ * at rot_aa.  GSFM_ERR_UNSUPPORTED where the problem has no fused evaluation (no spare set, kernel or loss without one, GSFM_TRIAL_LIN=0). */
+gsfm_status gsfm_rot_trial_lin_check(gsfm_rot_problem* p, const double* rot_aa, const double* rot_trial, double* cost_out, int32_t* same_out);
 
 /* ------------------------------------------------------------------------- */
 /* The step after the solve + the edge statistic ("next" row f-3 of the scope)  */
