@@ -203,6 +203,8 @@ def load_library():
     lib.gsfm_rot_locality_order.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, _U32P]; lib.gsfm_rot_locality_order.restype = C.c_int32
     lib.gsfm_rot_edge_sq_norms.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, _DP, _DP, _DP, C.c_double, _DP, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), _DP]
     lib.gsfm_rot_edge_sq_norms.restype = C.c_int
+    lib.gsfm_rot_dense_factor_check.argtypes = [C.c_int32, C.c_uint32, _U32P, _DP, _DP, C.POINTER(C.c_int32), _DP, _DP, C.POINTER(C.c_int32)]
+    lib.gsfm_rot_dense_factor_check.restype = C.c_int
     lib.gsfm_rot_init_spanning_tree.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, _DP, C.POINTER(C.c_int32), _DP, C.POINTER(C.c_int64),
                                                 _U32P, _U32P, _U32P, _DP]
     lib.gsfm_rot_init_spanning_tree.restype = C.c_int

@@ -2,6 +2,7 @@
 #pragma once
 #include "kernels.hpp"
 #include "dense_kernels.hpp"
+#include "comp_rest.hpp"
 
 namespace gsfm {
 
@@ -20,13 +21,15 @@ struct CompMap {
 // scene that converged dozens of LM iterations ago while the batch iterates on.  One workgroup per component over its cameras in a fixed
 // order: the same decision on every run.  (Its A tiles are then neither assembled nor factorised, its step is zero.)
 // Under a SMOOTH loss a component is moreover put to rest for the remainder of the solve once its EXACT step -- the factorisation's, measured
-// by k_comp_scatter: the largest camera update of the component in radians -- has been below `freeze_below` (1e-10 rad): the scenes of a batch
+// by k_comp_scatter: the largest camera update of the component in radians -- has been below `freeze_below` (1e-10 rad) while the damping did
+// not make it small (comp_rest.hpp): the scenes of a batch
 // are independent problems, a scene whose Newton step is 1e-10 rad has 1e-9 rad left to go at most (steps near convergence contract), three
 // orders inside the parity bar, and factorising it 30 more times while another scene iterates on is what made C4 cost twice the slow scene
 // alone.  Never under the MAGSAC losses (freeze_below = 0): there an iterate 1e-10 rad off can sit in another table cell.
 __global__ void __launch_bounds__(GSFM_BLOCK) k_comp_activity(const uint32_t* __restrict__ cam_ptr, const uint32_t* __restrict__ cams, const double* __restrict__ b,
                                                               const double* __restrict__ Minv, const double* zbound, double floor2, int* active,
-                                                              unsigned long long* stepmax, unsigned long long* stepprev, int* frozen, double freeze_below, const double* freeze_ok) {
+                                                              unsigned long long* stepmax, unsigned long long* stepprev, double* steprad, const int* info, int* frozen,
+                                                              double freeze_below, const double* radius) {
   __shared__ double lds[8];
   const uint32_t c = blockIdx.x;
   double v = 0.0;
@@ -41,18 +44,18 @@ __global__ void __launch_bounds__(GSFM_BLOCK) k_comp_activity(const uint32_t* __
   if (threadIdx.x == 0) {
     const double B = *zbound;
     int fr = frozen[c];
-    // cur: last iteration's exact step of this component (+inf before the first and after an iteration in which it was idle -- an idle component
-    // was not factorised, nothing was measured, and block-Jacobi's estimate, which idles it, is no bound on an ill-conditioned scene's true step);
-    // prev: the one measured before it.  A component goes to rest when its step is below the threshold AND there is evidence that it is small
-    // because the scene has converged, not because the shared trust region has collapsed under ANOTHER scene's rejections (round-5 advisor: a
-    // damped step can fall below any threshold on an unconverged scene): either the step has at least halved against the previous measurement --
-    // steps near convergence contract fast (C4: by 4-10 x per accepted step), a damping-limited scene's barely move, and a REJECTED iteration
-    // re-solves the same point (ratio ~ 1) -- or the damping is no stronger than at the start of the solve (*freeze_ok: radius >= its initial value).
-    const double cur = __longlong_as_double((long long)stepmax[c]), prev = __longlong_as_double((long long)stepprev[c]);
-    const bool contracted = prev < __longlong_as_double(0x7ff0000000000000ll) && cur <= 0.5 * prev;
-    if (!fr && freeze_below > 0.0 && cur <= freeze_below && (contracted || *freeze_ok != 0.0)) fr = 1;
+    // cur: last iteration's exact step of this component, measured at the trust radius steprad[2c] (+inf before the first, after an iteration in
+    // which it was idle -- an idle component was not factorised, nothing was measured, and block-Jacobi's estimate, which idles it, is no bound
+    // on an ill-conditioned scene's true step -- and after a failed factorisation: k_comp_scatter measures nothing then); prev: the one measured
+    // before it, at steprad[2c + 1].  A component goes to rest when its step is below the threshold AND there is evidence that it is small
+    // because the scene has converged, not because the shared trust region has collapsed under ANOTHER scene's rejections or the caller
+    // started at a small radius (a damped step can fall below any threshold on an unconverged scene): comp_rest.hpp, comp_may_rest.
+    const unsigned long long inf_bits = 0x7ff0000000000000ull, cur_bits = info[c] != 0 ? inf_bits : stepmax[c];
+    const double cur = __longlong_as_double((long long)cur_bits), prev = __longlong_as_double((long long)stepprev[c]);
+    if (!fr && comp_may_rest(cur, steprad[2 * c], prev, steprad[2 * c + 1], freeze_below)) fr = 1;
     const int act = !fr && (!(B > 0.0) || t * B > floor2);
-    frozen[c] = fr; stepprev[c] = stepmax[c]; stepmax[c] = act ? 0ull : 0x7ff0000000000000ull;
+    frozen[c] = fr; stepprev[c] = cur_bits; stepmax[c] = act ? 0ull : inf_bits;
+    steprad[2 * c + 1] = steprad[2 * c]; steprad[2 * c] = *radius;   // (this step's trust radius: the one its measurement is taken at)
     active[c] = act;
   }
 }
@@ -138,7 +141,9 @@ __global__ void __launch_bounds__(GSFM_BLOCK) k_comp_scatter(CompMap cm, const C
     const double* x = items[ci].x + 3 * (size_t)cm.loc[k];
 #pragma unroll
     for (int c = 0; c < 3; ++c) { eta[3 * (size_t)k + c] = live ? x[c] : 0.0; rcg[3 * (size_t)k + c] = 0.0; }
-    if (live) {   // the component's largest camera update (delta = Tinv eta, radians; half-angles for the quaternion state): positive doubles order like their bits
+    // the component's largest camera update (delta = Tinv eta, radians; half-angles for the quaternion state): positive doubles order like their
+    // bits.  Not after a bad pivot (*info != 0): that item's x is garbage, NaN or inf, and the step is solved again by PCG -- nothing is measured
+    if (live && *items[ci].info == 0) {
       const double* Ti = Tinv + 9 * (size_t)k;
       const double d0 = Ti[0] * x[0] + Ti[1] * x[1] + Ti[2] * x[2], d1 = Ti[3] * x[0] + Ti[4] * x[1] + Ti[5] * x[2], d2 = Ti[6] * x[0] + Ti[7] * x[1] + Ti[8] * x[2];
       const unsigned long long v = (unsigned long long)__double_as_longlong(2.0 * sqrt(d0 * d0 + d1 * d1 + d2 * d2));

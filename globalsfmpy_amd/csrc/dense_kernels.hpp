@@ -54,7 +54,9 @@ struct CholArgs {
   double* L;      // same layout: L_ik (i > k), L_kk, and in row T the forward-substituted y = L^-1 b
   uint32_t T;     // block rows of the matrix proper = ceil(3N / 32)
   uint32_t k;     // this step's block column
-  int* info;      // 0, or 1 + index of the first non-positive pivot
+  int* info;      // 0, or 1 + index of the first pivot that is not positive and finite (NaN, inf, <= 0).  Written only on a bad pivot (the
+                  // caller clears it).  After a bad pivot the factor, y and x hold garbage, NaN and inf included: every consumer tests
+                  // info before it touches the step (solver_lm.hpp: SC_DENSE_INFO; k_comp_scatter: CholBatchItem::info)
 };
 
 // The 64-row elimination (lanes 0..31: rows of A_kk, lanes 32..63: rows of a panel tile): entries above the diagonal of the diagonal rows
@@ -89,12 +91,13 @@ __device__ __forceinline__ int chol_eliminate64(double* r, uint32_t lane) {
   for (int c0 = 0; c0 < GSFM_CB; ++c0) {
 #if GSFM_ELIM_SHORT
     const double piv = readlane_f64(r[c0], c0);
-    if (!(piv > 0.0) && !bad) bad = c0 + 1;
+    // (an infinite pivot is refused too: it is no usable pivot, and whether a later pivot reports anything depends on how rsqrt(inf) spreads)
+    if (!(piv > 0.0 && piv < __builtin_inf()) && !bad) bad = c0 + 1;
     const double inv = chol_rsqrt(piv);
     r[c0] = r[c0] * inv;
 #else
     double piv = readlane_f64(r[c0], c0);
-    if (!(piv > 0.0)) { if (!bad) bad = c0 + 1; piv = 1.0; }
+    if (!(piv > 0.0 && piv < __builtin_inf())) { if (!bad) bad = c0 + 1; piv = 1.0; }
     const double inv = rsqrt(piv);
     r[c0] = (lane == (uint32_t)c0) ? piv * inv : r[c0] * inv;
 #endif

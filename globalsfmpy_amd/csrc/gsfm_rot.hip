@@ -549,6 +549,91 @@ gsfm_status gsfm_rot_trial_lin_check(gsfm_rot_problem* P, const double* rot, con
   return (gsfm_status)sync_check(P, "trial_lin_check");
 }
 
+gsfm_status gsfm_rot_dense_factor_check(int32_t schedule, uint32_t n_items, const uint32_t* n, const double* A, const double* b, const int32_t* active,
+                                        double* x_out, double* L_out, int32_t* info_out) {
+  if (!n || !A || !b || !x_out || !info_out || n_items == 0) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument or no matrix");
+  if (schedule < 0 || schedule > 2) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "schedule: 0 (look2), 1 (fused) or 2 (batch)");
+  if (schedule != 2 && (n_items != 1 || active)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "the single schedules take one matrix and no activity flags");
+  // the product's own limits: the single step up to GSFM_DENSE_MAX_T block rows (GSFM_CHOL_FUSED_MAX_T fused), a batch item up to dense_cholesky_max_cams cameras
+  const uint32_t maxT = schedule == 0 ? GSFM_DENSE_MAX_T : schedule == 1 ? GSFM_CHOL_FUSED_MAX_T : 0;
+  const uint64_t max_n = schedule == 2 ? 3 * (uint64_t)std::max(default_options().dense_cholesky_max_cams, 0) : (uint64_t)maxT * GSFM_CB;
+  for (uint32_t i = 0; i < n_items; ++i) {
+    if (n[i] == 0) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "a matrix with no unknowns");
+    if (n[i] > max_n) return (gsfm_status)fail(GSFM_ERR_UNSUPPORTED, "matrix beyond the size the exact step supports on this schedule");
+  }
+  if (const char* why = no_device_reason("the dense factorisation check")) return (gsfm_status)fail(GSFM_ERR_NO_DEVICE, why);
+  // host side of the assembly kernels' layout (k_dense_assemble, k_comp_assemble): the lower triangle in tiles, identity on the padding
+  // diagonal n .. 32 T - 1, the right-hand side in the first row of block row T; then one slab: A of all items, L, x, info, activity, items
+  std::vector<uint32_t> T(n_items);
+  std::vector<size_t> offA(n_items), offL(n_items), offX(n_items), offIn(n_items);
+  size_t words = 0, in_words = 0;
+  uint32_t Tmax = 0;
+  for (uint32_t i = 0; i < n_items; ++i) { T[i] = (n[i] + GSFM_CB - 1) / GSFM_CB; Tmax = std::max(Tmax, T[i]); offA[i] = words; words += chol_num_tiles(T[i]) * GSFM_TILE_ELEMS; offIn[i] = in_words; in_words += (size_t)n[i] * n[i]; }
+  const size_t a_words = words;
+  for (uint32_t i = 0; i < n_items; ++i) { offL[i] = words; words += chol_num_tiles(T[i]) * GSFM_TILE_ELEMS; }
+  for (uint32_t i = 0; i < n_items; ++i) { offX[i] = words; words += (size_t)T[i] * GSFM_CB; }
+  std::vector<double> hA;
+  try { hA.assign(a_words, 0.0); } catch (const std::exception&) { return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "out of host memory"); }
+  size_t b_off = 0;
+  for (uint32_t i = 0; i < n_items; ++i) {
+    double* At = hA.data() + offA[i];
+    const double* Ai = A + offIn[i];
+    auto elem = [&](uint32_t g, uint32_t h) -> double& { return At[chol_tile_off(g / GSFM_CB, h / GSFM_CB) + (g % GSFM_CB) * GSFM_CB + h % GSFM_CB]; };
+    for (uint32_t g = 0; g < n[i]; ++g) for (uint32_t h = 0; h <= g; ++h) elem(g, h) = Ai[(size_t)g * n[i] + h];
+    for (uint32_t g = n[i]; g < T[i] * GSFM_CB; ++g) elem(g, g) = 1.0;
+    for (uint32_t g = 0; g < n[i]; ++g) At[chol_tile_off(T[i], g / GSFM_CB) + g % GSFM_CB] = b[b_off + g];
+    b_off += n[i];
+  }
+  struct Guard {
+    hipStream_t s = nullptr; void* slab = nullptr;
+    ~Guard() { if (slab) (void)hipFree(slab); if (s) (void)hipStreamDestroy(s); }
+  } G;
+  auto up = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+  const size_t o_info = up(8 * words), o_act = o_info + up(4 * (size_t)n_items), o_items = o_act + up(4 * (size_t)n_items), total = o_items + up(sizeof(CholBatchItem) * n_items);
+  HIPCHK_S(hipStreamCreateWithFlags(&G.s, hipStreamNonBlocking));
+  if (hipMalloc(&G.slab, total) != hipSuccess) { G.slab = nullptr; return (gsfm_status)fail(GSFM_ERR_HIP, "allocating the factorisation check buffers failed"); }
+  char* base = (char*)G.slab;
+  double* dw = (double*)base;
+  int* dinfo = (int*)(base + o_info);
+  int* dact = (int*)(base + o_act);
+  HIPCHK_S(hipMemsetAsync(base, 0, total, G.s));
+  HIPCHK_S(hipMemcpyAsync(dw, hA.data(), 8 * a_words, hipMemcpyHostToDevice, G.s));
+  if (schedule == 2) {
+    std::vector<int> act(n_items, 1);
+    if (active) for (uint32_t i = 0; i < n_items; ++i) act[i] = active[i] != 0;
+    std::vector<CholBatchItem> items(n_items);
+    for (uint32_t i = 0; i < n_items; ++i) items[i] = CholBatchItem{dw + offA[i], dw + offL[i], dw + offX[i], T[i], n[i], dinfo + i, dact + i};
+    HIPCHK_S(hipMemcpyAsync(dact, act.data(), 4 * (size_t)n_items, hipMemcpyHostToDevice, G.s));
+    HIPCHK_S(hipMemcpyAsync(base + o_items, items.data(), sizeof(CholBatchItem) * n_items, hipMemcpyHostToDevice, G.s));
+    HIPCHK_S(hipStreamSynchronize(G.s));   // (the staging vectors die with this scope)
+    enqueue_chol_batch((const CholBatchItem*)(base + o_items), n_items, Tmax, G.s, false);
+  } else {
+    enqueue_chol_solve(dw + offA[0], dw + offL[0], dw + offX[0], n[0], T[0], dinfo, G.s, schedule == 1);
+  }
+  HIPCHK_S(hipGetLastError());
+  std::vector<double> hw(words - a_words);
+  std::vector<int> hinfo(n_items);
+  HIPCHK_S(hipMemcpyAsync(hw.data(), dw + a_words, 8 * hw.size(), hipMemcpyDeviceToHost, G.s));
+  HIPCHK_S(hipMemcpyAsync(hinfo.data(), dinfo, 4 * (size_t)n_items, hipMemcpyDeviceToHost, G.s));
+  HIPCHK_S(hipStreamSynchronize(G.s));
+  HIPCHK_S(hipGetLastError());
+  size_t x_off = 0, l_off = 0;
+  for (uint32_t i = 0; i < n_items; ++i) {
+    info_out[i] = hinfo[i];
+    const double* Lt = hw.data() + (offL[i] - a_words);
+    const double* xt = hw.data() + (offX[i] - a_words);
+    for (uint32_t g = 0; g < n[i]; ++g) x_out[x_off + g] = xt[g];
+    x_off += n[i];
+    if (L_out) {
+      double* Li = L_out + l_off;
+      for (uint32_t g = 0; g < n[i]; ++g) for (uint32_t h = 0; h < n[i]; ++h)
+        Li[(size_t)g * n[i] + h] = h <= g ? Lt[chol_tile_off(g / GSFM_CB, h / GSFM_CB) + (g % GSFM_CB) * GSFM_CB + h % GSFM_CB] : 0.0;
+      l_off += (size_t)n[i] * n[i];
+    }
+  }
+  return GSFM_OK;
+}
+
 gsfm_status gsfm_rot_time_kernels(gsfm_rot_problem* P, const double* rot, int32_t reps, double* out_ms4) {
   if (!P || !rot || !out_ms4 || reps <= 0) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "bad argument");
   if (P->cb) return (gsfm_status)fail(GSFM_ERR_UNSUPPORTED, "time_kernels needs a native loss");

@@ -82,7 +82,7 @@ bool comps_build(gsfm_rot_problem* P, int cap) {
   item_cams.resize(item_ptr.back());
   { std::vector<uint32_t> fill(item_ptr.begin(), item_ptr.end() - 1); for (uint32_t k = 0; k < P->n_cams; ++k) if (cam_item[k] >= 0) item_cams[fill[cam_item[k]]++] = k; }
   if (C.slab.alloc(words, true) != hipSuccess || C.info.alloc(items.size(), true) != hipSuccess || C.active.alloc(items.size(), true) != hipSuccess ||
-      C.stepmax.alloc(items.size(), true) != hipSuccess || C.stepprev.alloc(items.size(), true) != hipSuccess || C.frozen.alloc(items.size(), true) != hipSuccess ||
+      C.stepmax.alloc(items.size(), true) != hipSuccess || C.stepprev.alloc(items.size(), true) != hipSuccess || C.frozen.alloc(items.size(), true) != hipSuccess || C.steprad.alloc(2 * items.size(), true) != hipSuccess ||
       C.item_ptr.upload(item_ptr) != hipSuccess || C.item_cams.upload(item_cams) != hipSuccess || C.b_pcg.alloc(3 * (size_t)P->n_cams, true) != hipSuccess) {
     (void)hipGetLastError(); C.slab.release(); return false;
   }
@@ -94,45 +94,52 @@ bool comps_build(gsfm_rot_problem* P, int cap) {
   return true;
 }
 
+// Factorise + substitute n_items assembled matrices side by side (items: a device array; Tmax: the largest item's T): the launches of the
+// component step, shared by comps_enqueue_dense and gsfm_rot_dense_factor_check.  Enqueues only; an inactive item is left alone, an item's
+// *info is written only on a non-positive pivot (the caller clears it).  fused: the fused step of rounds 2-5.
+void enqueue_chol_batch(const CholBatchItem* items, uint32_t n_items, uint32_t Tmax, hipStream_t st, bool fused) {
+  // one launch per TWO block columns: their panels beside the update with the two columns before them (dense_kernels.hpp, k_chol_look2_batch; round 6: the
+  // fused step's bits at one elimination per block row and column -- the six scenes of C4 side by side 985 -> 660 us per factorisation + solve);
+  // GSFM_CHOL_FUSED=1: the fused step
+  if (!fused) {
+    hipLaunchKernelGGL(k_chol_look2_batch<0>, dim3(chol_look2_grid(Tmax, 0, false), n_items), dim3(256), 0, st, items, 0u);
+    for (uint32_t c0 = 2; c0 < Tmax; c0 += 2)
+      hipLaunchKernelGGL(k_chol_look2_batch<2>, dim3(chol_look2_grid(Tmax, c0, true), n_items), dim3(256), 0, st, items, c0);
+  } else for (uint32_t k = 0; k < Tmax; ++k) {
+    const uint32_t m = Tmax - k, nt = chol_step_tiles_per_wg(m);
+    const dim3 grid(chol_step_grid(m, nt), n_items);
+    if (nt == 3) hipLaunchKernelGGL(k_chol_step_batch<3>, grid, dim3(256), 0, st, items, k);
+    else if (nt == 2) hipLaunchKernelGGL(k_chol_step_batch<2>, grid, dim3(256), 0, st, items, k);
+    else hipLaunchKernelGGL(k_chol_step_batch<1>, grid, dim3(256), 0, st, items, k);
+  }
+  constexpr uint32_t GR = 8;
+  for (uint32_t g = 0; g * GR < Tmax; ++g) {
+    hipLaunchKernelGGL(k_chol_back_group_batch<GR>, dim3(1, n_items), dim3(64 * GR), 0, st, items, g);
+    const uint32_t k1 = Tmax - g * GR, k0 = k1 > GR ? k1 - GR : 0;
+    if (k0) hipLaunchKernelGGL(k_chol_back_update_batch<GR>, dim3(k0, n_items), dim3(32 * GR), 0, st, items, g);
+  }
+}
+
 // enqueue: clear + assemble + factorise + substitute, all factorised components side by side
 void comps_enqueue_dense(gsfm_rot_problem* P, hipStream_t st) {
   auto& C = P->comps;
   (void)hipMemsetAsync(C.slab.p, 0, 8 * C.a_words, st);
   hipLaunchKernelGGL(k_comp_activity, dim3(C.n_items), dim3(GSFM_BLOCK), 0, st, (const uint32_t*)C.item_ptr.p, (const uint32_t*)C.item_cams.p, (const double*)P->b.p,
-                     (const double*)P->Minv.p, (const double*)(P->scal.p + SC_ZBOUND), pcg_abs_floor2(P), C.active.p, C.stepmax.p, C.stepprev.p, C.frozen.p, comp_freeze_below(P), (const double*)(P->scal.p + SC_FREEZE_OK));
+                     (const double*)P->Minv.p, (const double*)(P->scal.p + SC_ZBOUND), pcg_abs_floor2(P), C.active.p, C.stepmax.p, C.stepprev.p, C.steprad.p, (const int*)C.info.p, C.frozen.p, comp_freeze_below(P),
+                     (const double*)(P->scal.p + SC_COMP_RADIUS));
   DenseArgs a{};
   a.n_rows = P->n_rows; a.row_ptr = P->row_ptr.p; a.col = P->col.p; a.h0 = P->h0.p; a.h1 = P->h1.p; a.h2 = P->h2.p; a.h3 = P->h3.p; a.h4 = P->h4.p;
   a.Mblk = P->Mblk.p; a.b = P->b.p; a.A = nullptr; a.n = 0; a.T = 0; a.q = P->q_lin; a.lap = P->lin_is_lap; a.info_slot = P->scal.p + SC_DENSE_INFO; a.rcg = P->r.p;
   const CompMap cm{C.cam_item.p, C.cam_loc.p, P->own_begin};
   hipLaunchKernelGGL(k_comp_assemble, dim3((uint32_t)C.item_cams.n), dim3(GSFM_BLOCK), 0, st, a, cm, (const CholBatchItem*)C.items.p, (const uint32_t*)C.item_cams.p);
-  // one launch per TWO block columns: their panels beside the update with the two columns before them (dense_kernels.hpp, k_chol_look2_batch; round 6: the
-  // fused step's bits at one elimination per block row and column -- the six scenes of C4 side by side 985 -> 660 us per factorisation + solve);
-  // GSFM_CHOL_FUSED=1: the fused step
   const char* fused_env = getenv("GSFM_CHOL_FUSED");
-  const bool fused = fused_env && fused_env[0] == '1';
-  if (!fused) {
-    hipLaunchKernelGGL(k_chol_look2_batch<0>, dim3(chol_look2_grid(C.Tmax, 0, false), C.n_items), dim3(256), 0, st, (const CholBatchItem*)C.items.p, 0u);
-    for (uint32_t c0 = 2; c0 < C.Tmax; c0 += 2)
-      hipLaunchKernelGGL(k_chol_look2_batch<2>, dim3(chol_look2_grid(C.Tmax, c0, true), C.n_items), dim3(256), 0, st, (const CholBatchItem*)C.items.p, c0);
-  } else for (uint32_t k = 0; k < C.Tmax; ++k) {
-    const uint32_t m = C.Tmax - k, nt = chol_step_tiles_per_wg(m);
-    const dim3 grid(chol_step_grid(m, nt), C.n_items);
-    if (nt == 3) hipLaunchKernelGGL(k_chol_step_batch<3>, grid, dim3(256), 0, st, (const CholBatchItem*)C.items.p, k);
-    else if (nt == 2) hipLaunchKernelGGL(k_chol_step_batch<2>, grid, dim3(256), 0, st, (const CholBatchItem*)C.items.p, k);
-    else hipLaunchKernelGGL(k_chol_step_batch<1>, grid, dim3(256), 0, st, (const CholBatchItem*)C.items.p, k);
-  }
-  constexpr uint32_t GR = 8;
-  for (uint32_t g = 0; g * GR < C.Tmax; ++g) {
-    hipLaunchKernelGGL(k_chol_back_group_batch<GR>, dim3(1, C.n_items), dim3(64 * GR), 0, st, (const CholBatchItem*)C.items.p, g);
-    const uint32_t k1 = C.Tmax - g * GR, k0 = k1 > GR ? k1 - GR : 0;
-    if (k0) hipLaunchKernelGGL(k_chol_back_update_batch<GR>, dim3(k0, C.n_items), dim3(32 * GR), 0, st, (const CholBatchItem*)C.items.p, g);
-  }
+  enqueue_chol_batch((const CholBatchItem*)C.items.p, C.n_items, C.Tmax, st, fused_env && fused_env[0] == '1');
 }
 
 // The step of a disconnected problem: *used = false if the path does not apply (the caller then runs its generic one).  On return the step
 // vector and the PCG residual are complete and the status word of the scalar block says whether every factorisation went through.
-// freeze_ok: this step's damping is not what would make a component's step small (lm_solve: the trust radius is at or above its initial value)
-int run_component_step(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol_requested, bool pcg_struggles, bool freeze_ok, bool* used, int* cg, double* cg_rel) {
+// radius: this step's trust radius (the damping is D / radius: k_comp_activity weighs a small step against it, comp_rest.hpp)
+int run_component_step(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol_requested, bool pcg_struggles, double radius, bool* used, int* cg, double* cg_rel) {
   *used = false; *cg = 0; *cg_rel = 0.0;
   if ((P->sharded && !P->packed) || P->n_components <= 1 || o.dense_cholesky_max_cams <= 0 || P->cs.active) return 0;
   if (!comps_build(P, o.dense_cholesky_max_cams)) return 0;
@@ -145,7 +152,7 @@ int run_component_step(gsfm_rot_problem* P, const gsfm_rot_options& o, double to
     HIPCHK(hipMemcpyAsync(C.stepprev.p, inf.data(), 8 * C.n_items, hipMemcpyHostToDevice, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));   // (the staging vector dies with this scope)
   }
-  hipLaunchKernelGGL(k_set_double, dim3(1), dim3(1), 0, P->stream, P->scal.p + SC_FREEZE_OK, freeze_ok ? 1.0 : 0.0);
+  hipLaunchKernelGGL(k_set_double, dim3(1), dim3(1), 0, P->stream, P->scal.p + SC_COMP_RADIUS, radius);
   // The factorisations and the PCG solve of the large components touch disjoint outputs and read the same inputs: with something left for PCG
   // the chain of the factorisations runs on a stream of its own beside it (fork behind the damping's kernels, join in front of the scatter).
   if (C.side_state == 0) {
@@ -190,15 +197,16 @@ int run_component_step(gsfm_rot_problem* P, const gsfm_rot_options& o, double to
   hipLaunchKernelGGL(k_comp_scatter, dim3(grid_for(P->n_cams)), dim3(GSFM_BLOCK), 0, P->stream, cm, (const CholBatchItem*)C.items.p, C.n_items, P->n_cams, C.all_dense ? 1 : 0,
                      P->xcg.p, P->r.p, P->scal.p + SC_DENSE_INFO, (const double*)P->Tinv.p, C.stepmax.p, P->packed ? P->scal.p + SC_COMPBAD : nullptr);
   if (o.verbose) {   // which components were live in this step (a read-back: verbose runs only)
-    std::vector<int> act(C.n_items), fr(C.n_items);
+    std::vector<int> act(C.n_items), fr(C.n_items), bad(C.n_items);
     std::vector<unsigned long long> sm(C.n_items);
     HIPCHK(hipMemcpyAsync(act.data(), C.active.p, sizeof(int) * C.n_items, hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipMemcpyAsync(fr.data(), C.frozen.p, sizeof(int) * C.n_items, hipMemcpyDeviceToHost, P->stream));
+    HIPCHK(hipMemcpyAsync(bad.data(), C.info.p, sizeof(int) * C.n_items, hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipMemcpyAsync(sm.data(), C.stepmax.p, 8 * C.n_items, hipMemcpyDeviceToHost, P->stream));
     HIPCHK(hipStreamSynchronize(P->stream));
     std::string line = "[gsfm] components:";
-    for (uint32_t i = 0; i < C.n_items; ++i) { double v; std::memcpy(&v, &sm[i], 8); char b[64]; snprintf(b, sizeof b, " %s%.1e", fr[i] ? "rest:" : act[i] ? "" : "idle:", v); line += b; }
-    fprintf(stderr, "%s  (largest camera update of each factorised component, rad; PCG %d iterations)\n", line.c_str(), *cg);
+    for (uint32_t i = 0; i < C.n_items; ++i) { double v; std::memcpy(&v, &sm[i], 8); char b[64]; snprintf(b, sizeof b, " %s%.1e", fr[i] ? "rest:" : !act[i] ? "idle:" : bad[i] ? "bad:" : "", v); line += b; }
+    fprintf(stderr, "%s  (largest camera update of each factorised component, rad -- bad: its factorisation failed, nothing measured; PCG %d iterations)\n", line.c_str(), *cg);
   }
   *used = true;
   return 0;

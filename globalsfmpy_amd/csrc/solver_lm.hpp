@@ -476,7 +476,7 @@ int lm_solve(gsfm_rot_problem* P, const gsfm_rot_options& o_in, gsfm_rot_summary
     bool comp_used = false;
     if (P->packed) (void)hipMemsetAsync(P->scal.p + SC_COMPBAD, 0, sizeof(double), P->stream);
     if (!dense_used && P->n_components > 1 && (!P->sharded || P->packed)) {
-      if (int st = run_component_step(P, o, o_in.cg_relative_tolerance, pcg_struggles, radius >= o.initial_trust_region_radius, &comp_used, &cg, &cg_rel)) return st;
+      if (int st = run_component_step(P, o, o_in.cg_relative_tolerance, pcg_struggles, radius, &comp_used, &cg, &cg_rel)) return st;
       if (comp_used) {
         loose = false;
         if (gmax_deferred) {

@@ -452,6 +452,16 @@ gsfm_status gsfm_rot_normal_matvec(gsfm_rot_problem* p, const double* v, double*
  * the linearisation at rot_aa (blocks, gD, quaternions) came through the (not accepted) trial unchanged.  Leaves the problem linearised
  * at rot_aa.  GSFM_ERR_UNSUPPORTED where the problem has no fused evaluation (no spare set, kernel or loss without one, GSFM_TRIAL_LIN=0). */
 gsfm_status gsfm_rot_trial_lin_check(gsfm_rot_problem* p, const double* rot_aa, const double* rot_trial, double* cost_out, int32_t* same_out);
+/* Check of the exact step's factorisation (no problem object needed): factorises the SPD matrices A and solves A x = b with the launches the
+ * LM step itself runs (the dense tiled Cholesky of dense_cholesky_max_cams / dense_cholesky_auto_cams).  schedule 0: one matrix, the default
+ * schedule (two block columns per launch); 1: one matrix, the fused step (GSFM_CHOL_FUSED=1); 2: n_items matrices side by side, as the
+ * components of a disconnected view graph.  n[i]: unknowns of matrix i; A: the items' full row-major n[i] x n[i] matrices, concatenated (only the
+ * lower triangle is read); b: their right-hand sides, concatenated; active (schedule 2 only, NULL = all): 0 leaves an item alone (x = 0, info = 0).
+ * Out: x_out (concatenated), L_out (optional: the row-major lower factors, zero above the diagonal), info_out[i]: 0, or 1 + index of the first
+ * pivot that is not positive and finite (the factor and x of that item are then meaningless).  GSFM_ERR_UNSUPPORTED beyond the product's limits:
+ * 32 * GSFM_DENSE_MAX_T unknowns (schedule 0), 32 * GSFM_CHOL_FUSED_MAX_T (1), 3 * the default dense_cholesky_max_cams per item (2). */
+gsfm_status gsfm_rot_dense_factor_check(int32_t schedule, uint32_t n_items, const uint32_t* n, const double* A, const double* b,
+                                        const int32_t* active, double* x_out, double* L_out, int32_t* info_out);
 
 /* ------------------------------------------------------------------------- */
 /* The step after the solve + the edge statistic ("next" row f-3 of the scope)  */
