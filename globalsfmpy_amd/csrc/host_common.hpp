@@ -244,10 +244,15 @@ struct gsfm_rot_problem {
   bool own_stream = false;
   // replayable chunk of PCG iterations (hipGraph), keyed on the by-value kernel arguments it froze
   struct PcgGraph {
+    struct Key {
+      int max_iters = 0, stall = 0, chunk = 0; uint32_t coarse = 0; bool lap = false;
+      const void* planes = nullptr;   // the block planes (h0) the captured mat-vecs read
+      bool operator==(const Key& k) const { return max_iters == k.max_iters && stall == k.stall && chunk == k.chunk && coarse == k.coarse && lap == k.lap && planes == k.planes; }
+    };
     hipGraphExec_t exec = nullptr;
-    double tol = 0; int max_iters = 0, stall = 0, chunk = 0, collectives = 0; uint32_t coarse = 0;
-    bool unusable = false, lap = false;
-    const void* planes = nullptr;   // the block planes (h0) the captured mat-vecs read
+    Key key;
+    int collectives = 0;
+    bool unusable = false;
     void reset() { if (exec) (void)hipGraphExecDestroy(exec); exec = nullptr; }
   } pcg_graph, pcg2_graph;
   // ... and the same two chunks captured on the spare set of block planes (trial_lin below): a fused trial that is accepted swaps the sets, and

@@ -187,8 +187,8 @@ int run_component_step(gsfm_rot_problem* P, const gsfm_rot_options& o, double to
     if (int st = coarse_build(P, pcg_struggles)) { P->b_rhs = nullptr; return st; }
     // one large component left: the global stopping rule is its own, the requested tolerance stands; several: the round-3 safeguard (1e-14)
     const double tol = C.n_pcg_comps > 1 ? std::min(tol_requested, 1e-14) : tol_requested;
-    const bool pcg2 = P->coarse_n == 0 && use_single_reduction(P, o);
-    const int st = pcg2 ? run_pcg2(P, o, tol, 0.0, -1, cg, cg_rel) : run_pcg(P, o, tol, 0.0, -1, cg, cg_rel);
+    bool single_reduction = false;
+    const int st = pcg_solve(P, o, tol, 0.0, -1, &single_reduction, cg, cg_rel);
     P->b_rhs = nullptr;
     if (st) return st;
     if (*cg_rel <= tol) *cg_rel = std::min(*cg_rel, o.cg_relative_tolerance);   // (held against the caller's tolerance afterwards)

@@ -1,5 +1,5 @@
-// Host side, part 3: the linear solve of an LM step by block-Jacobi PCG -- textbook recurrence (run_pcg), single-reduction recurrence
-// (run_pcg2), the two-level preconditioner's coarse matrix (coarse_build) -- with the chunks between two host looks replayed as hipGraphs.
+// Host side, part 3: the linear solve of an LM step by block-Jacobi PCG (pcg_solve) -- textbook recurrence (run_pcg), single-reduction
+// recurrence (run_pcg2), the two-level preconditioner's coarse matrix (coarse_build) -- with the chunks between two host looks replayed as hipGraphs.
 #pragma once
 #include "host_common.hpp"
 
@@ -149,10 +149,74 @@ double pcg_abs_floor2(const gsfm_rot_problem* P) { const double f = (P->n_compon
 // ... and a factorised component whose exact step has fallen below this is put to rest for the remainder of the solve (comp_kernels.hpp, k_comp_activity)
 double comp_freeze_below(const gsfm_rot_problem* P) { return (!P->loss_staircase && !P->cb && P->component_rest) ? 1e-10 : 0.0; }
 
-// block-Jacobi PCG on (J^T J + Lambda) eta = -g to the relative residual `tol` -- or, etol2 > 0 (a loose solve of the forcing schedule), until the
-// estimated relative energy-norm error squared falls below etol2 (kernels.hpp, cg_energy_stop); returns iterations.  resume_iters >= 0: continue the solve
-// that stopped after that many iterations (at a looser tolerance) instead of starting one -- the device state is exactly what the stopping
-// iteration left (kernels.hpp, CgScalars::done_seen), so the iterates are those of an uninterrupted solve at `tol`.
+// A recurrence's part of the chunk loop both share, and the points where the two have always differed -- kept as they are (harmonising them
+// would move num_pcg_launched and num_graph_launches).
+struct PcgLoop {
+  gsfm_rot_problem::PcgGraph& G;   // the recurrence's chunk, captured on the block planes the current linearisation lives in
+  bool blocked;                    // the fallback flags it reads (textbook: pcg_graph.unusable; single-reduction: both)
+  bool& unusable;                  // ... and the one a failed capture sets (textbook: pcg_graph's; single-reduction: pcg2_graph's)
+  int key_stall; uint32_t key_coarse;   // in the graph's key for the textbook recurrence; 0 (not keyed on) for the single-reduction one
+  bool clamp_chunks; int cap_slack;   // textbook only: the look-ahead stays within max_cg_iterations / the cap exit: launched >= max_cg_iterations + chunk + cap_slack (single-reduction: 2)
+};
+
+// The chunks between two host looks: replayed as one hipGraph each (captured on first use, keyed on the by-value kernel arguments it froze) or
+// launched plainly, the status read through the mailbox or a read-back.  Starts at parity 0 with `launched` iterations behind it.
+template <class Scalars, class Iter>
+int pcg_chunk_loop(gsfm_rot_problem* P, const gsfm_rot_options& o, const PcgLoop& L, Scalars* sc, Iter&& enqueue_iter, double tol, double etol2,
+                   int launched, int* iters_out, double* rel_out) {
+  const int chunk = std::max(1, o.cg_check_interval);
+  const bool mail = mail_usable(P);
+  auto enqueue_chunk = [&]() -> int {  // `chunk` iterations (+ the status post); leaves the parity where it found it when chunk is even
+    for (int c = 0; c < chunk; ++c) if (int st = enqueue_iter()) return st;
+    if (mail) mail_post(P, sc, sizeof(Scalars));
+    return 0;
+  };
+  auto& G = L.G;
+  bool graph = o.pcg_hip_graph && (!P->sharded || P->pcg_local || graph_collectives_ok(P, o)) && chunk % 2 == 0 && !L.blocked;
+  // (the tolerance is device-resident, CgScalars::tol / Cg2Scalars::tol: a captured chunk serves every tolerance)
+  const gsfm_rot_problem::PcgGraph::Key key{o.max_cg_iterations, L.key_stall, chunk, L.key_coarse, P->lin_is_lap, P->h0.p};
+  if (graph && (!G.exec || !(G.key == key))) {
+    G.reset();
+    hipGraph_t captured = nullptr;
+    if (hipStreamBeginCapture(P->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+      const int c0 = P->n_collectives, p0 = P->n_pcg_collectives;
+      const int st = enqueue_chunk();
+      const hipError_t e = hipStreamEndCapture(P->stream, &captured);
+      G.collectives = P->n_collectives - c0;            // captured, not issued: counted per replay below
+      P->n_collectives = c0; P->n_pcg_collectives = p0;
+      if (st == 0 && e == hipSuccess && captured && hipGraphInstantiate(&G.exec, captured, nullptr, nullptr, 0) == hipSuccess) G.key = key;
+      else G.exec = nullptr;
+      if (captured) (void)hipGraphDestroy(captured);
+    }
+    if (!G.exec) { (void)hipGetLastError(); L.unusable = true; graph = false; }  // e.g. a stream that cannot be captured: plain launches
+  }
+  int chunks = 1; PcgStagnation stagnation; Scalars h{};
+  while (true) {
+    const int tk = P->timer.begin(T_CG);
+    for (int c = 0; c < chunks; ++c) {
+      if (graph) { HIPCHK(hipGraphLaunch(G.exec, P->stream)); P->graph_launches++; P->n_collectives += G.collectives; P->n_pcg_collectives += G.collectives; }
+      else if (int st = enqueue_chunk()) return st;
+      launched += chunk; P->n_pcg_launched += chunk;
+      if (mail) P->mail_expected += 1.0;
+    }
+    P->timer.end(tk);
+    if (int st = mail ? mail_wait(P, &h, sizeof(h)) : read_back(P, &h, sc, sizeof(h), "pcg")) return st;
+    if (h.done || launched >= o.max_cg_iterations + chunk + L.cap_slack || stagnation.stop(h.iters, h.last_rel)) break;
+    // Fewer host round trips: extrapolate the average convergence factor so far to the tolerance and enqueue that many
+    // chunks before looking again (kernels past convergence return at their first instruction, so overshoot is cheap).
+    chunks = 1;
+    if (!(etol2 > 0.0) && h.iters > 0 && h.last_rel > 0.0 && h.last_rel < 1.0 && tol > 0.0 && tol < h.last_rel) {
+      const double per_iter = std::log(h.last_rel) / h.iters;
+      const double remaining = std::log(tol / h.last_rel) / per_iter;
+      chunks = (int)std::min(8.0, std::max(1.0, std::ceil(remaining / chunk)));
+    }
+    if (L.clamp_chunks) chunks = std::min(chunks, std::max(1, (o.max_cg_iterations + chunk - launched + chunk - 1) / chunk));
+  }
+  *iters_out = h.iters; *rel_out = h.last_rel <= h.tol ? std::fmin(h.last_rel, tol) : h.last_rel;   // (converged against the floor-adjusted tolerance: converged)
+  return 0;
+}
+
+// The textbook recurrence: 4 dependent kernels per iteration (+ the coarse correction's).
 int run_pcg(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double etol2, int resume_iters, int* iters_out, double* rel_out) {
   const bool resume = resume_iters >= 0;
   // PACKED sharded problem: this rank's own block of a block-diagonal system, solved without a collective -- right-hand side zero outside the
@@ -192,8 +256,6 @@ int run_pcg(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double e
   }
   ca.done = &P->cgsc.p->done; ca.rc_part = a.rc_part;
   P->timer.end(tk0);
-  CgScalars h{};
-  const int chunk = std::max(1, o.cg_check_interval);
   auto enqueue_iter = [&]() -> int {
     bool dotted = false;
     if (int st = launch_matvec(P, P->Mblk.p, P->p.p, P->Ap.p, &P->cgsc.p->done, a.part_a, &dotted)) return st;
@@ -208,71 +270,20 @@ int run_pcg(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double e
     a.par ^= 1;
     return 0;
   };
-  const bool mail = mail_usable(P);
-  auto enqueue_chunk = [&]() -> int {  // `chunk` iterations (+ the status post); leaves a.par where it found it when chunk is even
-    for (int c = 0; c < chunk; ++c) if (int st = enqueue_iter()) return st;
-    if (mail) mail_post(P, P->cgsc.p, sizeof(CgScalars));
-    return 0;
-  };
-  // The chunk between two host checks as one hipGraph launch: 4 * chunk dependent kernels whose arguments never change.
-  auto& G = P->lin_set ? P->pcg_graph_b : P->pcg_graph;   // (the chunk captured on the block planes the current linearisation lives in)
-  bool graph = o.pcg_hip_graph && (!P->sharded || P->pcg_local || graph_collectives_ok(P, o)) && chunk % 2 == 0 && !P->pcg_graph.unusable;
-  // (the tolerance is device-resident, CgScalars::tol: a captured chunk serves every tolerance)
-  if (graph && (!G.exec || G.max_iters != a.max_iters || G.stall != a.stall_limit || G.chunk != chunk || G.lap != P->lin_is_lap || G.coarse != a.coarse_n || G.planes != P->h0.p)) {
-    G.reset();
-    hipGraph_t captured = nullptr;
-    if (hipStreamBeginCapture(P->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-      const int c0 = P->n_collectives, p0 = P->n_pcg_collectives;
-      const int st = enqueue_chunk();
-      const hipError_t e = hipStreamEndCapture(P->stream, &captured);
-      G.collectives = P->n_collectives - c0;            // captured, not issued: counted per replay below
-      P->n_collectives = c0; P->n_pcg_collectives = p0;
-      if (st == 0 && e == hipSuccess && captured && hipGraphInstantiate(&G.exec, captured, nullptr, nullptr, 0) == hipSuccess) {
-        G.tol = a.tol; G.max_iters = a.max_iters; G.stall = a.stall_limit; G.chunk = chunk; G.lap = P->lin_is_lap; G.coarse = a.coarse_n; G.planes = P->h0.p;
-      } else { G.exec = nullptr; }
-      if (captured) (void)hipGraphDestroy(captured);
-    }
-    if (!G.exec) { (void)hipGetLastError(); P->pcg_graph.unusable = true; graph = false; }  // e.g. a stream that cannot be captured: plain launches
-  }
-  int launched = 0, chunks = 1;
-  PcgStagnation stagnation;
-  if (resume) {   // the parity of the iteration that follows the stop; a captured chunk starts at parity 0
-    launched = resume_iters;
-    if (resume_iters & 1) {
-      a.par = 1;
-      const int tk = P->timer.begin(T_CG);
-      if (int st = enqueue_iter()) return st;
-      P->timer.end(tk);
-      ++launched; P->n_pcg_launched++;
-    }
-  }
-  while (true) {
+  int launched = resume ? resume_iters : 0;
+  if (resume && (resume_iters & 1)) {   // the parity of the iteration that follows the stop; a captured chunk starts at parity 0
+    a.par = 1;
     const int tk = P->timer.begin(T_CG);
-    for (int c = 0; c < chunks; ++c) {
-      if (graph) { HIPCHK(hipGraphLaunch(G.exec, P->stream)); P->graph_launches++; P->n_collectives += G.collectives; P->n_pcg_collectives += G.collectives; }
-      else if (int st = enqueue_chunk()) return st;
-      launched += chunk; P->n_pcg_launched += chunk;
-      if (mail) P->mail_expected += 1.0;
-    }
+    if (int st = enqueue_iter()) return st;
     P->timer.end(tk);
-    if (int st = mail ? mail_wait(P, &h, sizeof(h)) : read_back(P, &h, P->cgsc.p, sizeof(h), "pcg")) return st;
-    if (h.done || launched >= o.max_cg_iterations + chunk || stagnation.stop(h.iters, h.last_rel)) break;
-    // Fewer host round trips: extrapolate the average convergence factor so far to the tolerance and enqueue that many
-    // chunks before looking again (kernels past convergence return at their first instruction, so overshoot is cheap).
-    chunks = 1;
-    if (!(etol2 > 0.0) && h.iters > 0 && h.last_rel > 0.0 && h.last_rel < 1.0 && tol > 0.0 && tol < h.last_rel) {
-      const double per_iter = std::log(h.last_rel) / h.iters;
-      const double remaining = std::log(tol / h.last_rel) / per_iter;
-      chunks = (int)std::min(8.0, std::max(1.0, std::ceil(remaining / chunk)));
-    }
-    chunks = std::min(chunks, std::max(1, (o.max_cg_iterations + chunk - launched + chunk - 1) / chunk));
+    ++launched; P->n_pcg_launched++;
   }
-  *iters_out = h.iters; *rel_out = h.last_rel <= h.tol ? std::fmin(h.last_rel, tol) : h.last_rel;   // (converged against the floor-adjusted tolerance: converged)
-  return 0;   // (packed: the step and the residual are gathered by the caller, once per evaluated step: packed_exchange)
+  const PcgLoop L{P->lin_set ? P->pcg_graph_b : P->pcg_graph, P->pcg_graph.unusable, P->pcg_graph.unusable, a.stall_limit, a.coarse_n, true, 0};
+  return pcg_chunk_loop(P, o, L, P->cgsc.p, enqueue_iter, tol, etol2, launched, iters_out, rel_out);   // (packed: the step and the residual are gathered by the caller, once per evaluated step: packed_exchange)
 }
 
 // single-reduction PCG (Chronopoulos-Gear): 2 kernels per iteration (3 + one all-gather when sharded); the launch-latency regime's
-// default (see use_single_reduction).  The chunk between two host checks replays as one hipGraph, like run_pcg's.
+// default (see use_single_reduction).
 int run_pcg2(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double etol2, int resume_iters, int* iters_out, double* rel_out) {
   const bool resume = resume_iters >= 0;
   Cg2Args c{};
@@ -302,8 +313,6 @@ int run_pcg2(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double 
   if (resume) hipLaunchKernelGGL(k_cg2_resume, dim3(1), dim3(1), 0, P->stream, P->cg2sc.p, tol, etol2);
   else hipLaunchKernelGGL(k_cg2_init, gcam, blk, 0, P->stream, c);
   P->timer.end(tk0);
-  Cg2Scalars h{};
-  const int chunk = std::max(1, o.cg_check_interval);
   // One iteration = mat-vec (+ delta partials), vector step.  `first` / `par` are by-value kernel arguments: a captured chunk must
   // start at par == 0, first == 0, so the very first iteration is launched plainly and chunks have even length.
   auto enqueue_iter = [&]() -> int {
@@ -329,60 +338,15 @@ int run_pcg2(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double 
     c.par ^= 1; c.first = 0;
     return 0;
   };
-  int launched = 0;
-  if (resume) {   // the launch that stopped had parity resume_iters & 1 (and `first` set only if nothing had run): take it again, plainly, up to parity 0
-    launched = resume_iters; c.par = resume_iters & 1; c.first = resume_iters == 0;
-    const int tk = P->timer.begin(T_CG);
-    while (c.par || c.first) { if (int st = enqueue_iter()) return st; ++launched; P->n_pcg_launched++; }
-    P->timer.end(tk);
-  } else {  // iterations 0 and 1 (first = 1, then par = 1): plain launches; afterwards par == 0 at every chunk start
-    const int tk = P->timer.begin(T_CG);
-    for (int k = 0; k < 2; ++k) { if (int st = enqueue_iter()) return st; ++launched; P->n_pcg_launched++; }
-    P->timer.end(tk);
-  }
-  const bool mail = mail_usable(P);
-  auto& G = P->lin_set ? P->pcg2_graph_b : P->pcg2_graph;   // (as run_pcg)
-  bool graph = o.pcg_hip_graph && (!P->sharded || graph_collectives_ok(P, o)) && chunk % 2 == 0 && !P->pcg2_graph.unusable && !P->pcg_graph.unusable;
-  if (graph && (!G.exec || G.max_iters != c.max_iters || G.chunk != chunk || G.lap != P->lin_is_lap || G.planes != P->h0.p)) {
-    G.reset();
-    hipGraph_t captured = nullptr;
-    if (hipStreamBeginCapture(P->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-      int st = 0;
-      const int c0 = P->n_collectives, p0 = P->n_pcg_collectives;
-      for (int k = 0; k < chunk && st == 0; ++k) st = enqueue_iter();
-      if (mail && st == 0) mail_post(P, P->cg2sc.p, sizeof(Cg2Scalars));
-      const hipError_t e = hipStreamEndCapture(P->stream, &captured);
-      G.collectives = P->n_collectives - c0;
-      P->n_collectives = c0; P->n_pcg_collectives = p0;
-      if (st == 0 && e == hipSuccess && captured && hipGraphInstantiate(&G.exec, captured, nullptr, nullptr, 0) == hipSuccess) {
-        G.tol = c.tol; G.max_iters = c.max_iters; G.chunk = chunk; G.lap = P->lin_is_lap; G.planes = P->h0.p;
-      } else { G.exec = nullptr; }
-      if (captured) (void)hipGraphDestroy(captured);
-    }
-    if (!G.exec) { (void)hipGetLastError(); P->pcg2_graph.unusable = true; graph = false; }
-  }
-  int chunks = 1;
-  PcgStagnation stagnation;
-  while (true) {
-    const int tk = P->timer.begin(T_CG);
-    for (int cc = 0; cc < chunks; ++cc) {
-      if (graph) { HIPCHK(hipGraphLaunch(G.exec, P->stream)); P->graph_launches++; P->n_collectives += G.collectives; P->n_pcg_collectives += G.collectives; }
-      else { for (int k = 0; k < chunk; ++k) if (int st = enqueue_iter()) return st; if (mail) mail_post(P, P->cg2sc.p, sizeof(Cg2Scalars)); }
-      launched += chunk; P->n_pcg_launched += chunk;
-      if (mail) P->mail_expected += 1.0;
-    }
-    P->timer.end(tk);
-    if (int st = mail ? mail_wait(P, &h, sizeof(h)) : read_back(P, &h, P->cg2sc.p, sizeof(h), "pcg")) return st;
-    if (h.done || launched >= o.max_cg_iterations + chunk + 2 || stagnation.stop(h.iters, h.last_rel)) break;
-    chunks = 1;   // same look-ahead as run_pcg: extrapolate the convergence factor, enqueue that many chunks before looking again
-    if (!(etol2 > 0.0) && h.iters > 0 && h.last_rel > 0.0 && h.last_rel < 1.0 && tol > 0.0 && tol < h.last_rel) {
-      const double per_iter = std::log(h.last_rel) / h.iters;
-      const double remaining = std::log(tol / h.last_rel) / per_iter;
-      chunks = (int)std::min(8.0, std::max(1.0, std::ceil(remaining / chunk)));
-    }
-  }
-  *iters_out = h.iters; *rel_out = h.last_rel <= h.tol ? std::fmin(h.last_rel, tol) : h.last_rel;   // (converged against the floor-adjusted tolerance: converged)
-  return 0;
+  // Plain launches up to parity 0, afterwards par == 0 at every chunk start: a new solve's iterations 0 and 1 (first = 1, then par = 1); a resumed
+  // one's launch that stopped, with parity resume_iters & 1 (and `first` set only if nothing had run), taken again.
+  int launched = resume ? resume_iters : 0;
+  if (resume) { c.par = resume_iters & 1; c.first = resume_iters == 0; }
+  const int tk = P->timer.begin(T_CG);
+  while (c.par || c.first) { if (int st = enqueue_iter()) return st; ++launched; P->n_pcg_launched++; }
+  P->timer.end(tk);
+  const PcgLoop L{P->lin_set ? P->pcg2_graph_b : P->pcg2_graph, P->pcg2_graph.unusable || P->pcg_graph.unusable, P->pcg2_graph.unusable, 0, 0u, false, 2};
+  return pcg_chunk_loop(P, o, L, P->cg2sc.p, enqueue_iter, tol, etol2, launched, iters_out, rel_out);
 }
 
 // Which PCG: the single-reduction variant halves the dependent launches per iteration (2 instead of 4), which is what bounds small
@@ -403,6 +367,15 @@ bool use_single_reduction(const gsfm_rot_problem* P, const gsfm_rot_options& o) 
   // residual of the textbook form is the safer one.
   if (P->sharded) return o.cg_relative_tolerance >= 1e-13 && P->n_components <= 1;
   return P->dir.n <= (size_t)2000000;
+}
+
+// block-Jacobi PCG on (J^T J + Lambda) eta = -g to the relative residual `tol` -- or, etol2 > 0 (a loose solve of the forcing schedule), until the
+// estimated relative energy-norm error squared falls below etol2 (kernels.hpp, cg_energy_stop).  resume_iters < 0: a new solve, its recurrence chosen
+// here and reported in *single_reduction; >= 0: continue the solve that stopped after that many iterations (at a looser tolerance) with the one that ran
+// it -- the device state is what the stopping iteration left (kernels.hpp, CgScalars::done_seen): the iterates of an uninterrupted solve at `tol`.
+int pcg_solve(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double etol2, int resume_iters, bool* single_reduction, int* iters_out, double* rel_out) {
+  if (resume_iters < 0) *single_reduction = P->coarse_n == 0 && use_single_reduction(P, o);
+  return (*single_reduction ? run_pcg2 : run_pcg)(P, o, tol, etol2, resume_iters, iters_out, rel_out);
 }
 
 }  // namespace
