@@ -279,6 +279,8 @@ __global__ void __launch_bounds__(GSFM_BLOCK) k_col_s(ColRowSArgs a) {
 // Dense assembly for the exact Cholesky step (k_dense_assemble's twin on this layout): the blocks are stored in the body frame,
 // H_km = -R_k B R_m^T; the lower triangle takes the entry whose row camera has the larger index.  One workgroup per ColWg for the
 // entries, a grid-stride loop over the cameras for the diagonal blocks, the right-hand side and the padding.  A is zero-filled before.
+// A block's positions are sorted by (camera, row, edge), so the entries of a repeated pair are adjacent: the lane of the first one adds
+// the run in position order, from +0.0, and writes the cell once -- also where the run crosses into a sub-chunk of another workgroup.
 __global__ void __launch_bounds__(GSFM_BLOCK) k_dense_assemble_col(DenseArgs a, ColLayoutDev L) {
   for (uint32_t row = blockIdx.x * GSFM_BLOCK + threadIdx.x; row < a.n_rows; row += gridDim.x * GSFM_BLOCK) {
     for (int c = 0; c < 3; ++c) a.rcg[3 * (size_t)row + c] = 0.0;
@@ -290,19 +292,37 @@ __global__ void __launch_bounds__(GSFM_BLOCK) k_dense_assemble_col(DenseArgs a, 
     if (row == 0) for (uint32_t g = a.n; g < a.T * 32; ++g) *dense_elem(a.A, g, g) = 1.0;
   }
   const ColWg w = L.wg[blockIdx.x];
+  // the block's positions: its first task (chunk 0) starts them, its last task (chunk nch - 1) ends them (build_colsort)
+  const uint32_t nblk = L.n_wg / L.nch, b = w.row0 / GSFM_COL_RB;
+  const uint32_t p0 = L.wg[b].first_sub * GSFM_COL_SUB;
+  const ColWg wl = L.wg[(L.nch - 1) * nblk + b];
+  const uint32_t p1 = (wl.first_sub + wl.n_sub) * GSFM_COL_SUB;
   for (uint32_t d = w.first_sub * GSFM_COL_SUB + threadIdx.x; d < (w.first_sub + w.n_sub) * GSFM_COL_SUB; d += GSFM_BLOCK) {
     const uint2 mt = col_load_meta(L.meta + d);
     if (mt.x == GSFM_COL_PAD) continue;
-    const uint32_t row = w.row0 + col_rowl(mt.y), m = mt.x & 0x7fffffffu;
+    const uint32_t rl = col_rowl(mt.y), row = w.row0 + rl, m = mt.x & 0x7fffffffu;
     if (m >= row) continue;
-    const double2 A0 = a.h0[d], B0 = a.h1[d], C0 = a.h2[d];
-    const double Bm[9] = {A0.x, A0.y, B0.x, A0.y, B0.y, C0.x, B0.x, C0.x, C0.y};
-    double Rk[9], Rm[9], T[9], H[9];
+    if (d > p0) {   // not the first entry of its (camera, row) run
+      const uint2 pv = col_load_meta(L.meta + d - 1);
+      if ((pv.x & 0x7fffffffu) == m && col_rowl(pv.y) == rl) continue;
+    }
+    double Rk[9], Rm[9], S[9];
     qmat(load_q(a.q, row), Rk);
     qmat(load_q(a.q, m), Rm);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) T[3 * r + c] = Bm[3 * r] * Rm[3 * c] + Bm[3 * r + 1] * Rm[3 * c + 1] + Bm[3 * r + 2] * Rm[3 * c + 2];   // B R_m^T
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) H[3 * r + c] = -(Rk[3 * r] * T[c] + Rk[3 * r + 1] * T[3 + c] + Rk[3 * r + 2] * T[6 + c]);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) atomicAdd(dense_elem(a.A, 3 * row + r, 3 * m + c), H[3 * r + c]);
+    for (int k = 0; k < 9; ++k) S[k] = 0.0;
+    for (uint32_t e = d; e < p1; ++e) {
+      if (e > d) {
+        const uint2 nx = col_load_meta(L.meta + e);
+        if (nx.x == GSFM_COL_PAD || (nx.x & 0x7fffffffu) != m || col_rowl(nx.y) != rl) break;
+      }
+      const double2 A0 = a.h0[e], B0 = a.h1[e], C0 = a.h2[e];
+      const double Bm[9] = {A0.x, A0.y, B0.x, A0.y, B0.y, C0.x, B0.x, C0.x, C0.y};
+      double T[9], H[9];
+      for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) T[3 * r + c] = Bm[3 * r] * Rm[3 * c] + Bm[3 * r + 1] * Rm[3 * c + 1] + Bm[3 * r + 2] * Rm[3 * c + 2];   // B R_m^T
+      for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) H[3 * r + c] = -(Rk[3 * r] * T[c] + Rk[3 * r + 1] * T[3 + c] + Rk[3 * r + 2] * T[6 + c]);
+      for (int k = 0; k < 9; ++k) S[k] += H[k];
+    }
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) *dense_elem(a.A, 3 * row + r, 3 * m + c) = S[3 * r + c];
   }
 }
 

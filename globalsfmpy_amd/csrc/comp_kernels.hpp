@@ -81,22 +81,11 @@ __global__ void __launch_bounds__(GSFM_BLOCK) k_comp_assemble(DenseArgs a, CompM
     const uint32_t m = a.col[d] & 0x7fffffffu;
     if (m >= row) continue;   // upper triangle; (m and row are in the same component: cm.item[m] == ci)
     const uint32_t lm = cm.loc[m];
+    // the numbering inside a component follows the cameras' order, so lm < lr and the entry is in the lower triangle; the directed
+    // entries of a repeated pair are added in CSR order by the lane of the first of them (k_dense_assemble)
     double H[9];
-    if (a.lap) {
-      const double2 A0 = a.h0[d], B0 = a.h1[d], C0 = a.h2[d];
-      const double Gm[9] = {A0.x, A0.y, B0.x, A0.y, B0.y, C0.x, B0.x, C0.x, C0.y};
-      double Rk[9], Rm[9], T[9];
-      qmat(load_q(a.q, row), Rk);
-      qmat(load_q(a.q, m), Rm);
-      for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) T[3 * r + c] = Rk[3 * r] * Rm[3 * c] + Rk[3 * r + 1] * Rm[3 * c + 1] + Rk[3 * r + 2] * Rm[3 * c + 2];   // R_k R_m^T
-      for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) H[3 * r + c] = -(Gm[3 * r] * T[c] + Gm[3 * r + 1] * T[3 + c] + Gm[3 * r + 2] * T[6 + c]);
-    } else {
-      const double2 A0 = a.h0[d], B0 = a.h1[d], C0 = a.h2[d], D0 = a.h3[d];
-      H[0] = A0.x; H[1] = A0.y; H[2] = B0.x; H[3] = B0.y; H[4] = C0.x; H[5] = C0.y; H[6] = D0.x; H[7] = D0.y; H[8] = a.h4[d];
-    }
-    // the numbering inside a component follows the cameras' order, so lm < lr and the entry is in the lower triangle; several directed
-    // entries of a repeated pair add up
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) atomicAdd(dense_elem(it.A, 3 * lr + r, 3 * lm + c), H[3 * r + c]);
+    if (!dense_pair_sum(a, row, m, d, H, lrow)) continue;
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) *dense_elem(it.A, 3 * lr + r, 3 * lm + c) = H[3 * r + c];
   }
 }
 // b_pcg = b with the factorised components' entries zeroed (PCG's right-hand side)
