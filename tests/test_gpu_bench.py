@@ -20,8 +20,8 @@ def _json_line(stdout):
 
 
 def test_bench_single_gpu_contract_line(tmp_path):
-    # (with the cpu_baseline leg: the oracle solves the same graph, so the line carries a device-vs-CPU comparison that is asserted below)
-    small = [a for a in SMALL]
+    # --full, with the cpu_baseline leg: the oracle solves the same graph, so the line carries a device-vs-CPU comparison that is asserted below
+    small = [a for a in SMALL] + ["--full"]
     small[small.index("--cpu-baseline") + 1] = "1"
     dump = tmp_path / "outputs"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + small + ["--cpu-single-cams", "0", "--dump-outputs", str(dump)],
@@ -54,13 +54,38 @@ def test_bench_single_gpu_contract_line(tmp_path):
     assert cost.dtype == np.float64 and cost[1] == out["final_cost"] and not (dump / "rotations_cameras.npy").exists()
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full the line carries the headline and the timed solves' own summary, and none of the legs that need runs of their own;
+    its `value` comes from the same timed solves as under --full: the dumped rotations and costs are identical bit for bit."""
+    lines, dumps = {}, {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--tree-init", "0", "--sigma-pass", "0"])):
+        dumps[mode] = tmp_path / mode
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + extra + ["--dump-outputs", str(dumps[mode])],
+                           cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines[mode] = _json_line(r.stdout)
+    out = lines["plain"]
+    assert out["metric"] == "edge_residuals_per_sec" and out["unit"] == "edge-residuals/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    moved = ("roofline", "roofline_other", "kernels_us", "state_transfer", "exact_schedule", "iters_to_1e-6_by_schedule", "spanning_tree_init",
+             "value_tree_init", "small_graph_ms", "cpu_baseline", "mean_angular_error_vs_ground_truth_deg")
+    assert not set(moved) & set(out), sorted(set(moved) & set(out))
+    assert {"roofline", "kernels_us", "state_transfer", "exact_schedule", "mean_angular_error_vs_ground_truth_deg"} <= set(lines["full"])
+    for key in ("lm_iterations", "residual_sweeps_per_solve", "cg_iterations_per_solve", "final_cost"):
+        assert out[key] == lines["full"][key], key
+    for name in ("rotations", "cost"):
+        a, b = np.load(dumps["plain"] / (name + ".npy")), np.load(dumps["full"] / (name + ".npy"))
+        assert a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64)), name
+    assert np.load(dumps["plain"] / "cost.npy")[1] == out["final_cost"]
+
+
 def test_bench_two_ranks_on_one_gpu_over_gloo():
     """`python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2`: camera partition, sharded problem creation (with its
     agreement all-reduce), all-gathers inside PCG, max-over-ranks timing, rank 0's JSON line."""
     env = dict(os.environ, GSFM_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", GSFM_BENCH_PEER="1")   # (+ the peer-store variant, which nccl launches try by default)
     port = 29900 + os.getpid() % 90
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full"] + SMALL
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out = _json_line(r.stdout)

@@ -1,14 +1,14 @@
 # round-5 artefacts (one box call): kernel trace of the benchmark command, PMC traffic of the hot kernels, SQ counters of the sweep
-# specialisations that sit below 0.60 of the HBM roofline (what binds them), the plain bench line
+# specialisations that sit below 0.60 of the HBM roofline (what binds them), the full bench line
 set -x
 cd "$(dirname "$0")/.."
 ROOT=$PWD
 export TMPDIR=/tmp
 OUT=$ROOT/gpurun_out/r05_final
 rm -rf "$OUT"; mkdir -p "$OUT"
-(cd /tmp && rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o r05 -- python "$ROOT/bench.py" --steps 5 --warmup 2 --cpu-baseline 0 --small-graphs 0 --tree-init 0 > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err")
+(cd "$TMPDIR" && rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o r05 -- python "$ROOT/bench.py" --full --steps 5 --warmup 2 --cpu-baseline 0 --small-graphs 0 --tree-init 0 > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err")
 DB=$(find "$OUT/trace" -name '*.db' | head -1)
-python profiles/summarize_rocpd.py "$DB" "round 5 (final tree): python bench.py --steps 5 --warmup 2 --cpu-baseline 0 --small-graphs 0 --tree-init 0, C5, 1x MI355X" > "$OUT/r05_kernel_stats.txt"
+python profiles/summarize_rocpd.py "$DB" "round 5 (final tree): python bench.py --full --steps 5 --warmup 2 --cpu-baseline 0 --small-graphs 0 --tree-init 0, C5, 1x MI355X" > "$OUT/r05_kernel_stats.txt"
 find "$OUT/trace" -name '*.db' -size +40M -delete
 for c in FETCH_SIZE WRITE_SIZE; do
   (cd /tmp && timeout 500 rocprofv3 --kernel-trace --pmc $c -d "$OUT/pmc_$c" -o pmc -- python "$ROOT/tools/r04_pmc_probe.py" > "$OUT/pmc_$c.log" 2>&1)
@@ -25,5 +25,5 @@ for grp in "sq_a:SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT
   if [ -n "$f" ]; then python profiles/summarize_pmc_db.py "$f" k_cost k_lin k_mv > "$OUT/sq/$name.txt" 2>&1; find "$d" -name '*.db' -size +30M -delete; fi
 done
 cp "$OUT/r05_pmc_traffic.json" profiles/r05_pmc_traffic.json   # so that the bench run below reports it (same kernel sources)
-timeout 900 python bench.py > "$OUT/r05_bench.json" 2> "$OUT/r05_bench.err"
+timeout 900 python bench.py --full > "$OUT/r05_bench.json" 2> "$OUT/r05_bench.err"
 head -5 "$OUT/r05_kernel_stats.txt"; head -c 600 "$OUT/r05_bench.json"

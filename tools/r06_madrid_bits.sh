@@ -2,7 +2,7 @@
 cd "$(dirname "$0")/.."
 for lib in default tools/_ab/libgsfm_rot_q4.so tools/_ab/libgsfm_rot_r05.so; do
   if [ $lib = default ]; then unset GSFM_ROT_LIB; else export GSFM_ROT_LIB=$PWD/$lib; fi
-  python bench.py --cams 20000 --edges 400000 --steps 1 --warmup 1 --tree-init 0 --sigma-pass 0 --cpu-baseline 1 --cpu-single-cams 0 2>/dev/null | python -c "
+  python bench.py --full --cams 20000 --edges 400000 --steps 1 --warmup 1 --tree-init 0 --sigma-pass 0 --cpu-baseline 1 --cpu-single-cams 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 m=d['small_graph_ms']['C1_madrid_394_views_23784_edges_cov_magsac']

@@ -2,7 +2,7 @@
 # latency-bound configurations, smoke, and the randomised suites that exercise the dense / component steps
 cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/r06b_final; rm -rf $OUT; mkdir -p $OUT
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r06b_bench.json 2> $OUT/r06b_bench.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r06b_bench.json 2> $OUT/r06b_bench.err
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1
 bash tools/r06b_latency_traces.sh > $OUT/latency.log 2>&1
 mkdir -p $OUT/latency_after; cp gpurun_out/r06b_latency/*_gaps.txt $OUT/latency_after/
