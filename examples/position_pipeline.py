@@ -1,0 +1,40 @@
+#!/usr/bin/env python3
+"""The reference's scripts/sfm_pipeline.py 1DSfM branch through step 7: rotations, FilterRotations(), then camera positions
+(EstimatePosition(HuberLoss(0.1), PositionErrorType.BASELINE) there; NonlinearPositionEstimator.EstimatePositions here) and the PLY
+with the estimated camera positions.
+usage: position_pipeline.py <dataset_dir with EGs.txt, cc.txt> [flags.yaml]"""
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "globalsfmpy_amd"))  # like sys.path.append('../build')
+sys.path.insert(0, os.path.dirname(HERE))
+
+import GlobalSfMpy as sfm  # noqa: E402
+from globalsfmpy_amd.loss_functions import HuberLoss  # noqa: E402
+
+
+def position_pipeline(dataset_dir, flagfile=None):
+    opts = sfm.ReconstructionBuilderOptions()
+    if flagfile:
+        sfm.load_1DSFM_config(flagfile, opts)
+    scene, graph, edge_cov = sfm.Reconstruction(), sfm.ViewGraph(), sfm.MapEdgesCovariance()
+    sfm.Read1DSFM(dataset_dir, scene, graph, edge_cov)
+    solver = sfm.GlobalReconstructionEstimator(opts.reconstruction_estimator_options)
+    solver.FilterInitialViewGraphAndCalibrateCameras(graph, scene)
+    assert solver.EstimateGlobalRotations(HuberLoss(0.1)), solver.LastError()
+    solver.FilterRotations()
+    positions = sfm.MapViewIdVector3d()
+    estimator = sfm.NonlinearPositionEstimator()
+    assert estimator.EstimatePositions(graph.GetAllEdges(), solver.orientations, positions, HuberLoss(0.1),
+                                       sfm.PositionErrorType.BASELINE), estimator.LastError()
+    sfm.SetReconstructionFromEstimatedPoses(solver.orientations, positions, scene)
+    return scene, estimator
+
+
+if __name__ == "__main__":
+    dataset = sys.argv[1]
+    scene, estimator = position_pipeline(dataset, sys.argv[2] if len(sys.argv) > 2 else None)
+    print("estimated %d positions (view %d held at the origin); solver summary: %s"
+          % (len(scene.EstimatedPositions()), estimator.FixedView(), estimator.LastSummary()))
+    sfm.WritePlyFile(os.path.join(dataset, "positions_out.ply"), scene, 2)

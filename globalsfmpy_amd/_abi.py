@@ -79,6 +79,41 @@ class Summary(C.Structure):
         return d
 
 
+class PosOptions(C.Structure):
+    """gsfm_pos_options (include/gsfm_pos.h)"""
+    _fields_ = [
+        ("max_num_iterations", C.c_int32), ("jacobi_scaling", C.c_int32),
+        ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
+        ("parameter_tolerance", C.c_double), ("initial_trust_region_radius", C.c_double),
+        ("max_trust_region_radius", C.c_double), ("min_trust_region_radius", C.c_double),
+        ("min_relative_decrease", C.c_double), ("min_lm_diagonal", C.c_double),
+        ("max_lm_diagonal", C.c_double), ("dense_max_cams", C.c_int32),
+        ("max_cg_iterations", C.c_int32), ("cg_relative_tolerance", C.c_double),
+        ("cg_check_interval", C.c_int32), ("cg_stall_iterations", C.c_int32),
+        ("remove_scale_gauge", C.c_int32), ("verbose", C.c_int32),
+    ]
+
+
+class PosSummary(C.Structure):
+    """gsfm_pos_summary (include/gsfm_pos.h)"""
+    _fields_ = [
+        ("termination", C.c_int32), ("num_iterations", C.c_int32),
+        ("num_successful_steps", C.c_int32), ("num_unsuccessful_steps", C.c_int32),
+        ("num_cg_iterations", C.c_int32), ("num_dense_solves", C.c_int32),
+        ("num_pcg_stalled_steps", C.c_int32), ("num_residual_sweeps", C.c_int32),
+        ("num_linearizations", C.c_int32), ("nonfinite", C.c_int32),
+        ("num_edges_used", C.c_uint64),
+        ("initial_cost", C.c_double), ("final_cost", C.c_double),
+        ("final_gradient_max_norm", C.c_double), ("final_radius", C.c_double),
+        ("max_radius", C.c_double), ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["termination_name"] = TERMINATION_NAMES[self.termination] if 0 <= self.termination < 5 else "?"
+        return d
+
+
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 ALL_REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 LOSS_CALLBACK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_double, C.POINTER(C.c_double))
@@ -214,5 +249,19 @@ def load_library():
     lib.gsfm_cov_estimate.restype = C.c_int
     lib.gsfm_magsac_table.argtypes = [C.c_int32, _DP, C.c_int32]; lib.gsfm_magsac_table.restype = C.c_int32
     lib.gsfm_magsac_constants.argtypes = [C.c_int32, _DP, _DP, _DP]; lib.gsfm_magsac_constants.restype = C.c_int
+    declare_position_signatures(lib)
     _lib = lib
     return lib
+
+
+def declare_position_signatures(lib):
+    """include/gsfm_pos.h"""
+    lib.gsfm_pos_abi_version.restype = C.c_int
+    lib.gsfm_pos_options_default.argtypes = [C.POINTER(PosOptions)]; lib.gsfm_pos_options_default.restype = None
+    lib.gsfm_pos_problem_create.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, _DP, _DP, C.POINTER(C.c_void_p)]
+    lib.gsfm_pos_problem_create.restype = C.c_int
+    lib.gsfm_pos_set_loss.argtypes = [C.c_void_p, C.POINTER(LossNode), C.c_int32]; lib.gsfm_pos_set_loss.restype = C.c_int
+    lib.gsfm_pos_set_loss_callback.argtypes = [C.c_void_p, LOSS_CALLBACK_FN, C.c_void_p]; lib.gsfm_pos_set_loss_callback.restype = C.c_int
+    lib.gsfm_pos_solve.argtypes = [C.c_void_p, _DP, C.c_int32, C.POINTER(PosOptions), C.POINTER(PosSummary)]; lib.gsfm_pos_solve.restype = C.c_int
+    lib.gsfm_pos_residuals.argtypes = [C.c_void_p, _DP, _DP, _DP]; lib.gsfm_pos_residuals.restype = C.c_int
+    lib.gsfm_pos_problem_destroy.argtypes = [C.c_void_p]; lib.gsfm_pos_problem_destroy.restype = None

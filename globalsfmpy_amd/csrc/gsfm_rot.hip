@@ -10,6 +10,7 @@
 #include "solver_lm.hpp"
 #include "problem_create.hpp"
 #include "spanning_tree.hpp"
+#include "solver_pos.hpp"
 
 // =============================================================================================
 extern "C" {

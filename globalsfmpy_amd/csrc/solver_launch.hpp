@@ -106,10 +106,10 @@ int read_back(gsfm_rot_problem* P, void* dst, const void* src_dev, size_t bytes,
 }
 
 // ---- loss preparation ---------------------------------------------------------------------
-int prepare_loss(gsfm_rot_problem* P, const gsfm_loss_node* prog, int n) {
+// The device form of a loss program (node checks, MAGSAC constants, the tables uploaded once into tables[0..2]): shared by the rotation
+// problem (prepare_loss) and the position problem (solver_pos.hpp).
+int build_dev_loss(const gsfm_loss_node* prog, int n, DevBuf<double>* tables, DevLoss& L) {
   if (n < 0 || n > GSFM_LOSS_MAX_NODES) return fail(GSFM_ERR_INVALID_ARG, "loss program length out of range");
-  P->loss_epoch++;   // (captured LM iterations froze the kernels the old loss selected)
-  DevLoss L;
   std::memset(&L, 0, sizeof(L));
   L.n = n;
   int nr = 0, na = 1;
@@ -156,15 +156,23 @@ int prepare_loss(gsfm_rot_problem* P, const gsfm_loss_node* prog, int n) {
         d.x_clamp = 0;
         while (d.x_clamp < c.n && (double)d.x_clamp * (2.0 * squared_sigma) / 1000.0 < 1e-7) d.x_clamp++;   // cells whose s = x 2 sigma^2 / 1000 the reference lifts to 1e-7 (:317)
         const int ti = nu == 3 ? 0 : nu == 4 ? 1 : 2;
-        if (!P->tables[ti].p) {
-          if (P->tables[ti].upload(magsac_table(nu)) != hipSuccess) return fail(GSFM_ERR_HIP, "uploading MAGSAC table failed");
+        if (!tables[ti].p) {
+          if (tables[ti].upload(magsac_table(nu)) != hipSuccess) return fail(GSFM_ERR_HIP, "uploading MAGSAC table failed");
         }
-        d.table = P->tables[ti].p; d.table_len = c.n;
+        d.table = tables[ti].p; d.table_len = c.n;
         ++nr; break; }
       default: return fail(GSFM_ERR_INVALID_ARG, "loss program: unknown node kind");
     }
   }
   if (n > 0 && (nr != 1 || na != 1)) return fail(GSFM_ERR_INVALID_ARG, "loss program does not reduce to one value");
+  return 0;
+}
+
+int prepare_loss(gsfm_rot_problem* P, const gsfm_loss_node* prog, int n) {
+  if (n < 0 || n > GSFM_LOSS_MAX_NODES) return fail(GSFM_ERR_INVALID_ARG, "loss program length out of range");
+  P->loss_epoch++;   // (captured LM iterations froze the kernels the old loss selected)
+  DevLoss L;
+  if (int st = build_dev_loss(prog, n, P->tables, L)) return st;
   // K2's fast path assumes rho'' <= 0 for every s (Ceres' Corrector then always takes its alpha = 0 branch).  That is a property of the leaf
   // kind AND of its parameters: Geman-McClure, rho'' = -g2^2 / (a^2 t^3) with t = s / a^2 + g2, turns positive for a negative sigma^2 (g2);
   // a MAGSAC weight loss with a negative sigma flips the sign of rho' and rho''.  Anything doubtful takes the general path (full Corrector).

@@ -13,6 +13,7 @@
 #include <fstream>
 #include <memory>
 
+#include "../../include/gsfm/GSfM_nonlinear_position_estimator.hpp"
 #include "../../include/gsfm/GSfM_nonlinear_rotation_estimator.hpp"
 #include "../../include/gsfm/evaluation.hpp"
 #include "../../include/gsfm/view_graph.hpp"
@@ -213,6 +214,18 @@ class GlobalReconstructionEstimator {
   std::string error_;
 };
 
+py::dict pos_summary_dict(const gsfm_pos_summary& s) {
+  py::dict d;
+  d["termination"] = s.termination; d["num_iterations"] = s.num_iterations;
+  d["num_successful_steps"] = s.num_successful_steps; d["num_unsuccessful_steps"] = s.num_unsuccessful_steps;
+  d["num_cg_iterations"] = s.num_cg_iterations; d["num_dense_solves"] = s.num_dense_solves; d["num_pcg_stalled_steps"] = s.num_pcg_stalled_steps;
+  d["num_residual_sweeps"] = s.num_residual_sweeps; d["num_linearizations"] = s.num_linearizations; d["nonfinite"] = s.nonfinite;
+  d["num_edges_used"] = s.num_edges_used; d["initial_cost"] = s.initial_cost; d["final_cost"] = s.final_cost;
+  d["final_gradient_max_norm"] = s.final_gradient_max_norm; d["final_radius"] = s.final_radius; d["max_radius"] = s.max_radius;
+  d["t_total_ms"] = s.t_total_ms;
+  return d;
+}
+
 void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions& options) {
   // bind :185-271 parses the YAML with yaml-cpp; only the keys the rotation stage consumes are read here.
   py::gil_scoped_acquire gil;
@@ -242,14 +255,38 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .value("ANGLE_AXIS", RotationErrorType::ANGLE_AXIS)
       .value("ANGLE_AXIS_COVTRACE", RotationErrorType::ANGLE_AXIS_COVTRACE)
       .value("ANGLE_AXIS_COVNORM", RotationErrorType::ANGLE_AXIS_COVNORM);
-  enum class PositionErrorType { BASELINE = 0 };
-  py::enum_<PositionErrorType>(m, "PositionErrorType", py::arithmetic()).value("BASELINE", PositionErrorType::BASELINE);
+  py::enum_<PositionErrorType>(m, "PositionErrorType", py::arithmetic()).value("BASELINE", PositionErrorType::BASELINE);   // the one value bound
 
   py::class_<ceres::LossFunction, PyLoss>(m, "LossFunction").def(py::init<>());
 
   py::class_<RotationEstimator, PyRotationEstimator>(m, "RotationEstimator")
       .def(py::init<>())
       .def("EstimateRotations", &RotationEstimator::EstimateRotations);
+
+  // reference src/GSfM_nonlinear_position_estimator.cpp on the device (include/gsfm_pos.h): fills `positions` in place; the view held
+  // constant is positions->begin() of the map, as in the reference (FixedView() tells which)
+  py::class_<GSfMNonlinearPositionEstimator>(m, "NonlinearPositionEstimator")
+      .def(py::init<>())
+      .def(py::init([](int max_num_iterations, double robust_loss_width) {
+             GSfMNonlinearPositionEstimator::Options o;
+             o.max_num_iterations = max_num_iterations; o.robust_loss_width = robust_loss_width;
+             return new GSfMNonlinearPositionEstimator(o);
+           }), py::arg("max_num_iterations") = 400, py::arg("robust_loss_width") = 0.1)
+      .def("EstimatePositions",
+           [](GSfMNonlinearPositionEstimator& e, const EdgeMap& vp, const OrientationMap& o, OrientationMap* positions, ceres::LossFunction* loss,
+              PositionErrorType type) { return e.EstimatePositions(vp, o, positions, type, loss); },
+           py::arg("view_pairs"), py::arg("orientations"), py::arg("positions"), py::arg("loss_function") = nullptr,
+           py::arg("position_error_type") = PositionErrorType::BASELINE, py::call_guard<py::gil_scoped_release>())
+      .def("FixedView", &GSfMNonlinearPositionEstimator::FixedView)
+      .def("LastSummary", [](const GSfMNonlinearPositionEstimator& e) { return pos_summary_dict(e.LastSummary()); })
+      .def("LastError", [](const GSfMNonlinearPositionEstimator& e) { return std::string(e.LastError()); })
+      .def("SetSolverOption", [](GSfMNonlinearPositionEstimator& e, const std::string& name, double v) {   // a few fields of gsfm_pos_options
+        gsfm_pos_options* o = e.MutableOptions();
+        if (name == "dense_max_cams") o->dense_max_cams = (int32_t)v;
+        else if (name == "remove_scale_gauge") o->remove_scale_gauge = (int32_t)v;
+        else if (name == "cg_relative_tolerance") o->cg_relative_tolerance = v;
+        else throw std::invalid_argument("unknown position solver option " + name);
+      });
 
   py::class_<GSfMNonlinearRotationEstimator, RotationEstimator>(m, "NonlinearRotationEstimator")
       .def(py::init<>())
@@ -288,6 +325,7 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def("NumTracks", &Reconstruction::NumTracks)
       .def("NumViews", &Reconstruction::NumViews)
       .def("EstimatedOrientations", [](const Reconstruction& r) { return r.orientation; })
+      .def("EstimatedPositions", [](const Reconstruction& r) { return r.position; })
       .def("ViewNames", [](const Reconstruction& r) { return r.view_names; })
       .def("SetViewName", [](Reconstruction& r, ViewId v, const std::string& name) { r.views.insert(v); r.view_names[v] = name; })
       .def("SetOrientation", [](Reconstruction& r, ViewId v, const Eigen::Vector3d& aa) { r.views.insert(v); r.orientation[v] = aa; })
@@ -426,6 +464,18 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
     rec->orientation.clear();
     for (const auto& kv : o) if (rec->views.count(kv.first)) rec->orientation[kv.first] = kv.second;
   });
+  // bind :273 (Theia's SetReconstructionFromEstimatedPoses): the orientation and, where there is
+  // one, the position of every view of the reconstruction that has an estimated orientation
+  m.def("SetReconstructionFromEstimatedPoses", [](const OrientationMap& o, const OrientationMap& p, Reconstruction* rec) {
+    rec->orientation.clear();
+    rec->position.clear();
+    for (const auto& kv : o) {
+      if (!rec->views.count(kv.first)) continue;
+      rec->orientation[kv.first] = kv.second;
+      auto it = p.find(kv.first);
+      if (it != p.end()) rec->position[kv.first] = it->second;
+    }
+  }, py::call_guard<py::gil_scoped_release>());
   m.def("InitGlog", [](int, bool, std::string) {}, py::arg("log_level") = 0, py::arg("logtostderr") = true, py::arg("log_dir") = "./log");
   m.def("StopGlog", []() {});
   m.def("WriteReconstruction", [](const Reconstruction& rec, const std::string& path) {
@@ -435,8 +485,8 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
     return (bool)f;
   });
   // bind :631 / Theia io/write_ply_file.cc:74-123: tracks (3-D points) and the positions of the estimated views as green vertices.
-  // A rotation-only reconstruction has no tracks and no camera positions, so the file holds one green vertex at the origin per
-  // estimated view -- the same header, the same vertex format, so sfm_pipeline.py's __main__ (:146) runs through.
+  // There are no tracks: the file holds one green vertex per estimated view, at its estimated position where it has one
+  // (SetReconstructionFromEstimatedPoses), else at the origin (a rotation-only reconstruction) -- the header and vertex format of Theia.
   m.def("WritePlyFile", [](const std::string& ply_file, const Reconstruction& rec, int /*min_num_observations_per_point*/) {
     if (ply_file.empty()) throw std::invalid_argument("WritePlyFile: empty file name");
     std::ofstream f(ply_file);
@@ -445,7 +495,12 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
     for (const auto& kv : rec.orientation) n += rec.views.count(kv.first);
     f << "ply\nformat ascii 1.0\nelement vertex " << n
       << "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header" << std::endl;
-    for (const auto& kv : rec.orientation) if (rec.views.count(kv.first)) f << "0 0 0 0 255 0\n";
+    for (const auto& kv : rec.orientation) {
+      if (!rec.views.count(kv.first)) continue;
+      auto it = rec.position.find(kv.first);
+      if (it == rec.position.end()) f << "0 0 0 0 255 0\n";
+      else f << it->second[0] << " " << it->second[1] << " " << it->second[2] << " 0 255 0\n";
+    }
     return (bool)f;
   }, py::call_guard<py::gil_scoped_release>());
   // ---- evaluation (bind :387-394, :396-403, :651-664; orientations only) ----

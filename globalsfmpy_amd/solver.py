@@ -353,3 +353,57 @@ def orientations_from_maximum_spanning_tree(n_cams, edge_i, edge_j, rel_aa, weig
         raise SolverError("gsfm_rot_init_spanning_tree failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
     return {"rot_aa": rot, "parent_edge": parent, "root": int(root.value), "n_tree_cams": int(n_tree.value), "depth": int(depth.value),
             "kernel_ms": ms.value}
+
+
+class PositionProblem(ProblemBase):
+    """Camera positions from relative translations (include/gsfm_pos.h): the reference's EstimatePositions with BASELINE residuals
+    r = (c_j - c_i) / |c_j - c_i| - R(aa_i)^T t_ij on the device.  rel_t: E x 3 position_2 of each view pair (frame of camera i);
+    rot_aa: N x 3 angle-axis orientations.  A new problem has Ceres' NULL loss; set_loss takes the rotation path's descriptors."""
+
+    _prefix = "gsfm_pos_"
+
+    def __init__(self, n_cams, edge_i, edge_j, rel_t, rot_aa):
+        lib = _abi.load_library()
+        ei = np.ascontiguousarray(edge_i, dtype=np.uint32)
+        ej = np.ascontiguousarray(edge_j, dtype=np.uint32)
+        rel = np.ascontiguousarray(rel_t, dtype=np.float64).reshape(-1, 3)
+        rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(int(n_cams), 3)
+        if not (ei.shape == ej.shape == (rel.shape[0],)):
+            raise ValueError("edge_i, edge_j and rel_t must describe the same edges")
+        h = C.c_void_p()
+        st = lib.gsfm_pos_problem_create(int(n_cams), ei.size, _u32p(ei), _u32p(ej), _dp(rel), _dp(rot), C.byref(h))
+        if st != 0:
+            raise SolverError("gsfm_pos_problem_create failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+        ProblemBase.__init__(self, lib, h, n_cams, ei.size, -1, 3)
+
+    def _last_error(self):
+        return self._lib.gsfm_last_error().decode("utf-8", "replace")
+
+    def default_options(self):
+        o = _abi.PosOptions()
+        self._lib.gsfm_pos_options_default(C.byref(o))
+        return o
+
+    def solve(self, init=None, fixed_cam=0, **options):
+        """init: N x 3 start positions, None = the reference's all-zero start.  fixed_cam: the camera held constant (-1: none).
+        Returns (positions, summary dict)."""
+        pos = np.zeros((self.n_cams, 3)) if init is None else np.array(init, dtype=np.float64, order="C").reshape(self.n_cams, 3)
+        o = self._options(options)
+        s = _abi.PosSummary()
+        st = self._lib.gsfm_pos_solve(self._h, _dp(pos), int(fixed_cam), C.byref(o), C.byref(s))
+        self._reraise_callback_error()
+        self._check(st, "solve")
+        return pos, s.as_dict()
+
+    def residuals(self, pos):
+        """(r: E x 3, rho: E) at pos"""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(self.n_cams, 3)
+        r = np.empty((self.n_edges, 3))
+        rho = np.empty(self.n_edges)
+        st = self._lib.gsfm_pos_residuals(self._h, _dp(pos), _dp(r), _dp(rho))
+        self._reraise_callback_error()
+        self._check(st, "residuals")
+        return r, rho
+
+    def set_edge_weights(self, w):
+        raise NotImplementedError("position residuals have weight 1 (the reference's BASELINE error)")

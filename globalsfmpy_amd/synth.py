@@ -229,3 +229,64 @@ def matrix_to_quat(R):
     q[..., 1] = np.where(c0, (R[..., 0, 2] - R[..., 2, 0]) * s, np.where(c1, (R[..., 0, 1] + R[..., 1, 0]) * s, np.where(c2, 0.5 * t, (R[..., 1, 2] + R[..., 2, 1]) * s)))
     q[..., 2] = np.where(c0, (R[..., 1, 0] - R[..., 0, 1]) * s, np.where(c1, (R[..., 0, 2] + R[..., 2, 0]) * s, np.where(c2, (R[..., 1, 2] + R[..., 2, 1]) * s, 0.5 * t)))
     return q
+
+
+def aa_to_matrix(aa):
+    """Rotation matrices of angle-axis vectors (..., 3) -> (..., 3, 3), as Ceres' AngleAxisToRotationMatrix computes them (its
+    first-order form below theta^2 = machine epsilon included)."""
+    aa = np.asarray(aa, dtype=np.float64)
+    th2 = np.sum(aa * aa, axis=-1)
+    big = th2 > np.finfo(np.float64).eps
+    th = np.sqrt(np.where(big, th2, 1.0))
+    w = aa / th[..., None]
+    c, s = np.cos(th), np.sin(th)
+    wx, wy, wz = w[..., 0], w[..., 1], w[..., 2]
+    R = np.empty(aa.shape[:-1] + (3, 3))
+    R[..., 0, 0] = c + wx * wx * (1 - c); R[..., 1, 0] = wz * s + wx * wy * (1 - c); R[..., 2, 0] = -wy * s + wx * wz * (1 - c)
+    R[..., 0, 1] = wx * wy * (1 - c) - wz * s; R[..., 1, 1] = c + wy * wy * (1 - c); R[..., 2, 1] = wx * s + wy * wz * (1 - c)
+    R[..., 0, 2] = wy * s + wx * wz * (1 - c); R[..., 1, 2] = -wx * s + wy * wz * (1 - c); R[..., 2, 2] = c + wz * wz * (1 - c)
+    x, y, z = aa[..., 0], aa[..., 1], aa[..., 2]
+    one, zero = np.ones_like(x), np.zeros_like(x)
+    small = np.stack([np.stack([one, -z, y], -1), np.stack([z, one, -x], -1), np.stack([-y, x, one], -1)], -2)
+    return np.where(big[..., None, None], R, small)
+
+
+def make_position_graph(n_cams, n_edges, seed, outlier_frac=0.0, noise=0.0, extent=10.0, local_window=0):
+    """Returns dict(n_cams, edge_i, edge_j, rel_t, rot_aa, gt_pos, is_outlier) for camera-position estimation.
+
+    The rotations and the edge set are those make_graph(n_cams, n_edges, seed) draws (its ground-truth rotations, then make_edges from
+    the same generator), so the benchmark graph of the rotation path and this one share their topology.  Positions are uniform in a cube
+    of side 2 * extent; rel_t = position_2 = R_i (c_j - c_i) / |c_j - c_i|, its world direction perturbed by N(0, noise^2) per component
+    and renormalised; outliers (only among the non-chain edges) get uniform random unit directions.  local_window > 0: edges only
+    between cameras close in a hidden ordering (make_local_edges: a normal matrix that a sparse direct solver factorises with
+    little fill-in; not the benchmark's topology)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    rot_aa = 0.2 * rng.uniform(-1.0, 1.0, (n_cams, 3))
+    ei, ej = make_local_edges(rng, n_cams, n_edges, local_window) if local_window else make_edges(rng, n_cams, n_edges)
+    E = ei.shape[0]
+    gt = extent * rng.uniform(-1.0, 1.0, (n_cams, 3))
+    d = gt[ej] - gt[ei]
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    if noise > 0:
+        d = d + noise * rng.standard_normal((E, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+    is_out = np.zeros(E, dtype=bool)
+    if outlier_frac > 0:
+        cand = np.arange(n_cams - 1, E)
+        k = int(round(outlier_frac * E))
+        pick = rng.choice(cand, size=min(k, cand.size), replace=False)
+        is_out[pick] = True
+        u = rng.standard_normal((pick.size, 3))
+        d[pick] = u / np.linalg.norm(u, axis=1, keepdims=True)
+    rel_t = np.empty((E, 3))
+    for b0 in range(0, E, 1 << 22):   # R_i d in blocks (the 10M-edge graph)
+        sl = slice(b0, min(E, b0 + (1 << 22)))
+        rel_t[sl] = np.einsum("eij,ej->ei", aa_to_matrix(rot_aa[ei[sl]]), d[sl])
+    return {"n_cams": int(n_cams), "edge_i": ei, "edge_j": ej, "rel_t": rel_t, "rot_aa": rot_aa, "gt_pos": gt, "is_outlier": is_out}
+
+
+def gauge_normalize(pos, fixed_cam):
+    """Positions with translation and scale removed: subtract the fixed camera, divide by the RMS distance from it."""
+    p = np.asarray(pos, dtype=np.float64) - np.asarray(pos, dtype=np.float64)[fixed_cam]
+    rms = np.sqrt(np.mean(np.sum(p * p, axis=1)))
+    return p / rms if rms > 0 else p

@@ -46,6 +46,7 @@ class ViewGraph {
 class Reconstruction {
  public:
   std::unordered_map<ViewId, Eigen::Vector3d> orientation;
+  std::unordered_map<ViewId, Eigen::Vector3d> position;   // estimated camera positions (SetReconstructionFromEstimatedPoses)
   std::unordered_set<ViewId> views;
   std::unordered_map<ViewId, std::string> view_names;  // COLMAP ingestion: image file name per view
   // The matched features of the view pairs, in place of theia's tracks: all that store_covariance_rot reads of them
