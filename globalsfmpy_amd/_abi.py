@@ -264,4 +264,9 @@ def declare_position_signatures(lib):
     lib.gsfm_pos_set_loss_callback.argtypes = [C.c_void_p, LOSS_CALLBACK_FN, C.c_void_p]; lib.gsfm_pos_set_loss_callback.restype = C.c_int
     lib.gsfm_pos_solve.argtypes = [C.c_void_p, _DP, C.c_int32, C.POINTER(PosOptions), C.POINTER(PosSummary)]; lib.gsfm_pos_solve.restype = C.c_int
     lib.gsfm_pos_residuals.argtypes = [C.c_void_p, _DP, _DP, _DP]; lib.gsfm_pos_residuals.restype = C.c_int
+    lib.gsfm_pos_linearize.argtypes = [C.c_void_p, _DP, _DP, _DP, _DP]; lib.gsfm_pos_linearize.restype = C.c_int
+    lib.gsfm_pos_normal_matvec.argtypes = [C.c_void_p, _DP, _DP]; lib.gsfm_pos_normal_matvec.restype = C.c_int
+    lib.gsfm_pos_step_check.argtypes = [C.c_void_p, _DP, C.c_int32, C.c_double, C.POINTER(PosOptions), _DP, _DP, _DP, _DP, _DP,
+                                        C.POINTER(C.c_int32)]
+    lib.gsfm_pos_step_check.restype = C.c_int
     lib.gsfm_pos_problem_destroy.argtypes = [C.c_void_p]; lib.gsfm_pos_problem_destroy.restype = None

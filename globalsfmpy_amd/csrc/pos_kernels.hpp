@@ -188,7 +188,7 @@ __global__ void __launch_bounds__(256) k_pos_absmax(const double* __restrict__ a
   __shared__ double lds[5];
   double acc = 0.0;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)GSFM_POS_PARTS * 256)
-    if (!mask || mask[i / 3]) acc = fmax(acc, fabs(a[i]) + 0.0 * a[i]);   // (a NaN propagates: 0 * NaN)
+    if (!mask || mask[i / 3]) acc = fmax(acc, fabs(a[i]));   // (a NaN entry is dropped: fmax(acc, NaN) = acc, as std::fmax in the oracle)
   const double t = block_max_bcast(acc, lds);
   if (threadIdx.x == 0) part[blockIdx.x] = t;
 }

@@ -30,6 +30,7 @@ struct gsfm_pos_problem {
   void* cb_user = nullptr;
   DevBuf<double> rho_ext, s_dev;
   std::vector<double> h_s, h_rho;
+  bool have_lin = false;                   // a linearisation from gsfm_pos_linearize / gsfm_pos_step_check is on the device
 };
 
 namespace {
@@ -107,9 +108,10 @@ void pos_norms(gsfm_pos_problem* P) {
   pos_dot(P, P->x.p, P->x.p, P->active.p, PS_XNORM2);
 }
 
-// Exact step by the dense tiled Cholesky; *ok = false: not used (size, memory) or the factorisation met a non-positive pivot
-int pos_dense_step(gsfm_pos_problem* P, bool* ok) {
-  *ok = false;
+// Exact step by the dense tiled Cholesky; *ok = false: not used (size, memory; *info = -1) or the factorisation met a non-positive pivot
+// (*info > 0).  K_tiles (may be NULL): a host copy of the assembled tiles, taken before the factorisation overwrites them.
+int pos_dense_step(gsfm_pos_problem* P, bool* ok, int* info_out, std::vector<double>* K_tiles) {
+  *ok = false; *info_out = -1;
   const uint32_t n = 3 * P->n_cams, T = (n + GSFM_CB - 1) / GSFM_CB;
   if (T > GSFM_DENSE_MAX_T) return 0;
   const size_t elems = chol_num_tiles(T) * GSFM_TILE_ELEMS;
@@ -123,18 +125,25 @@ int pos_dense_step(gsfm_pos_problem* P, bool* ok) {
   HIPCHK(hipMemsetAsync(P->denseA.p, 0, 8 * elems, P->stream));
   HIPCHK(hipMemsetAsync(P->dense_info.p, 0, sizeof(int), P->stream));
   hipLaunchKernelGGL(k_pos_dense_assemble, dim3(P->n_cams), dim3(256), 0, P->stream, pos_dev(P), P->S.p, P->Mblk.p, P->b.p, P->denseA.p, n, T);
+  if (K_tiles) {
+    K_tiles->resize(elems);
+    HIPCHK(hipMemcpyAsync(K_tiles->data(), P->denseA.p, 8 * elems, hipMemcpyDeviceToHost, P->stream));
+    if (int st = pos_sync(P, "dense assembly")) return st;
+  }
   enqueue_chol_solve(P->denseA.p, P->denseL.p, P->dense_x.p, n, T, P->dense_info.p, P->stream, false);
   HIPCHK(hipMemcpyAsync(P->y.p, P->dense_x.p, 8 * (size_t)n, hipMemcpyDeviceToDevice, P->stream));
   int info = 0;
   HIPCHK(hipMemcpyAsync(&info, P->dense_info.p, sizeof(int), hipMemcpyDeviceToHost, P->stream));
   if (int st = pos_sync(P, "dense step")) return st;
+  *info_out = info;
   *ok = info == 0;
   return 0;
 }
 
-// PCG on (S L S + D^2) y = b from y = 0 (k_pos_prep set r, z, p, q); returns its iterations, *stalled: ended above the tolerance
-int pos_pcg(gsfm_pos_problem* P, const gsfm_pos_options& o, int* iters, bool* stalled) {
-  *iters = 0; *stalled = false;
+// PCG on (S L S + D^2) y = b from y = 0 (k_pos_prep set r, z, p, q); returns its iterations, *stalled: ended above the tolerance,
+// *rel: the last relative residual read back, sqrt(r.M^-1 r / b.M^-1 b) of the recursion (0 when b = 0)
+int pos_pcg(gsfm_pos_problem* P, const gsfm_pos_options& o, int* iters, bool* stalled, double* rel) {
+  *iters = 0; *stalled = false; *rel = 0.0;
   const PosDev a = pos_dev(P);
   const uint32_t N = P->n_cams;
   pos_dot(P, P->r.p, P->z.p, nullptr, PS_RZ0);
@@ -159,8 +168,9 @@ int pos_pcg(gsfm_pos_problem* P, const gsfm_pos_options& o, int* iters, bool* st
       double rz = 0.0;
       HIPCHK(hipMemcpyAsync(&rz, P->scal.p + cur, 8, hipMemcpyDeviceToHost, P->stream));
       if (int st = pos_sync(P, "pcg")) return st;
-      if (!std::isfinite(rz)) break;
-      if (std::sqrt(std::fmax(rz, 0.0) / rz0) <= o.cg_relative_tolerance) { *iters = it; return 0; }
+      *rel = std::sqrt(std::fmax(rz, 0.0) / rz0);
+      if (!std::isfinite(rz)) { *rel = rz; break; }
+      if (*rel <= o.cg_relative_tolerance) { *iters = it; return 0; }
       if (rz <= 0.25 * best) { best = rz; best_it = it; }   // the relative residual sqrt(rz / rz0) halved
       else if (o.cg_stall_iterations > 0 && it - best_it >= o.cg_stall_iterations) break;
     }
@@ -170,9 +180,42 @@ int pos_pcg(gsfm_pos_problem* P, const gsfm_pos_options& o, int* iters, bool* st
   return 0;
 }
 
-int pos_lm_solve(gsfm_pos_problem* P, int32_t fixed, const gsfm_pos_options& o, gsfm_pos_summary* sum) {
+// One LM step's linear algebra at P->x, after its linearisation and with the Jacobi scale S in place -- shared by the solve and by
+// gsfm_pos_step_check, so that the check runs the solve's own code.  LevenbergMarquardtStrategy::ComputeStep: (J^T J + D^2) y = J^T r
+// in scaled coordinates, D = sqrt(clamp(diag) / radius), step = -S y; the dense Cholesky up to dense_max_cams cameras (PCG when it is
+// not used or meets a non-positive pivot), then the step's scale-gauge part removed, the trial point P->cand, and scal[PS_STEP2],
+// scal[PS_DG] = delta.g and scal[PS_DLD] = delta^T L delta, enqueued (the caller reads them back).  K_tiles: see pos_dense_step.
+struct PosStep { bool dense = false; int info = -1; int cg = 0; bool stalled = false; double cg_rel = 0.0; };
+int pos_step(gsfm_pos_problem* P, int32_t fixed, double radius, const gsfm_pos_options& o, PosStep* out, std::vector<double>* K_tiles) {
   const uint32_t N = P->n_cams;
   const PosDev a = pos_dev(P);
+  *out = PosStep();
+  hipLaunchKernelGGL(k_pos_prep, pos_grid(N), dim3(256), 0, P->stream, N, P->active.p, P->Dg.p, P->g.p, P->S.p, radius, o.min_lm_diagonal, o.max_lm_diagonal,
+                     P->D2.p, P->Mblk.p, P->Minv.p, P->b.p, P->r.p, P->z.p, P->p.p, P->q.p, P->y.p);
+  bool solved = false;
+  if ((int64_t)N <= (int64_t)o.dense_max_cams) {
+    if (int st = pos_dense_step(P, &solved, &out->info, K_tiles)) return st;
+    if (!solved)
+      hipLaunchKernelGGL(k_pos_prep, pos_grid(N), dim3(256), 0, P->stream, N, P->active.p, P->Dg.p, P->g.p, P->S.p, radius, o.min_lm_diagonal, o.max_lm_diagonal,
+                         P->D2.p, P->Mblk.p, P->Minv.p, P->b.p, P->r.p, P->z.p, P->p.p, P->q.p, P->y.p);
+  }
+  out->dense = solved;
+  if (!solved)
+    if (int st = pos_pcg(P, o, &out->cg, &out->stalled, &out->cg_rel)) return st;
+  // the step, its scale-gauge part removed, the trial point, and what the decision needs
+  hipLaunchKernelGGL(k_pos_step, pos_grid(N), dim3(256), 0, P->stream, N, P->active.p, P->S.p, P->y.p, P->x.p, fixed, o.remove_scale_gauge, P->delta.p, P->v.p);
+  pos_dot(P, P->delta.p, P->v.p, nullptr, PS_DV);
+  pos_dot(P, P->v.p, P->v.p, nullptr, PS_VV);
+  hipLaunchKernelGGL(k_pos_project, pos_grid(N), dim3(256), 0, P->stream, N, P->scal.p, PS_DV, PS_VV, P->v.p, P->delta.p, P->x.p, P->cand.p);
+  pos_dot(P, P->delta.p, P->delta.p, nullptr, PS_STEP2);
+  pos_dot(P, P->delta.p, P->g.p, nullptr, PS_DG);
+  hipLaunchKernelGGL(k_pos_matvec<false>, pos_row_grid(N), dim3(256), 0, P->stream, a, P->delta.p, P->delta.p, P->S.p, P->D2.p, P->Ap.p);
+  pos_dot(P, P->delta.p, P->Ap.p, nullptr, PS_DLD);
+  return 0;
+}
+
+int pos_lm_solve(gsfm_pos_problem* P, int32_t fixed, const gsfm_pos_options& o, gsfm_pos_summary* sum) {
+  const uint32_t N = P->n_cams;
   double radius = o.initial_trust_region_radius, decrease_factor = 2.0;
   int num_invalid = 0, iteration = 0;
   double x_cost = 0.0, x_norm = 0.0, gmax = 0.0;
@@ -208,7 +251,6 @@ int pos_lm_solve(gsfm_pos_problem* P, int32_t fixed, const gsfm_pos_options& o, 
   log(0, 0, 0, 0);
   if (!std::isfinite(x_cost)) return finish(GSFM_TERM_FAILURE);
   if (gmax <= o.gradient_tolerance) return finish(GSFM_TERM_GRADIENT_TOLERANCE);
-  const bool dense_ok = (int64_t)N <= (int64_t)o.dense_max_cams;
   bool last_successful = false;
   while (true) {
     if (iteration >= o.max_num_iterations) return finish(GSFM_TERM_NO_CONVERGENCE);
@@ -216,32 +258,14 @@ int pos_lm_solve(gsfm_pos_problem* P, int32_t fixed, const gsfm_pos_options& o, 
     if (radius <= o.min_trust_region_radius) return finish(GSFM_TERM_FAILURE);
     ++iteration;
     last_successful = false;
-    // LevenbergMarquardtStrategy::ComputeStep: (J^T J + D^2) y = J^T r in scaled coordinates, D = sqrt(clamp(diag) / radius), step = -y
-    hipLaunchKernelGGL(k_pos_prep, pos_grid(N), dim3(256), 0, P->stream, N, P->active.p, P->Dg.p, P->g.p, P->S.p, radius, o.min_lm_diagonal, o.max_lm_diagonal,
-                       P->D2.p, P->Mblk.p, P->Minv.p, P->b.p, P->r.p, P->z.p, P->p.p, P->q.p, P->y.p);
-    int cg = 0;
-    bool solved = false;
-    if (dense_ok) {
-      if (int st = pos_dense_step(P, &solved)) return st;
-      if (solved) sum->num_dense_solves++;
-      else hipLaunchKernelGGL(k_pos_prep, pos_grid(N), dim3(256), 0, P->stream, N, P->active.p, P->Dg.p, P->g.p, P->S.p, radius, o.min_lm_diagonal, o.max_lm_diagonal,
-                              P->D2.p, P->Mblk.p, P->Minv.p, P->b.p, P->r.p, P->z.p, P->p.p, P->q.p, P->y.p);
-    }
-    if (!solved) {
-      bool stalled = false;
-      if (int st = pos_pcg(P, o, &cg, &stalled)) return st;
+    PosStep step;
+    if (int st = pos_step(P, fixed, radius, o, &step, nullptr)) return st;
+    const int cg = step.cg;
+    if (step.dense) sum->num_dense_solves++;
+    else {
       sum->num_cg_iterations += cg;
-      if (stalled) sum->num_pcg_stalled_steps++;
+      if (step.stalled) sum->num_pcg_stalled_steps++;
     }
-    // the step, its scale-gauge part removed, the trial point, and what the decision needs
-    hipLaunchKernelGGL(k_pos_step, pos_grid(N), dim3(256), 0, P->stream, N, P->active.p, P->S.p, P->y.p, P->x.p, fixed, o.remove_scale_gauge, P->delta.p, P->v.p);
-    pos_dot(P, P->delta.p, P->v.p, nullptr, PS_DV);
-    pos_dot(P, P->v.p, P->v.p, nullptr, PS_VV);
-    hipLaunchKernelGGL(k_pos_project, pos_grid(N), dim3(256), 0, P->stream, N, P->scal.p, PS_DV, PS_VV, P->v.p, P->delta.p, P->x.p, P->cand.p);
-    pos_dot(P, P->delta.p, P->delta.p, nullptr, PS_STEP2);
-    pos_dot(P, P->delta.p, P->g.p, nullptr, PS_DG);
-    hipLaunchKernelGGL(k_pos_matvec<false>, pos_row_grid(N), dim3(256), 0, P->stream, a, P->delta.p, P->delta.p, P->S.p, P->D2.p, P->Ap.p);
-    pos_dot(P, P->delta.p, P->Ap.p, nullptr, PS_DLD);
     if (int st = read_scal("step")) return st;
     const double step2 = hs[PS_STEP2];
     bool valid = std::isfinite(step2) && std::isfinite(hs[PS_DG]) && std::isfinite(hs[PS_DLD]);
@@ -289,6 +313,24 @@ int pos_lm_solve(gsfm_pos_problem* P, int32_t fixed, const gsfm_pos_options& o, 
     sum->max_radius = std::fmax(sum->max_radius, radius);
     log(cost_change, step_norm, rel_dec, cg);
   }
+}
+
+// The active set (the present cameras, less fixed_cam when >= 0), x = pos, the cost and the linearisation at x: what a solve does before
+// its first step.  *cost: the cost of pos.
+int pos_setup_linearize(gsfm_pos_problem* P, const double* pos, int32_t fixed_cam, double* cost) {
+  std::vector<uint8_t> act(P->present);
+  if (fixed_cam >= 0) act[fixed_cam] = 0;
+  HIPCHK(hipMemcpyAsync(P->active.p, act.data(), act.size(), hipMemcpyHostToDevice, P->stream));
+  HIPCHK(hipMemcpyAsync(P->x.p, pos, 24 * (size_t)P->n_cams, hipMemcpyHostToDevice, P->stream));
+  double cb_cost = 0.0;
+  if (int st = pos_cost(P, P->x.p, &cb_cost)) return st;
+  if (int st = pos_linearize(P)) return st;
+  double c = cb_cost;
+  if (!P->cb) HIPCHK(hipMemcpyAsync(&c, P->scal.p + PS_COST, 8, hipMemcpyDeviceToHost, P->stream));
+  if (int st = pos_sync(P, "linearisation")) return st;
+  *cost = c;
+  P->have_lin = true;
+  return 0;
 }
 
 int pos_create_impl(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j, const double* rel_t, const double* rot_aa,
@@ -461,6 +503,77 @@ gsfm_status gsfm_pos_residuals(gsfm_pos_problem* P, const double* pos, double* r
   HIPCHK_S(hipMemcpyAsync(s.data(), d_s.p, 8 * E, hipMemcpyDeviceToHost, P->stream));
   if (int st = pos_sync(P, "residuals")) return (gsfm_status)st;
   if (rho_out && P->cb) for (size_t e = 0; e < E; ++e) { double t[3]; P->cb(P->cb_user, s[e], t); rho_out[e] = t[0]; }
+  return GSFM_OK;
+}
+
+gsfm_status gsfm_pos_linearize(gsfm_pos_problem* P, const double* pos, double* gradient, double* diag_blocks, double* cost) {
+  if (!P || !pos) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
+  PosDevice g(P->device);
+  const size_t N = P->n_cams;
+  double c = 0.0;
+  if (int st = pos_setup_linearize(P, pos, -1, &c)) return (gsfm_status)st;
+  std::vector<double> g3(3 * N), d6(6 * N);
+  HIPCHK_S(hipMemcpyAsync(g3.data(), P->g.p, 24 * N, hipMemcpyDeviceToHost, P->stream));
+  HIPCHK_S(hipMemcpyAsync(d6.data(), P->Dg.p, 48 * N, hipMemcpyDeviceToHost, P->stream));
+  if (int st = pos_sync(P, "linearize outputs")) return (gsfm_status)st;
+  if (gradient) std::copy(g3.begin(), g3.end(), gradient);
+  if (diag_blocks)
+    for (size_t k = 0; k < N; ++k) {
+      const double* m = &d6[6 * k];
+      const double full[9] = {m[0], m[1], m[2], m[1], m[3], m[4], m[2], m[4], m[5]};
+      std::copy(full, full + 9, diag_blocks + 9 * k);
+    }
+  if (cost) *cost = c;
+  return GSFM_OK;
+}
+
+gsfm_status gsfm_pos_normal_matvec(gsfm_pos_problem* P, const double* v, double* y) {
+  if (!P || !v || !y) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
+  if (!P->have_lin) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "call gsfm_pos_linearize or gsfm_pos_step_check first");
+  PosDevice g(P->device);
+  const size_t N = P->n_cams;
+  HIPCHK_S(hipMemcpyAsync(P->q.p, v, 24 * N, hipMemcpyHostToDevice, P->stream));
+  hipLaunchKernelGGL(k_pos_matvec<false>, pos_row_grid(P->n_cams), dim3(256), 0, P->stream, pos_dev(P), P->q.p, P->q.p, P->S.p, P->D2.p, P->Ap.p);
+  HIPCHK_S(hipMemcpyAsync(y, P->Ap.p, 24 * N, hipMemcpyDeviceToHost, P->stream));
+  if (int st = pos_sync(P, "normal_matvec")) return (gsfm_status)st;
+  return GSFM_OK;
+}
+
+gsfm_status gsfm_pos_step_check(gsfm_pos_problem* P, const double* pos, int32_t fixed_cam, double radius, const gsfm_pos_options* opt, double* K_out,
+                                double* b_out, double* y_out, double* delta_out, double* scal_out, int32_t* info_out) {
+  if (!P || !pos) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
+  if (fixed_cam < -1 || fixed_cam >= (int64_t)P->n_cams || (fixed_cam >= 0 && !P->present[fixed_cam]))
+    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "fixed_cam must be -1 or a camera that appears in an edge");
+  if (!(radius > 0.0)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "radius must be positive");
+  PosDevice g(P->device);
+  gsfm_pos_options o;
+  if (opt) o = *opt; else gsfm_pos_options_default(&o);
+  const uint32_t N = P->n_cams, n = 3 * N;
+  double cost = 0.0;
+  if (int st = pos_setup_linearize(P, pos, fixed_cam, &cost)) return (gsfm_status)st;
+  hipLaunchKernelGGL(k_pos_scale, pos_grid(N), dim3(256), 0, P->stream, N, P->Dg.p, P->S.p, o.jacobi_scaling);
+  PosStep step;
+  std::vector<double> tiles;
+  if (int st = pos_step(P, fixed_cam, radius, o, &step, K_out ? &tiles : nullptr)) return (gsfm_status)st;
+  double hs[PS_N];
+  HIPCHK_S(hipMemcpyAsync(hs, P->scal.p, sizeof(hs), hipMemcpyDeviceToHost, P->stream));
+  if (b_out) HIPCHK_S(hipMemcpyAsync(b_out, P->b.p, 8 * (size_t)n, hipMemcpyDeviceToHost, P->stream));
+  if (y_out) HIPCHK_S(hipMemcpyAsync(y_out, P->y.p, 8 * (size_t)n, hipMemcpyDeviceToHost, P->stream));
+  if (delta_out) HIPCHK_S(hipMemcpyAsync(delta_out, P->delta.p, 8 * (size_t)n, hipMemcpyDeviceToHost, P->stream));
+  if (int st = pos_sync(P, "step check")) return (gsfm_status)st;
+  if (K_out && !tiles.empty()) {
+    for (uint32_t r = 0; r < n; ++r)
+      for (uint32_t c = 0; c <= r; ++c) {
+        const double v = tiles[chol_tile_off(r / GSFM_CB, c / GSFM_CB) + (r % GSFM_CB) * GSFM_CB + c % GSFM_CB];
+        K_out[(size_t)r * n + c] = v;
+        K_out[(size_t)c * n + r] = v;
+      }
+  }
+  if (scal_out) {
+    scal_out[0] = -hs[PS_DG] - 0.5 * hs[PS_DLD];   // the solve's model cost change
+    scal_out[1] = hs[PS_DG]; scal_out[2] = hs[PS_DLD]; scal_out[3] = step.cg_rel;
+  }
+  if (info_out) { info_out[0] = step.dense ? 0 : 1; info_out[1] = step.info; info_out[2] = step.cg; }
   return GSFM_OK;
 }
 

@@ -405,5 +405,26 @@ class PositionProblem(ProblemBase):
         self._check(st, "residuals")
         return r, rho
 
+    # linearize(pos) and normal_matvec(v) are ProblemBase's: gsfm_pos_linearize / gsfm_pos_normal_matvec share gsfm_rot_'s argument lists
+
+    def step_check(self, pos, fixed_cam=0, radius=1e4, want_K=True, **options):
+        """gsfm_pos_step_check: one LM step's linear algebra at pos (iteration 1 of a solve from pos, at `radius`).  Returns a dict:
+        K (3N x 3N, when the dense path assembled it, else None), b, y, delta (N x 3), model_cost_change, dg, dld, cg_rel, path (0 dense, 1 PCG),
+        chol_info, cg_iterations."""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(self.n_cams, 3)
+        o = self._options(options)
+        n = 3 * self.n_cams
+        K = np.full((n, n), np.nan) if want_K else None
+        b, y, delta = np.empty((self.n_cams, 3)), np.empty((self.n_cams, 3)), np.empty((self.n_cams, 3))
+        scal = np.empty(4)
+        info = np.zeros(3, dtype=np.int32)
+        st = self._lib.gsfm_pos_step_check(self._h, _dp(pos), int(fixed_cam), float(radius), C.byref(o), None if K is None else _dp(K),
+                                           _dp(b), _dp(y), _dp(delta), _dp(scal), info.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._reraise_callback_error()
+        self._check(st, "step_check")
+        return {"K": K if info[1] >= 0 else None, "b": b, "y": y, "delta": delta,
+                "model_cost_change": scal[0], "dg": scal[1], "dld": scal[2], "cg_rel": scal[3], "path": int(info[0]),
+                "chol_info": int(info[1]), "cg_iterations": int(info[2])}
+
     def set_edge_weights(self, w):
         raise NotImplementedError("position residuals have weight 1 (the reference's BASELINE error)")

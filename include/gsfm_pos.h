@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GSFM_POS_ABI_VERSION 1
+#define GSFM_POS_ABI_VERSION 2
 
 typedef struct gsfm_pos_problem gsfm_pos_problem;
 
@@ -90,6 +90,27 @@ gsfm_status gsfm_pos_set_loss_callback(gsfm_pos_problem* p, gsfm_loss_callback f
 gsfm_status gsfm_pos_solve(gsfm_pos_problem* p, double* pos_inout, int32_t fixed_cam, const gsfm_pos_options* options, gsfm_pos_summary* summary);
 /* residuals at pos: r_out n_edges x 3, rho_out n_edges (rho(|r|^2) of the loss; either may be NULL) */
 gsfm_status gsfm_pos_residuals(gsfm_pos_problem* p, const double* pos, double* r_out, double* rho_out);
+/* Checks of the solve's own code (the tests compare them with a high-precision reference).
+ *
+ * gsfm_pos_linearize: the cost and the linearisation at pos with every present camera active, as a solve evaluates them (callback loss
+ * included): gradient g = J~^T r~ (n_cams x 3), the diagonal blocks D_k = sum_e H_e of J~^T J~ (n_cams x 9, row-major) and the cost
+ * (each may be NULL).  The per-entry blocks H_e stay on the device for gsfm_pos_normal_matvec.
+ * A NaN gradient entry is not counted in a solve's final_gradient_max_norm (fmax drops it, as the oracle's std::fmax does).          */
+gsfm_status gsfm_pos_linearize(gsfm_pos_problem* p, const double* pos, double* gradient, double* diag_blocks, double* cost);
+/* y = L v with L = J~^T J~ of the last gsfm_pos_linearize or gsfm_pos_step_check: y_k = sum_e H_e (v_k - v_m) on the active rows of that
+ * call and 0 on inactive rows.  v is used as given, on inactive cameras too (a neighbour's v_m enters y_k whether or not m is active). */
+gsfm_status gsfm_pos_normal_matvec(gsfm_pos_problem* p, const double* v, double* y);
+/* One LM step's linear algebra at pos, exactly as iteration 1 of gsfm_pos_solve(pos, fixed_cam, o) computes it but at the given radius
+ * (the same code): the linearisation, the Jacobi scale S of pos, D^2 = clamp(S^2 diag(L), min_lm_diagonal, max_lm_diagonal) / radius,
+ * the damped system K y = b with K = S L S + D^2 and b = S g (the identity and 0 on inactive rows), solved by the dense Cholesky (up to
+ * o->dense_max_cams cameras) or PCG, the step delta = -S y with its scale-gauge part removed, and the model cost change.  No accept or
+ * reject decision; the solve's state is not an input.  o may be NULL (defaults).  Outputs (each may be NULL):
+ *   K_out      (3 n_cams)^2 row-major, full symmetric: K as assembled for the dense Cholesky (written only when the dense path assembled it)
+ *   b_out, y_out, delta_out   3 n_cams each
+ *   scal_out[4]   model cost change -delta.g - delta^T L delta / 2, delta.g, delta^T L delta, PCG's final sqrt(rz / rz0) (0 on the dense path)
+ *   info_out[3]   path (0 dense, 1 PCG), the Cholesky's info (-1: not run, > 0: a non-positive pivot, then PCG), PCG iterations       */
+gsfm_status gsfm_pos_step_check(gsfm_pos_problem* p, const double* pos, int32_t fixed_cam, double radius, const gsfm_pos_options* o, double* K_out,
+                                double* b_out, double* y_out, double* delta_out, double* scal_out, int32_t* info_out);
 void gsfm_pos_problem_destroy(gsfm_pos_problem* p);
 
 #ifdef __cplusplus
