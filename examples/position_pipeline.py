@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The reference's scripts/sfm_pipeline.py 1DSfM branch through step 7: rotations, FilterRotations(), then camera positions
+"""The reference's scripts/sfm_pipeline.py 1DSfM branch through step 7: rotations, FilterRotations(), FilterRelativeTranslation() (the
+1DSfM filter of relative translations; OptimizePairwiseTranslations before it is not built), then camera positions
 (EstimatePosition(HuberLoss(0.1), PositionErrorType.BASELINE) there; NonlinearPositionEstimator.EstimatePositions here) and the PLY
 with the estimated camera positions.
 usage: position_pipeline.py <dataset_dir with EGs.txt, cc.txt> [flags.yaml]"""
@@ -24,6 +25,7 @@ def position_pipeline(dataset_dir, flagfile=None):
     solver.FilterInitialViewGraphAndCalibrateCameras(graph, scene)
     assert solver.EstimateGlobalRotations(HuberLoss(0.1)), solver.LastError()
     solver.FilterRotations()
+    solver.FilterRelativeTranslation()
     positions = sfm.MapViewIdVector3d()
     estimator = sfm.NonlinearPositionEstimator()
     assert estimator.EstimatePositions(graph.GetAllEdges(), solver.orientations, positions, HuberLoss(0.1),

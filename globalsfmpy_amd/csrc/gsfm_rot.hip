@@ -11,6 +11,7 @@
 #include "problem_create.hpp"
 #include "spanning_tree.hpp"
 #include "solver_pos.hpp"
+#include "trans_filter.hpp"
 
 // =============================================================================================
 extern "C" {
@@ -382,6 +383,19 @@ gsfm_status gsfm_rot_init_spanning_tree(uint32_t n_cams, uint64_t n_edges, const
     return init_spanning_tree_impl(n_cams, n_edges, edge_i, edge_j, rel_aa, weight, rot_aa_out, parent_edge_out, root_out, n_tree_cams_out, depth_out, kernel_ms);
   } catch (const std::exception& e) {
     return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("spanning-tree initialisation ran out of host resources: ") + e.what());
+  }
+}
+
+gsfm_status gsfm_pos_filter_relative_translations(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j, const double* rel_t,
+                                                  const double* rot_aa, int32_t n_axes, const double* axes, uint64_t seed, double tolerance,
+                                                  double* bad_weight_out, uint8_t* keep_out, uint64_t* n_kept, double* stats_out, double* axes_out,
+                                                  double* proj_out, uint32_t* num_passes_out, uint32_t* num_picks_out, double* kernel_ms) {
+  // (host vectors of O(E) and host threads: an exception must not cross the C boundary)
+  try {
+    return trans_filter_impl(n_cams, n_edges, edge_i, edge_j, rel_t, rot_aa, n_axes, axes, seed, tolerance, bad_weight_out, keep_out, n_kept, stats_out,
+                             axes_out, proj_out, num_passes_out, num_picks_out, kernel_ms);
+  } catch (const std::exception& e) {
+    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the translation filter ran out of host resources: ") + e.what());
   }
 }
 

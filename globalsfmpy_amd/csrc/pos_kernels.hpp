@@ -335,14 +335,9 @@ __global__ void __launch_bounds__(256) k_pos_dense_assemble(PosDev a, const doub
   }
 }
 
-// world directions of the edges on the device: d_e = R(aa_i)^T t_ij with R = Ceres' AngleAxisToRotationMatrix (small-angle branch
-// included), written for the edge and, with their signs, for its two directed entries
-__global__ void k_pos_directions(uint32_t n_edges, const uint32_t* __restrict__ ei, const double* __restrict__ rot_aa, const double* __restrict__ rel_t,
-                                 const uint32_t* __restrict__ pos_i, const uint32_t* __restrict__ pos_j, double* __restrict__ dir_e, double* __restrict__ dir_k) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n_edges) return;
-  const double* w = rot_aa + 3 * (size_t)ei[e];
-  const double* t = rel_t + 3 * e;
+// d = R(aa)^T t with R = Ceres' AngleAxisToRotationMatrix (small-angle branch included): an edge's world direction from position_2 and
+// the orientation of its first camera.  One routine for the position problem and for the translation filter (trans_filter_kernels.hpp).
+__device__ __forceinline__ void pos_world_direction(const double* __restrict__ w, const double* __restrict__ t, double* d) {
   double R[9];
   const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
   if (th2 > DBL_EPSILON) {
@@ -356,8 +351,16 @@ __global__ void k_pos_directions(uint32_t n_edges, const uint32_t* __restrict__ 
     R[2] = w[1]; R[5] = -w[0]; R[8] = 1.0;
   }
   // (R is row-major here: R[3 r + c]); d = R^T t
-  double d[3];
   for (int c = 0; c < 3; ++c) d[c] = R[c] * t[0] + R[3 + c] * t[1] + R[6 + c] * t[2];
+}
+
+// world directions of the edges on the device, written for the edge and, with their signs, for its two directed entries
+__global__ void k_pos_directions(uint32_t n_edges, const uint32_t* __restrict__ ei, const double* __restrict__ rot_aa, const double* __restrict__ rel_t,
+                                 const uint32_t* __restrict__ pos_i, const uint32_t* __restrict__ pos_j, double* __restrict__ dir_e, double* __restrict__ dir_k) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_edges) return;
+  double d[3];
+  pos_world_direction(rot_aa + 3 * (size_t)ei[e], rel_t + 3 * e, d);
   for (int c = 0; c < 3; ++c) { dir_e[3 * e + c] = d[c]; dir_k[3 * (size_t)pos_i[e] + c] = d[c]; dir_k[3 * (size_t)pos_j[e] + c] = -d[c]; }
 }
 

@@ -108,6 +108,9 @@ struct ReconstructionEstimatorOptions {
   int num_threads = 1;                                       // reconstruction_estimator_options.h:99
   int min_num_two_view_inliers = 30;                         // :107
   double rotation_filtering_max_difference_degrees = 5.0;    // :122
+  bool filter_relative_translations_with_1dsfm = true;       // :143
+  int translation_filtering_num_iterations = 48;             // :146
+  double translation_filtering_projection_tolerance = 0.1;   // :149
 };
 struct ReconstructionBuilderOptions {
   int num_threads = 1;
@@ -206,6 +209,18 @@ class GlobalReconstructionEstimator {
     FilterViewPairsFromOrientation(orientations_, options_.rotation_filtering_max_difference_degrees, view_graph_);
     for (ViewId v : RemoveDisconnectedViewPairs(view_graph_)) orientations_.erase(v);
   }
+  void FilterRelativeTranslation() {  // :537-563 (extract_maximal_rigid_subgraph, off by default, is not built)
+    if (!view_graph_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
+    if (options_.filter_relative_translations_with_1dsfm) {
+      FilterViewPairsFromRelativeTranslationOptions o;
+      o.num_threads = options_.num_threads;
+      o.num_iterations = options_.translation_filtering_num_iterations;
+      o.translation_projection_tolerance = options_.translation_filtering_projection_tolerance;
+      o.seed = 1;   // translation_filter_options_.rng->Seed(1) (:551)
+      FilterViewPairsFromRelativeTranslation(o, orientations_, view_graph_);
+    }
+    for (ViewId v : RemoveDisconnectedViewPairs(view_graph_)) orientations_.erase(v);
+  }
   ReconstructionEstimatorOptions options_;
   ViewGraph* view_graph_ = nullptr;
   Reconstruction* reconstruction_ = nullptr;
@@ -235,6 +250,7 @@ void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions
   options.reconstruction_estimator_options.num_threads = options.num_threads;
   get("min_num_inliers_for_valid_match", options.reconstruction_estimator_options.min_num_two_view_inliers);
   get("post_rotation_filtering_degrees", options.reconstruction_estimator_options.rotation_filtering_max_difference_degrees);
+  get("filter_relative_translations_with_1dsfm", options.reconstruction_estimator_options.filter_relative_translations_with_1dsfm);
 }
 
 }  // namespace
@@ -313,7 +329,10 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def(py::init<>())
       .def_readwrite("num_threads", &ReconstructionEstimatorOptions::num_threads)
       .def_readwrite("min_num_two_view_inliers", &ReconstructionEstimatorOptions::min_num_two_view_inliers)
-      .def_readwrite("rotation_filtering_max_difference_degrees", &ReconstructionEstimatorOptions::rotation_filtering_max_difference_degrees);
+      .def_readwrite("rotation_filtering_max_difference_degrees", &ReconstructionEstimatorOptions::rotation_filtering_max_difference_degrees)
+      .def_readwrite("filter_relative_translations_with_1dsfm", &ReconstructionEstimatorOptions::filter_relative_translations_with_1dsfm)
+      .def_readwrite("translation_filtering_num_iterations", &ReconstructionEstimatorOptions::translation_filtering_num_iterations)
+      .def_readwrite("translation_filtering_projection_tolerance", &ReconstructionEstimatorOptions::translation_filtering_projection_tolerance);
   py::class_<ReconstructionBuilderOptions>(m, "ReconstructionBuilderOptions")
       .def(py::init<>())
       .def_readwrite("num_threads", &ReconstructionBuilderOptions::num_threads)
@@ -386,6 +405,7 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def("EstimateGlobalRotationsWithSigmaConsensus", &GlobalReconstructionEstimator::EstimateGlobalRotationsSigmaConsensus,
            py::call_guard<py::gil_scoped_release>())
       .def("FilterRotations", &GlobalReconstructionEstimator::FilterRotations)
+      .def("FilterRelativeTranslation", &GlobalReconstructionEstimator::FilterRelativeTranslation, py::call_guard<py::gil_scoped_release>())
       .def("LastSummary", [](const GlobalReconstructionEstimator& e) { return summary_dict(e.summary_); })
       .def("LastError", [](const GlobalReconstructionEstimator& e) { return e.error_; });
 
@@ -456,6 +476,13 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
   m.def("OrientationsFromMaximumSpanningTree", [](const ViewGraph& vg, OrientationMap* o) { return OrientationsFromMaximumSpanningTree(vg, o); });
   m.def("OrientationsFromMaximumSpanningTreeOnDevice", [](const ViewGraph& vg, OrientationMap* o) { return OrientationsFromMaximumSpanningTreeOnDevice(vg, o); });
   m.def("FilterViewPairsFromOrientation", &FilterViewPairsFromOrientation);
+  py::class_<FilterViewPairsFromRelativeTranslationOptions>(m, "FilterViewPairsFromRelativeTranslationOptions")
+      .def(py::init<>())
+      .def_readwrite("num_threads", &FilterViewPairsFromRelativeTranslationOptions::num_threads)
+      .def_readwrite("num_iterations", &FilterViewPairsFromRelativeTranslationOptions::num_iterations)
+      .def_readwrite("translation_projection_tolerance", &FilterViewPairsFromRelativeTranslationOptions::translation_projection_tolerance)
+      .def_readwrite("seed", &FilterViewPairsFromRelativeTranslationOptions::seed);
+  m.def("FilterViewPairsFromRelativeTranslation", &FilterViewPairsFromRelativeTranslation, py::call_guard<py::gil_scoped_release>());
   // bind :658, src/compare_reconstructions.cpp:617-647: (view_graph, reconstruction_to_eval, covariances, residuals) -- fills `residuals`
   m.def("residuals_of_relative_rot", [](const ViewGraph& vg, const Reconstruction& rec, const CovarianceMap& cov, std::vector<double>& residuals) {
     gsfm::ResidualsOfRelativeRotations(vg, rec.orientation, cov, &residuals);

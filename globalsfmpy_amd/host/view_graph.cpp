@@ -1,6 +1,7 @@
 // Host-side callers / data formats around the rotation path (SURVEY section 8f "next" rows).
 #include "../../include/gsfm/view_graph.hpp"
 #include "../../include/gsfm_rot.h"
+#include "../../include/gsfm_pos.h"
 
 #include <algorithm>
 #include <cinttypes>
@@ -253,6 +254,36 @@ void FilterViewPairsFromOrientation(const std::unordered_map<ViewId, Eigen::Vect
     for (size_t e = 0; e < f.keys.size(); ++e) if (!keep[e]) bad.push_back(f.keys[e]);
   }
   for (const auto& k : bad) view_graph->RemoveEdge(k.first, k.second);
+}
+
+void FilterViewPairsFromRelativeTranslation(const FilterViewPairsFromRelativeTranslationOptions& options,
+                                            const std::unordered_map<ViewId, Eigen::Vector3d>& orientations, ViewGraph* view_graph) {
+  std::vector<ViewId> ids;
+  for (ViewId v : view_graph->ViewIds()) ids.push_back(v);
+  std::sort(ids.begin(), ids.end());
+  auto rank = [&ids](ViewId v) { return (uint32_t)(std::lower_bound(ids.begin(), ids.end(), v) - ids.begin()); };
+  std::vector<ViewIdPair> all, keys;
+  for (const auto& e : view_graph->GetAllEdges()) all.push_back(e.first);
+  std::sort(all.begin(), all.end());
+  std::vector<uint32_t> ei, ej;
+  std::vector<double> rel, rot(3 * ids.size(), 0.0);
+  for (const ViewIdPair& k : all) {
+    auto o = orientations.find(k.first);
+    if (o == orientations.end()) continue;   // no world direction for this pair: it stays
+    const uint32_t i = rank(k.first);
+    for (int c = 0; c < 3; ++c) rot[3 * (size_t)i + c] = o->second[c];
+    const Eigen::Vector3d& t = view_graph->GetEdge(k.first, k.second)->position_2;
+    keys.push_back(k); ei.push_back(i); ej.push_back(rank(k.second));
+    rel.push_back(t[0]); rel.push_back(t[1]); rel.push_back(t[2]);
+  }
+  if (keys.empty()) return;
+  std::vector<double> bad(keys.size());
+  std::vector<uint8_t> keep(keys.size());
+  const gsfm_status st = gsfm_pos_filter_relative_translations((uint32_t)ids.size(), keys.size(), ei.data(), ej.data(), rel.data(), rot.data(),
+                                                               options.num_iterations, nullptr, options.seed, options.translation_projection_tolerance,
+                                                               bad.data(), keep.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (st != GSFM_OK) throw std::runtime_error(std::string("FilterViewPairsFromRelativeTranslation: ") + gsfm_last_error());
+  for (size_t e = 0; e < keys.size(); ++e) if (!keep[e]) view_graph->RemoveEdge(keys[e].first, keys[e].second);
 }
 
 std::unordered_set<ViewId> RemoveDisconnectedViewPairs(ViewGraph* view_graph) {

@@ -355,6 +355,42 @@ def orientations_from_maximum_spanning_tree(n_cams, edge_i, edge_j, rel_aa, weig
             "kernel_ms": ms.value}
 
 
+def filter_relative_translations(n_cams, edge_i, edge_j, rel_t, rot_aa, num_iterations=48, tolerance=0.1, seed=1, axes=None,
+                                 want_projections=False):
+    """gsfm_pos_filter_relative_translations: the 1DSfM filter of relative translations (Theia's FilterViewPairsFromRelativeTranslation
+    under the reproducible definition of include/gsfm_pos.h) on the device.  rel_t: E x 3 position_2 of each view pair; rot_aa: N x 3
+    orientations; axes: num_iterations x 3 projection axes, None = drawn by the library from `seed` (not the reference's axes).
+    Returns (keep mask, dict(bad_weight, n_kept, mean, variance, axes, projections (E x num_iterations, or None), num_passes, num_picks
+    (per projection), kernel_ms))."""
+    lib = _abi.load_library()
+    n, K = int(n_cams), int(num_iterations)
+    ei = np.ascontiguousarray(edge_i, dtype=np.uint32).reshape(-1)
+    ej = np.ascontiguousarray(edge_j, dtype=np.uint32).reshape(-1)
+    rel = np.ascontiguousarray(rel_t, dtype=np.float64).reshape(-1, 3)
+    rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(n, 3)
+    E = ei.shape[0]
+    if ej.shape[0] != E or rel.shape[0] != E:
+        raise ValueError("edge_i, edge_j and rel_t must describe the same edges")
+    ax = None
+    if axes is not None:
+        ax = np.ascontiguousarray(axes, dtype=np.float64).reshape(-1, 3)
+        if ax.shape[0] != K:
+            raise ValueError("axes must hold num_iterations rows")
+    Kc = max(K, 0)
+    bad, keep = np.empty(E), np.empty(E, dtype=np.uint8)
+    stats, axes_out = np.empty(6), np.empty((Kc, 3))
+    proj = np.empty((E, Kc)) if want_projections else None
+    passes, picks = np.zeros(Kc, dtype=np.uint32), np.zeros(Kc, dtype=np.uint32)
+    kept, ms = C.c_uint64(0), C.c_double(0)
+    st = lib.gsfm_pos_filter_relative_translations(n, E, _u32p(ei), _u32p(ej), _dp(rel), _dp(rot), K, _dp(ax), int(seed), float(tolerance),
+                                                   _dp(bad), keep.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(kept), _dp(stats), _dp(axes_out),
+                                                   _dp(proj), _u32p(passes), _u32p(picks), C.byref(ms))
+    if st != 0:
+        raise SolverError("gsfm_pos_filter_relative_translations failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+    return keep.astype(bool), {"bad_weight": bad, "n_kept": int(kept.value), "mean": stats[:3].copy(), "variance": stats[3:].copy(), "axes": axes_out,
+                               "projections": proj, "num_passes": passes, "num_picks": picks, "kernel_ms": ms.value}
+
+
 class PositionProblem(ProblemBase):
     """Camera positions from relative translations (include/gsfm_pos.h): the reference's EstimatePositions with BASELINE residuals
     r = (c_j - c_i) / |c_j - c_i| - R(aa_i)^T t_ij on the device.  rel_t: E x 3 position_2 of each view pair (frame of camera i);

@@ -2,6 +2,7 @@
 // host-side C++: a minimal theia::ViewGraph, the maximum-spanning-tree initialisation, the 1DSfM
 // EGs.txt / covariance_rot.txt codecs, the post-rotation edge filter and the evaluation metrics.
 #pragma once
+#include <cstdint>
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
@@ -72,6 +73,20 @@ bool OrientationsFromMaximumSpanningTreeOnDevice(const ViewGraph& view_graph, st
 // std::runtime_error when no device is usable (there is no CPU fallback).
 void FilterViewPairsFromOrientation(const std::unordered_map<ViewId, Eigen::Vector3d>& orientations,
                                     double max_relative_rotation_difference_degrees, ViewGraph* view_graph);
+// thirdparty/TheiaSfM/src/theia/sfm/filter_view_pairs_from_relative_translation.h: the 1DSfM filter of relative translations.
+struct FilterViewPairsFromRelativeTranslationOptions {
+  int num_threads = 1;                              // accepted and ignored: the projections run side by side on the device
+  int num_iterations = 48;                          // number of random projection axes
+  double translation_projection_tolerance = 0.08;   // an edge goes when its summed bad weight exceeds this times num_iterations
+  uint64_t seed = 1;                                // in place of the reference's rng pointer: seeds the library's own axis generator
+};
+// filter_view_pairs_from_relative_translation.cc:256-308 on the device (gsfm_pos_filter_relative_translations, under the reproducible
+// definition of include/gsfm_pos.h: the library's own axes, integer arc weights, the smallest index among equal scores).  The edges are
+// flattened in sorted ViewIdPair order with dense index = rank of the ViewId among the graph's views.  An edge whose first view has no
+// orientation is skipped and kept (the reference aborts in FindOrDie).  Throws std::runtime_error when no device is usable (there is no
+// CPU fallback) or the device call fails.
+void FilterViewPairsFromRelativeTranslation(const FilterViewPairsFromRelativeTranslationOptions& options,
+                                            const std::unordered_map<ViewId, Eigen::Vector3d>& orientations, ViewGraph* view_graph);
 // thirdparty/TheiaSfM/src/theia/sfm/view_graph/remove_disconnected_view_pairs.cc: keeps the largest component.
 std::unordered_set<ViewId> RemoveDisconnectedViewPairs(ViewGraph* view_graph);
 

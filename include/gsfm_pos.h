@@ -113,6 +113,41 @@ gsfm_status gsfm_pos_step_check(gsfm_pos_problem* p, const double* pos, int32_t 
                                 double* b_out, double* y_out, double* delta_out, double* scal_out, int32_t* info_out);
 void gsfm_pos_problem_destroy(gsfm_pos_problem* p);
 
+
+/* The 1DSfM outlier filter of relative translations (Wilson and Snavely), Theia's FilterViewPairsFromRelativeTranslation
+ * (filter_view_pairs_from_relative_translation.cc), on flat arrays and on the device.  The reference's result depends on the iteration
+ * order of its hash maps and on libstdc++'s normal_distribution; this entry keeps every rule of the reference that decides something
+ * and fixes what the reference leaves to chance, so that two calls return the same bytes:
+ *   1. world directions  d_e = R(aa_i)^T t_e (t_e = position_2, used as given, not normalised; the position problem's routine).
+ *   2. mean = sum d_e / E, var = sum (d_e - mean)^2 / (E - 1) per component (0 for E = 1), reduced in a fixed order.
+ *   3. axes == NULL: axis_k = normalise(mean + var o z_k), z_k standard normal.  The reference hands the VARIANCE to a parameter named
+ *      std_dev; that is kept.  The normals come from the library's own generator (splitmix64 + Box-Muller, host code) seeded with
+ *      `seed` (the reference's pipeline seeds with 1): these are NOT the reference's axes.  axes != NULL: n_axes x 3, used as given.
+ *   4. projections  p_ek = d_e . axis_k  = fma(d2, a2, fma(d1, a1, d0 a0)).
+ *   5. under projection k edge e is the arc i -> j if p_ek > 0, else j -> i (p == 0: a reversed arc of weight 0), with the INTEGER
+ *      weight q_ek = floor(|p_ek| 2^32 + 0.5).  Integer weights are the one deliberate departure in the arithmetic: their sums are exact,
+ *      so a camera's in- and out-weight do not depend on the order in which its neighbours are removed.  Input whose per-camera sums
+ *      could reach 2^62 is rejected (with |t| <= 1 and unit axes: a camera of about 2^30 edges).
+ *   6. ordering.  Nodes: the cameras that appear in an edge.  Per live node qin, qout (sums over arcs from / to live nodes) and indeg
+ *      (live incoming arcs, zero-weight arcs included).  Until no node is live: if any live node has indeg == 0, ALL such nodes are
+ *      removed (they are pairwise non-adjacent, and removing one never stops another from being a source, so every order of removing
+ *      them leaves each edge on the same side -- the reference removes them one at a time in hash order); otherwise the one live node
+ *      with the largest score double(qout + 2^32) / double(qin + 2^32) (the reference's (out + 1) / (in + 1)) is removed, the smallest
+ *      camera index among equal scores (the reference: whichever its hash map meets first).  A removed node gets the number of its pass.
+ *   7. edge e is inconsistent under projection k when its arc's tail was removed in a later pass than its head;
+ *      bad_e = sum_k [inconsistent] |p_ek| in fp64, k ascending.
+ *   8. keep_e = !(bad_e > tolerance * n_axes).
+ * rot_aa is read for the first camera of every edge only.  A repeated pair is a parallel arc.  Outputs: bad_weight_out, keep_out (n_edges
+ * each, required), n_kept; optional (NULL: not returned) stats_out[6] (mean, var), axes_out (n_axes x 3: the axes used), proj_out
+ * (n_edges x n_axes, row per edge; computed only on request -- the ordering recomputes projections from the directions and never stores
+ * them), num_passes_out / num_picks_out (n_axes each: passes of step 6 and how many of them picked by score), kernel_ms (device time of
+ * all kernels).  Device memory O(n_edges + n_axes n_cams).  Arguments are checked on the host before any device call
+ * (GSFM_ERR_INVALID_ARG); without a device GSFM_ERR_NO_DEVICE: there is no host fallback.  No edges: GSFM_OK, n_kept = 0. */
+gsfm_status gsfm_pos_filter_relative_translations(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j, const double* rel_t,
+                                                  const double* rot_aa, int32_t n_axes, const double* axes, uint64_t seed, double tolerance,
+                                                  double* bad_weight_out, uint8_t* keep_out, uint64_t* n_kept, double* stats_out, double* axes_out,
+                                                  double* proj_out, uint32_t* num_passes_out, uint32_t* num_picks_out, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
