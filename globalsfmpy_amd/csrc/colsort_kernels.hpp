@@ -19,7 +19,10 @@
 //   measured at C5: prototype on random data (tools/bench_matvec6.hip) row-major 322 us -> 193 + 3 us; in the product 296 -> 182-201 us
 //   (profiles/r03_k3c_tuning.txt has every step in between).
 #pragma once
-#include "kernels.hpp"
+#include "edge_math.hpp"
+#include "lin_kernels.hpp"
+#include "pcg_kernels.hpp"
+#include "dense_assemble_kernels.hpp"
 
 namespace gsfm {
 
@@ -399,7 +402,7 @@ __device__ __forceinline__ void lin_col_body(const ColLinArgs& a) {
       const uint32_t d = sc * SUB + k * T + t;
       const uint32_t cr = mt[k].x, pm = col_slot(mt[k].y);
       double g3[3] = {0, 0, 0}, G6[6] = {0, 0, 0, 0, 0, 0}, B6[6] = {0, 0, 0, 0, 0, 0};
-      if constexpr (BODY) {   // body-frame evaluation (kernels.hpp, lin_entry_body_aa): the slots carry (gb, B), the finishing kernel rotates the row sums
+      if constexpr (BODY) {   // body-frame evaluation (lin_kernels.hpp, lin_entry_body_aa): the slots carry (gb, B), the finishing kernel rotates the row sums
         if (cr != GSFM_COL_PAD) {
           const uint32_t rl = col_rowl(mt[k].y);
           const double2 k0 = qrow[0][rl], k1 = qrow[1][rl];

@@ -1,6 +1,7 @@
 // Kernels of the per-component exact step of a disconnected view graph (host side: solver_components.hpp).
 #pragma once
-#include "kernels.hpp"
+#include "edge_math.hpp"
+#include "dense_assemble_kernels.hpp"
 #include "dense_kernels.hpp"
 #include "comp_rest.hpp"
 
@@ -17,7 +18,7 @@ struct CompMap {
   uint32_t row_base;      // camera of row 0 (a rank of a packed sharded problem holds the rows of its own cameras only)
 };
 // Which factorised components have anything to solve in this LM step: component c is skipped when sum_{k in c} b_k . Minv_k b_k <= floor^2 / B,
-// i.e. when block-Jacobi's estimate of every one of its cameras' steps is below the absolute floor of the step (kernels.hpp, k_cam_bound) -- a
+// i.e. when block-Jacobi's estimate of every one of its cameras' steps is below the absolute floor of the step (cam_kernels.hpp, k_cam_bound) -- a
 // scene that converged dozens of LM iterations ago while the batch iterates on.  One workgroup per component over its cameras in a fixed
 // order: the same decision on every run.  (Its A tiles are then neither assembled nor factorised, its step is zero.)
 // Under a SMOOTH loss a component is moreover put to rest for the remainder of the solve once its EXACT step -- the factorisation's, measured

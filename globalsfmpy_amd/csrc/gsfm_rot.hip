@@ -164,7 +164,7 @@ gsfm_status gsfm_rot_solve_sigma_consensus(gsfm_rot_problem* P, double* rot, int
   const double weight_zero = one_over_sigma * (std::tgamma(dof_minus_one_per_two) - c.gk);
   // The scalar-weight planes live on the device for the whole loop, each in its kernel's own order.  There is no weight pass: the first
   // cost sweep and the first linearisation of every inner solve start from exactly the rotations the reference computes the weights at
-  // (:378-416), so they compute, store and use them (kernels.hpp, SigmaDev).  The first comparison is against zero weights, like the
+  // (:378-416), so they compute, store and use them (setup_kernels.hpp, SigmaDev).  The first comparison is against zero weights, like the
   // reference's zero-initialised last_weights (:352-353).
   if (P->wmode == W_NONE) {
     if (P->cost.ws.alloc(P->cost.n) != hipSuccess || P->dir.ws.alloc(P->dir.n) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc weight planes");
@@ -706,7 +706,7 @@ gsfm_status gsfm_rot_sweep_bytes(gsfm_rot_problem* P, double* algorithmic, doubl
   // indices 8 B + measurement 24 B (32 B for the quaternion types) + whitening 48/8/0 B + weight out 8 B
   const double w = P->wmode == W_MATRIX ? 48.0 : P->wmode == W_SCALAR ? 8.0 : 0.0;
   if (algorithmic) *algorithmic = 8.0 + (P->functor == F_AA ? 24.0 : 32.0) + w + 8.0;
-  // as laid out: uint2 idx + the measurement (24 B on the W_MATRIX problems of >= 1 M edges since round 6: three quaternion components, kernels.hpp qrel_three; 32 B otherwise) + whitening planes; the weight is consumed in-kernel (no per-edge store)
+  // as laid out: uint2 idx + the measurement (24 B on the W_MATRIX problems of >= 1 M edges since round 6: three quaternion components, edge_math.hpp qrel_three; 32 B otherwise) + whitening planes; the weight is consumed in-kernel (no per-edge store)
   if (layout) *layout = 8.0 + (P->q3 ? 24.0 : 32.0) + w;
   return GSFM_OK;
 }

@@ -260,12 +260,12 @@ struct gsfm_rot_problem {
   PcgGraph pcg_graph_b, pcg2_graph_b;
   void reset_pcg_graphs() { pcg_graph.reset(); pcg2_graph.reset(); pcg_graph_b.reset(); pcg2_graph_b.reset(); }
 
-  bool q3 = false;            // the measurement planes hold three quaternion components, 24 B (kernels.hpp qrel_three: W_MATRIX problems of >= 1 M edges)
+  bool q3 = false;            // the measurement planes hold three quaternion components, 24 B (edge_math.hpp qrel_three: W_MATRIX problems of >= 1 M edges)
   EdgePlanes cost;            // cost-owned edges
   double cost_n_global = 0.0; // edges counted in the cost over ALL ranks (= cost.n unsharded; sharded: summed in the create-time agreement, identical on every rank)
   DevBuf<uint2> cost_idx;
   DevBuf<CostTile> cost_tiles;
-  // Laplacian form of the normal matrix (kernels.hpp, lin_rows): chosen per linearisation; u_rot = R^T p for the mat-vec
+  // Laplacian form of the normal matrix (lin_kernels.hpp, lin_rows): chosen per linearisation; u_rot = R^T p for the mat-vec
   const double2* q_lin = nullptr;   // quaternions the current blocks were linearised at
   bool lap = false, lap_capable = false, lin_is_lap = false;   // lin_is_lap: what the stored blocks currently are
   DevBuf<double> u_rot;
@@ -295,7 +295,7 @@ struct gsfm_rot_problem {
   DevBuf<double> w_gather;   // sharded single-reduction PCG: per rank [slice of A u | delta partials of its rows] (run_pcg2)
   uint32_t w_tail = 0;
   DevBuf<Cg2Scalars> cg2sc;
-  // two-level preconditioner (kernels.hpp, k_coarse_*): aggregates wanted (0 = off, decided at create) / in use for the current LM step
+  // two-level preconditioner (pcg_kernels.hpp, k_coarse_*): aggregates wanted (0 = off, decided at create) / in use for the current LM step
   uint32_t coarse_want = 0, coarse_n = 0, coarse_chunk = 0;
   bool coarse_adaptive = false;     // use it only once a block-Jacobi PCG solve of the run has needed more than 150 iterations
   DevBuf<double> coarseA, coarseAinv, coarse_rc, coarse_xc, coarse_scale, coarse_part;

@@ -15,7 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "loss_dev.hpp"
-#include "kernels.hpp"
+#include "edge_math.hpp"
+#include "dense_assemble_kernels.hpp"
 
 namespace gsfm {
 

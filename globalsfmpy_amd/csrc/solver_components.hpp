@@ -127,13 +127,10 @@ void comps_enqueue_dense(gsfm_rot_problem* P, hipStream_t st) {
   hipLaunchKernelGGL(k_comp_activity, dim3(C.n_items), dim3(GSFM_BLOCK), 0, st, (const uint32_t*)C.item_ptr.p, (const uint32_t*)C.item_cams.p, (const double*)P->b.p,
                      (const double*)P->Minv.p, (const double*)(P->scal.p + SC_ZBOUND), pcg_abs_floor2(P), C.active.p, C.stepmax.p, C.stepprev.p, C.steprad.p, (const int*)C.info.p, C.frozen.p, comp_freeze_below(P),
                      (const double*)(P->scal.p + SC_COMP_RADIUS));
-  DenseArgs a{};
-  a.n_rows = P->n_rows; a.row_ptr = P->row_ptr.p; a.col = P->col.p; a.h0 = P->h0.p; a.h1 = P->h1.p; a.h2 = P->h2.p; a.h3 = P->h3.p; a.h4 = P->h4.p;
-  a.Mblk = P->Mblk.p; a.b = P->b.p; a.A = nullptr; a.n = 0; a.T = 0; a.q = P->q_lin; a.lap = P->lin_is_lap; a.info_slot = P->scal.p + SC_DENSE_INFO; a.rcg = P->r.p;
+  const DenseArgs a = dense_args(P);   // (A, n, T stay zero: every item carries its own)
   const CompMap cm{C.cam_item.p, C.cam_loc.p, P->own_begin};
   hipLaunchKernelGGL(k_comp_assemble, dim3((uint32_t)C.item_cams.n), dim3(GSFM_BLOCK), 0, st, a, cm, (const CholBatchItem*)C.items.p, (const uint32_t*)C.item_cams.p);
-  const char* fused_env = getenv("GSFM_CHOL_FUSED");
-  enqueue_chol_batch((const CholBatchItem*)C.items.p, C.n_items, C.Tmax, st, fused_env && fused_env[0] == '1');
+  enqueue_chol_batch((const CholBatchItem*)C.items.p, C.n_items, C.Tmax, st, chol_fused_requested());
 }
 
 // The step of a disconnected problem: *used = false if the path does not apply (the caller then runs its generic one).  On return the step

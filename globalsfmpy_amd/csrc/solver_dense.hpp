@@ -53,13 +53,10 @@ int run_dense(gsfm_rot_problem* P, bool* used, bool plain = false) {
   auto enqueue = [&]() {
     (void)hipMemsetAsync(P->denseA.p, 0, 8 * elems, P->stream);
     int* const info = (int*)(P->scal.p + SC_DENSE_INFO);
-    DenseArgs a{};
-    a.n_rows = P->n_rows; a.row_ptr = P->row_ptr.p; a.col = P->col.p; a.h0 = P->h0.p; a.h1 = P->h1.p; a.h2 = P->h2.p; a.h3 = P->h3.p; a.h4 = P->h4.p;
-    a.Mblk = P->Mblk.p; a.b = P->b.p; a.A = P->denseA.p; a.n = n; a.T = T; a.q = P->q_lin; a.lap = P->lin_is_lap; a.info_slot = P->scal.p + SC_DENSE_INFO; a.rcg = P->r.p;
+    DenseArgs a = dense_args(P); a.A = P->denseA.p; a.n = n; a.T = T;
     if (P->cs.active) hipLaunchKernelGGL(k_dense_assemble_col, dim3(P->cs.n_wg), dim3(GSFM_BLOCK), 0, P->stream, a, P->cs.dev());
     else hipLaunchKernelGGL(k_dense_assemble, dim3(P->n_rows), dim3(GSFM_BLOCK), 0, P->stream, a);
-    const char* fused_env = getenv("GSFM_CHOL_FUSED");
-    enqueue_chol_solve(P->denseA.p, P->denseL.p, P->dense_x.p, n, T, info, P->stream, fused_env && fused_env[0] == '1' && T <= GSFM_CHOL_FUSED_MAX_T);
+    enqueue_chol_solve(P->denseA.p, P->denseL.p, P->dense_x.p, n, T, info, P->stream, chol_fused_requested() && T <= GSFM_CHOL_FUSED_MAX_T);
     (void)hipMemcpyAsync(P->xcg.p, P->dense_x.p, 8 * (size_t)n, hipMemcpyDeviceToDevice, P->stream);
     // (exact solve: the PCG residual term of the model decrease is zero -- k_dense_assemble cleared it)
   };

@@ -219,19 +219,22 @@ int all_reduce(gsfm_rot_problem* P, double* buf, size_t count) {
 
 // ---- launches -----------------------------------------------------------------------------
 enum { SC_COST = 0, SC_GMAX = 1, SC_STEP = 2 /* ..6 */, SC_XNORM2 = 7, SC_TRIAL = 8, SC_ZL8 = 9 /* k_cam_step's sixth sum (loose steps) */, SC_ZBOUND = 10 /* k_cam_bound's B: the absolute floor of the PCG tolerance */, SC_COMPBAD = 11 /* packed sharded problems: ranks whose component factorisation broke down (all-reduced) */, SC_COMP_RADIUS = 12 /* component step: the trust radius of this step (k_comp_activity: the damping its measurement is taken at) */, SC_DENSE_INFO = 15 /* an int: status of the Cholesky factorisation (CholArgs::info; != 0: the step holds garbage, NaN or inf -- test it before touching the step) */, SC_N = 16,
-       SC_CTL = 16 /* .. 31: the device-side LM control block (kernels.hpp, CT_*) */, SC_REC = 32 /* .. 95: ring of four per-iteration records of it */, SC_ALL = 96 };
+       SC_CTL = 16 /* .. 31: the device-side LM control block (lm_kernels.hpp, CT_*) */, SC_REC = 32 /* .. 95: ring of four per-iteration records of it */, SC_ALL = 96 };
 enum { T_LIN = 0, T_SWEEP = 1, T_CG = 2 };
 
 void launch_cache(gsfm_rot_problem* P, const double* x, double2* q) {
   hipLaunchKernelGGL(k_cam_cache, dim3(grid_for(P->n_cams)), dim3(GSFM_BLOCK), 0, P->stream, x, P->n_cams, P->param_dim, q);
 }
 
+// Kernel arguments the problem determines are filled in one place each (the caller sets what is particular to its launch): the block-CSR's row structure and the directed entries' planes
+template <class A> void set_rows(A& a, const gsfm_rot_problem* P) { a.n_rows = P->n_rows; a.row_base = P->own_begin; a.G = P->G; a.row_ptr = P->row_ptr.p; a.col = P->col.p; }
+template <class A> void set_dir_planes(A& a, const gsfm_rot_problem* P) { a.eid = P->dir.eid.p; a.qr0 = P->dir.qr0.p; a.qr1 = P->dir.qr1.p; a.w0 = P->dir.w0.p; a.w1 = P->dir.w1.p; a.w2 = P->dir.w2.p; a.ws = P->dir.ws.p; }
+
 // s of every edge this rank holds, by rows (sharded problems): see k_row_s
 int launch_row_s(gsfm_rot_problem* P, const double2* q, double* s_out, bool unit_weights) {
   if (P->cs.active) {   // column-sorted layout (Laplacian-capable functors only); unit_weights is no longer asked for by any caller
     ColRowSArgs ca{};
-    ca.L = P->cs.dev(); ca.row_base = P->own_begin; ca.n_rows = P->n_rows; ca.eid = P->dir.eid.p; ca.qr0 = P->dir.qr0.p; ca.qr1 = P->dir.qr1.p;
-    ca.w0 = P->dir.w0.p; ca.w1 = P->dir.w1.p; ca.w2 = P->dir.w2.p; ca.ws = P->dir.ws.p; ca.q = q; ca.s_out = s_out;
+    ca.L = P->cs.dev(); ca.row_base = P->own_begin; ca.n_rows = P->n_rows; set_dir_planes(ca, P); ca.q = q; ca.s_out = s_out;
     const dim3 grid(P->cs.n_wg), blk(GSFM_BLOCK);
     if (unit_weights) return fail(GSFM_ERR_UNSUPPORTED, "unit-weight row sweep on the column-sorted layout");
     if (P->functor == F_AA && P->wmode == W_NONE) hipLaunchKernelGGL((k_col_s<F_AA, W_NONE>), grid, blk, 0, P->stream, ca);
@@ -243,8 +246,7 @@ int launch_row_s(gsfm_rot_problem* P, const double2* q, double* s_out, bool unit
     return 0;
   }
   RowSArgs ra{};
-  ra.n_rows = P->n_rows; ra.row_base = P->own_begin; ra.G = P->G; ra.row_ptr = P->row_ptr.p; ra.col = P->col.p; ra.eid = P->dir.eid.p;
-  ra.qr0 = P->dir.qr0.p; ra.qr1 = P->dir.qr1.p; ra.w0 = P->dir.w0.p; ra.w1 = P->dir.w1.p; ra.w2 = P->dir.w2.p; ra.ws = P->dir.ws.p; ra.q = q; ra.s_out = s_out;
+  set_rows(ra, P); set_dir_planes(ra, P); ra.q = q; ra.s_out = s_out;
   const dim3 grid(grid_for((size_t)P->n_rows * P->G)), blk(GSFM_BLOCK);
   const int f = P->functor, w = P->wmode;
 #define GSFM_ROWS(F, W, U) hipLaunchKernelGGL((k_row_s<F, W, U>), grid, blk, 0, P->stream, ra)
@@ -268,6 +270,18 @@ CostArgs cost_args(gsfm_rot_problem* P, const double2* q) {
   a.q = q; a.loss = P->d_loss.p; a.eid = P->cost.eid.p; a.partials = P->part_cost.p;
   return a;
 }
+MatvecArgs matvec_args(const gsfm_rot_problem* P, const double* Mblk, const double* p, double* y, const int* done) {   // K3, and MatvecCgArgs::mv of its fused PCG form
+  MatvecArgs a{}; set_rows(a, P);
+  a.h0 = P->h0.p; a.h1 = P->h1.p; a.h2 = P->h2.p; a.h3 = P->h3.p; a.h4 = P->h4.p; a.Mblk = Mblk; a.p = p; a.y = y; a.done = done;
+  a.q = P->q_lin; a.u = P->u_rot.p;   // Laplacian form: the caller keeps u_rot = R^T p (PCG vector kernels, or k_cam_rotT)
+  return a;
+}
+DenseArgs dense_args(const gsfm_rot_problem* P) {   // the exact step's assembly; A, n, T (run_dense's single matrix) stay zero for the batched components, whose items carry their own
+  DenseArgs a{}; a.n_rows = P->n_rows; a.row_ptr = P->row_ptr.p; a.col = P->col.p; a.h0 = P->h0.p; a.h1 = P->h1.p; a.h2 = P->h2.p; a.h3 = P->h3.p; a.h4 = P->h4.p;
+  a.Mblk = P->Mblk.p; a.b = P->b.p; a.q = P->q_lin; a.lap = P->lin_is_lap; a.info_slot = P->scal.p + SC_DENSE_INFO; a.rcg = P->r.p;
+  return a;
+}
+bool chol_fused_requested() { const char* e = getenv("GSFM_CHOL_FUSED"); return e && e[0] == '1'; }   // the fused Cholesky step of rounds 2-5 (A/B, the bit-identity test); read at every enqueue
 
 // host-callback loss: s per edge -> host -> rho triples per ORIGINAL edge -> device
 int refresh_external_rho(gsfm_rot_problem* P, const double2* q) {
@@ -345,9 +359,7 @@ int launch_lin(gsfm_rot_problem* P, const double2* q, const double* go, bool fus
   if (fused && !trial_lin_supported(P)) return fail(GSFM_ERR_UNSUPPORTED, "fused trial evaluation without its preconditions");
   if (P->cb) { if (int st = refresh_external_rho(P, q)) return st; }
   LinArgs a{};
-  a.n_rows = P->n_rows; a.row_base = P->own_begin; a.G = P->G; a.row_ptr = P->row_ptr.p; a.col = P->col.p; a.eid = P->dir.eid.p;
-  a.qr0 = P->dir.qr0.p; a.qr1 = P->dir.qr1.p; a.w0 = P->dir.w0.p; a.w1 = P->dir.w1.p; a.w2 = P->dir.w2.p; a.ws = P->dir.ws.p; a.ws_rw = P->dir.ws.p;
-  a.q = q; a.loss = P->d_loss.p; a.rho_ext = P->cb ? P->rho_ext.p : nullptr; a.fast_ok = k2_fast_path(P) ? 1 : 0; a.go = go;
+  set_rows(a, P); set_dir_planes(a, P); a.ws_rw = P->dir.ws.p; a.q = q; a.loss = P->d_loss.p; a.rho_ext = P->cb ? P->rho_ext.p : nullptr; a.fast_ok = k2_fast_path(P) ? 1 : 0; a.go = go;
   if (P->sigma_pending_lin) { a.sigma = P->sigma; a.sigma.on = 1; P->sigma_pending_lin = false; }
   if (!P->lap && !P->h3.p && (P->h3.alloc(P->dir.n) != hipSuccess || P->h4.alloc(P->dir.n) != hipSuccess)) return fail(GSFM_ERR_HIP, "allocating the general normal-equation blocks failed");
   a.h0 = P->h0.p; a.h1 = P->h1.p; a.h2 = P->h2.p; a.h3 = P->h3.p; a.h4 = P->h4.p; a.gD = P->gD.p; a.lap = P->lap;
@@ -387,7 +399,7 @@ void launch_prep(gsfm_rot_problem* P, const gsfm_rot_options& o, double radius, 
   hipLaunchKernelGGL(k_cam_prep, dim3(P->nb_cam), dim3(GSFM_BLOCK), 0, P->stream, a);
   if (reduce) {
     hipLaunchKernelGGL(k_max_partials, dim3(1), dim3(GSFM_BLOCK), 0, P->stream, P->part_cam.p, P->nb_cam, P->scal.p + SC_GMAX);
-    // B of the PCG tolerance's absolute floor (kernels.hpp, k_cam_bound) for the damping just built -- host-controlled steps only: the
+    // B of the PCG tolerance's absolute floor (cam_kernels.hpp, k_cam_bound) for the damping just built -- host-controlled steps only: the
     // device-controlled exact pipeline runs no PCG (a PCG step behind it finds the bound of the last host-controlled prep, or none)
     double* part = P->part_cam.p + (size_t)5 * P->nb_cam;
     hipLaunchKernelGGL(k_cam_bound, dim3(P->nb_cam), dim3(GSFM_BLOCK), 0, P->stream, (const double*)P->Minv.p, (const double*)P->Tinv.p, (const double*)P->active.p, P->n_cams, part);
@@ -395,25 +407,32 @@ void launch_prep(gsfm_rot_problem* P, const gsfm_rot_options& o, double radius, 
   }
 }
 
+// K3c, the column-sorted mat-vec pair (always Laplacian): k_mv_col, or with `cg` k_mv_col_cg (the single-reduction PCG's entry decision: it takes no `done`), then k_mv_col_finish
+void enqueue_mv_col(gsfm_rot_problem* P, const double* Mblk, const double* p, double* y, const int* done, double* dot_part, const Cg2Args* cg = nullptr) {
+  auto& c = P->cs;
+  ColMatvecArgs m{};
+  m.L = c.dev(); m.b0 = P->h0.p; m.b1 = P->h1.p; m.b2 = P->h2.p; m.u = P->u_rot.p; m.part = c.part.p; m.done = cg ? nullptr : done;
+  // (occupancy: four workgroups per CU; holding it at 3 / 2 / 1 with unused dynamic LDS measured 215 / 226 / 306 us against 196)
+  const dim3 grid(c.n_wg), blk(GSFM_K3C_THREADS);
+  if (cg) {
+    const ColMatvecCgArgs cm{m, *cg};
+    if (c.k16_active) hipLaunchKernelGGL(k_mv_col_cg<true>, grid, blk, 0, P->stream, cm);
+    else hipLaunchKernelGGL(k_mv_col_cg<false>, grid, blk, 0, P->stream, cm);
+  } else if (c.k16_active) hipLaunchKernelGGL(k_mv_col<true>, grid, blk, 0, P->stream, m);
+  else hipLaunchKernelGGL(k_mv_col<false>, grid, blk, 0, P->stream, m);
+  ColFinishArgs f{};
+  f.n_rows = P->n_rows; f.row_base = P->own_begin; f.nch = c.nch; f.n_wg = c.n_wg; f.part = c.part.p; f.Mblk = Mblk; f.p = p; f.q = P->q_lin; f.y = y; f.done = done; f.dot_part = dot_part;
+  hipLaunchKernelGGL(k_mv_col_finish, dim3(grid_for(P->n_rows)), dim3(GSFM_BLOCK), 0, P->stream, f);
+}
+
 int launch_matvec(gsfm_rot_problem* P, const double* Mblk, const double* p, double* y, const int* done, double* dot_part = nullptr, bool* dot_done = nullptr) {
   if (dot_done) *dot_done = false;
-  MatvecArgs a{};
-  a.n_rows = P->n_rows; a.row_base = P->own_begin; a.G = P->G; a.row_ptr = P->row_ptr.p; a.col = P->col.p;
-  a.h0 = P->h0.p; a.h1 = P->h1.p; a.h2 = P->h2.p; a.h3 = P->h3.p; a.h4 = P->h4.p; a.Mblk = Mblk; a.p = p; a.y = y; a.done = done;
-  a.q = P->q_lin; a.u = P->u_rot.p;   // Laplacian form: the caller keeps u_rot = R^T p (PCG vector kernels, or k_cam_rotT)
-  if (P->cs.active) {   // graphs without locality: the column-sorted form (always Laplacian)
-    auto& c = P->cs;
-    ColMatvecArgs m{};
-    m.L = c.dev(); m.b0 = P->h0.p; m.b1 = P->h1.p; m.b2 = P->h2.p; m.u = P->u_rot.p; m.part = c.part.p; m.done = done;
-    // (occupancy: four workgroups per CU; holding it at 3 / 2 / 1 with unused dynamic LDS measured 215 / 226 / 306 us against 196)
-    if (c.k16_active) hipLaunchKernelGGL(k_mv_col<true>, dim3(c.n_wg), dim3(GSFM_K3C_THREADS), 0, P->stream, m);
-    else hipLaunchKernelGGL(k_mv_col<false>, dim3(c.n_wg), dim3(GSFM_K3C_THREADS), 0, P->stream, m);
-    ColFinishArgs f{};
-    f.n_rows = P->n_rows; f.row_base = P->own_begin; f.nch = c.nch; f.n_wg = c.n_wg; f.part = c.part.p; f.Mblk = Mblk; f.p = p; f.q = P->q_lin; f.y = y; f.done = done;
-    if (dot_part && !P->sharded) { f.dot_part = dot_part; *dot_done = true; }   // (one GPU: rows = cameras, the finish grid is the camera kernels' grid)
-    hipLaunchKernelGGL(k_mv_col_finish, dim3(grid_for(P->n_rows)), dim3(GSFM_BLOCK), 0, P->stream, f);
+  if (P->cs.active) {   // graphs without locality: the column-sorted form
+    if (P->sharded) dot_part = nullptr; else if (dot_part) *dot_done = true;   // (one GPU: rows = cameras, the finish grid is the camera kernels' grid)
+    enqueue_mv_col(P, Mblk, p, y, done, dot_part);
     return P->pcg_local ? 0 : all_gather(P, y, (size_t)P->shard.slice_width * 3);
   }
+  const MatvecArgs a = matvec_args(P, Mblk, p, y, done);
   if (P->lin_is_lap) hipLaunchKernelGGL(k_matvec<true>, dim3(grid_for((size_t)P->n_rows * P->G)), dim3(GSFM_BLOCK), 0, P->stream, a);
   else hipLaunchKernelGGL(k_matvec<false>, dim3(grid_for((size_t)P->n_rows * P->G)), dim3(GSFM_BLOCK), 0, P->stream, a);
   return P->pcg_local ? 0 : all_gather(P, y, (size_t)P->shard.slice_width * 3);

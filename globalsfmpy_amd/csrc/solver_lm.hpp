@@ -23,7 +23,7 @@ constexpr int GSFM_INTERNAL_RESTART = 1000;
 // reduce = false: the caller sums k_cam_step's partials itself (k_lm_decide)
 int launch_step(gsfm_rot_problem* P, bool inexact = false, bool reduce = true) {
   StepArgs a{};
-  if (inexact && P->lap_capable) {   // (functors whose cost depends on R_j R_i^T alone: for those the gauge is an exact symmetry) a loose PCG iterate: its gauge component is taken out first (kernels.hpp, k_gauge_part) -- inside k_cam_step, the PCG state stays resumable
+  if (inexact && P->lap_capable) {   // (functors whose cost depends on R_j R_i^T alone: for those the gauge is an exact symmetry) a loose PCG iterate: its gauge component is taken out first (cam_kernels.hpp, k_gauge_part) -- inside k_cam_step, the PCG state stays resumable
     const double2* gq = P->q_lin ? P->q_lin : P->q.p;
     GaugeArgs ga{P->n_cams, P->nb_cam, P->active.p, gq, P->Lam.p, P->xcg.p, P->r.p, P->part_gauge.p};
     hipLaunchKernelGGL(k_gauge_part, dim3(P->nb_cam), dim3(GSFM_BLOCK), 0, P->stream, ga);
@@ -360,7 +360,7 @@ struct LmSolve {
     return LM_GO_ON;
   }
 
-  // ---- an exact step with the trust-region decisions on the device (kernels.hpp, k_lm_decide) ----
+  // ---- an exact step with the trust-region decisions on the device (lm_kernels.hpp, k_lm_decide) ----
   // The whole LM iteration -- factorisation, step, trial cost, decision, predicated accept path, damping for the next step -- is enqueued without
   // a host decision, and iteration k + 1 is enqueued BEFORE iteration k's record is read (from a side stream), so the GPU never waits for the
   // host between two exact steps.  An iteration enqueued ahead of a verdict that ends the run (termination, broken factor) decides nothing (CT_SKIPPED).
@@ -535,7 +535,7 @@ struct LmSolve {
     double tn = std::fmax(kappa * sn / sqrt_n, eps_rad / std::fmax(sn / sqrt_n, 1e-300));
     // ... and no single camera may be left far from its exact step: block-Jacobi's estimate of what each camera's step still lacks
     // (k_cam_step's sixth sum, a smooth maximum in radians) is held against 10 x the rms tolerance -- the energy norm does not see a
-    // camera whose weights have all but vanished (kernels.hpp, StepArgs::Minv)
+    // camera whose weights have all but vanished (cam_kernels.hpp, StepArgs::Minv)
     const double zmax = std::pow(std::fmax(zl8, 0.0), 0.125) * (P->param_dim == 4 ? 2.0 : 1.0);
     *cams_ok = zmax <= zcap * eps_rad;
     if (!*cams_ok) tn = std::fmin(tn, 0.5 * tau_now * (zcap * eps_rad / zmax));

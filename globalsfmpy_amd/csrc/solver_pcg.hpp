@@ -53,9 +53,8 @@ int coarse_build(gsfm_rot_problem* P, bool pcg_struggles) {
   const int tk = P->timer.begin(T_CG);
   HIPCHK(hipMemsetAsync(P->coarseA.p, 0, 8 * (size_t)nc * nc, P->stream));
   CoarseAsmArgs a{};
-  a.n_rows = P->n_rows; a.G = P->G; a.n_agg = na; a.chunk = P->coarse_chunk; a.row_ptr = P->row_ptr.p; a.col = P->col.p;
-  a.h0 = P->h0.p; a.h1 = P->h1.p; a.h2 = P->h2.p; a.Mblk = P->Mblk.p; a.q = P->q_lin; a.Ac = P->coarseA.p;
-  a.row_base = P->own_begin; a.scale = P->coarse_scale.p;
+  set_rows(a, P); a.n_agg = na; a.chunk = P->coarse_chunk;
+  a.h0 = P->h0.p; a.h1 = P->h1.p; a.h2 = P->h2.p; a.Mblk = P->Mblk.p; a.q = P->q_lin; a.Ac = P->coarseA.p; a.scale = P->coarse_scale.p;
   {  // the fixed-point scale must be the same on every rank: the largest diagonal entry over ALL cameras (Mblk is complete everywhere)
     const uint32_t nb = (uint32_t)grid_for(P->n_cams);
     hipLaunchKernelGGL(k_coarse_scale, dim3(nb), dim3(GSFM_BLOCK), 0, P->stream, (const double*)P->Mblk.p, P->n_cams, 0u, P->part_a.p, P->coarse_scale.p, 0);
@@ -92,7 +91,7 @@ bool graph_collectives_ok(const gsfm_rot_problem* P, const gsfm_rot_options& o) 
   return !(e && *e && atoi(e) == 0);
 }
 
-// ---- the PCG's status without a stream synchronisation (kernels.hpp, k_pcg_mail) -----------------------------------------------------------
+// ---- the PCG's status without a stream synchronisation (pcg_kernels.hpp, k_pcg_mail) -----------------------------------------------------------
 // mail_usable: allocates on first use (mapped, coherent host memory + the device counter); the read-backs remain the fallback when that fails.
 bool mail_usable(gsfm_rot_problem* P) {
   if (P->mail_state == 0) {
@@ -140,7 +139,7 @@ struct PcgStagnation {
   }
 };
 
-// floor^2 of the absolute tolerance (kernels.hpp, k_cam_bound): 2e-14 rad -- below what a relative residual of 1e-12 leaves on a step of a degree
+// floor^2 of the absolute tolerance (cam_kernels.hpp, k_cam_bound): 2e-14 rad -- below what a relative residual of 1e-12 leaves on a step of a degree
 // For a DISCONNECTED problem under a smooth loss the floor is 1e-11 rad: its scenes are independent problems that converge at their own pace,
 // and the ones that have converged must stop costing iterations while the slowest iterates on (C4: 13 of 14); what they are left short of is
 // their conditioning times 1e-11 rad, five orders inside the bar.  (Not under MAGSAC: an iterate 1e-11 rad off can sit in another table cell.)
@@ -304,10 +303,7 @@ int run_pcg2(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double 
     double* slot = P->w_gather.p + (size_t)P->shard.rank * stride;
     w_own = slot - 3 * (size_t)P->own_begin; dots_own = slot + 3 * (size_t)slice;
   }
-  MatvecCgArgs m{};
-  m.mv.n_rows = P->n_rows; m.mv.row_base = P->own_begin; m.mv.G = P->G; m.mv.row_ptr = P->row_ptr.p; m.mv.col = P->col.p;
-  m.mv.h0 = P->h0.p; m.mv.h1 = P->h1.p; m.mv.h2 = P->h2.p; m.mv.h3 = P->h3.p; m.mv.h4 = P->h4.p; m.mv.Mblk = P->Mblk.p;
-  m.mv.p = P->z.p; m.mv.y = w_own; m.mv.done = nullptr; m.mv.q = P->q_lin; m.mv.u = P->u_rot.p; m.with_dots = 1; m.reps = (uint32_t)reps;
+  MatvecCgArgs m{matvec_args(P, P->Mblk.p, P->z.p, w_own, nullptr), /* cg: set per iteration */ {}, /* with_dots */ 1, (uint32_t)reps};
   const dim3 gcam(P->nb_cam), gmv(nb_mv), blk(GSFM_BLOCK);
   const int tk0 = P->timer.begin(T_CG);
   if (resume) hipLaunchKernelGGL(k_cg2_resume, dim3(1), dim3(1), 0, P->stream, P->cg2sc.p, tol, etol2);
@@ -317,17 +313,7 @@ int run_pcg2(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double 
   // start at par == 0, first == 0, so the very first iteration is launched plainly and chunks have even length.
   auto enqueue_iter = [&]() -> int {
     m.cg = c; m.cg.part_d = dots_own;
-    if (P->cs.active) {   // column-sorted layout: K3c with the same entry decision, delta partials from its finishing kernel (one per camera block)
-      auto& L = P->cs;
-      ColMatvecCgArgs cm{};
-      cm.mv.L = L.dev(); cm.mv.b0 = P->h0.p; cm.mv.b1 = P->h1.p; cm.mv.b2 = P->h2.p; cm.mv.u = P->u_rot.p; cm.mv.part = L.part.p; cm.mv.done = nullptr; cm.cg = c;
-      if (L.k16_active) hipLaunchKernelGGL(k_mv_col_cg<true>, dim3(L.n_wg), dim3(GSFM_K3C_THREADS), 0, P->stream, cm);
-      else hipLaunchKernelGGL(k_mv_col_cg<false>, dim3(L.n_wg), dim3(GSFM_K3C_THREADS), 0, P->stream, cm);
-      ColFinishArgs f{};
-      f.n_rows = P->n_rows; f.row_base = P->own_begin; f.nch = L.nch; f.n_wg = L.n_wg; f.part = L.part.p; f.Mblk = P->Mblk.p; f.p = P->z.p; f.q = P->q_lin; f.y = w_own;
-      f.done = &P->cg2sc.p->done; f.dot_part = dots_own;
-      hipLaunchKernelGGL(k_mv_col_finish, dim3(grid_for(P->n_rows)), dim3(GSFM_BLOCK), 0, P->stream, f);
-    }
+    if (P->cs.active) enqueue_mv_col(P, P->Mblk.p, P->z.p, w_own, &P->cg2sc.p->done, dots_own, &c);   // column-sorted layout: K3c with the same entry decision, delta partials from its finishing kernel
     else if (P->lin_is_lap) hipLaunchKernelGGL(k_matvec_cg<true>, gmv, blk, 0, P->stream, m);
     else hipLaunchKernelGGL(k_matvec_cg<false>, gmv, blk, 0, P->stream, m);
     if (P->sharded) {
@@ -370,9 +356,9 @@ bool use_single_reduction(const gsfm_rot_problem* P, const gsfm_rot_options& o) 
 }
 
 // block-Jacobi PCG on (J^T J + Lambda) eta = -g to the relative residual `tol` -- or, etol2 > 0 (a loose solve of the forcing schedule), until the
-// estimated relative energy-norm error squared falls below etol2 (kernels.hpp, cg_energy_stop).  resume_iters < 0: a new solve, its recurrence chosen
+// estimated relative energy-norm error squared falls below etol2 (pcg_kernels.hpp, cg_energy_stop).  resume_iters < 0: a new solve, its recurrence chosen
 // here and reported in *single_reduction; >= 0: continue the solve that stopped after that many iterations (at a looser tolerance) with the one that ran
-// it -- the device state is what the stopping iteration left (kernels.hpp, CgScalars::done_seen): the iterates of an uninterrupted solve at `tol`.
+// it -- the device state is what the stopping iteration left (pcg_kernels.hpp, CgScalars::done_seen): the iterates of an uninterrupted solve at `tol`.
 int pcg_solve(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double etol2, int resume_iters, bool* single_reduction, int* iters_out, double* rel_out) {
   if (resume_iters < 0) *single_reduction = P->coarse_n == 0 && use_single_reduction(P, o);
   return (*single_reduction ? run_pcg2 : run_pcg)(P, o, tol, etol2, resume_iters, iters_out, rel_out);

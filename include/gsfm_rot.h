@@ -181,7 +181,7 @@ typedef struct {
                                           needs.  PCG first stops once the estimated relative energy-norm error of the step is below tau, with tau
                                           chosen so that tau x (rms step size, predicted from the previous accepted step) <= pcg_forcing_tolerance
                                           radians.  (Estimate: Hestenes-Stiefel -- the squared energy error is the sum of the LATER iterations' model
-                                          decreases alpha_j r_j.z_j, extrapolated geometrically from the last four; csrc/kernels.hpp cg_energy_stop.
+                                          decreases alpha_j r_j.z_j, extrapolated geometrically from the last four; csrc/pcg_kernels.hpp cg_energy_stop.
                                           Unlike a residual norm it bounds the missing share of the step whatever the conditioning and the
                                           preconditioner.)  The loose step is evaluated, and every decision taken from it must be the exact step's:
                                           a cost change or step norm more than a factor two away from the function / parameter tolerance decides
@@ -239,7 +239,7 @@ typedef struct {
                                           north_star's parity bar of 1e-6 rad (DESIGN.md section 6 has the measured trade: 1e-7 is 4 % faster on
                                           the benchmark graph and flips a borderline termination on one MAGSAC test graph).  A loose iterate's
                                           component along the gauge (all cameras rotated alike: the null space of J^T J, invisible to the energy
-                                          norm) is removed before the step is taken, as the exact step has none (kernels.hpp, k_gauge_part; for the
+                                          norm) is removed before the step is taken, as the exact step has none (cam_kernels.hpp, k_gauge_part; for the
                                           error types whose cost depends on R_j R_i^T alone, i.e. all but QUATERNION_NORM / ROTATION_MAT_FNORM). */
   int32_t lm_device_control;           /* default 1: for EXACT (Cholesky) steps of unsharded problems with a native loss the trust-region decisions
                                           of an LM iteration -- step validity, function / parameter tolerance, acceptance, the radius law -- are
