@@ -114,6 +114,39 @@ template <typename K> void parallel_count(int T, size_t n, size_t n_keys, K key,
   });
 }
 
+// Stable scatter of the items u in [0, n) by key: item u goes to the next free slot of its key, put(u, slot), where key k owns the slots
+// [start[k], start[k + 1]) (start: the exclusive prefix sum of the counts, one entry per key and the total).  Every thread streams over ALL
+// items and keeps those of its own contiguous key range (ranges balanced by cumulative count), so each key still receives its items in item
+// order: the result is identical to the serial loop for any thread count.  A key outside [0, n_keys) is dropped (a camera of another rank).
+template <typename S, typename K, typename Put> void stable_scatter(int T, size_t n, const std::vector<S>& start, K key, Put put) {
+  const size_t n_keys = start.size() - 1;
+  std::vector<S> fill(start.begin(), start.end() - 1);
+  std::vector<size_t> cut((size_t)T + 1, 0);
+  for (int t = 1; t < T; ++t) cut[t] = (size_t)(std::lower_bound(start.begin(), start.end(), (S)((uint64_t)start[n_keys] * t / T)) - start.begin());
+  cut[T] = n_keys;
+  for (int t = 1; t <= T; ++t) cut[t] = std::max(cut[t], cut[t - 1]);
+  parallel_run(T, [&](int t, int) {
+    const size_t lo = cut[t], hi = cut[t + 1];
+    if (lo >= hi) return;
+    for (size_t u = 0; u < n; ++u) { const size_t k = key(u); if (k >= lo && k < hi) put(u, fill[k]++); }
+  });
+}
+
+// union-find over 0 .. n - 1 with path halving; the smaller index of two roots stays the root (a component's root is its smallest member)
+struct UnionFind {
+  std::vector<uint32_t> parent;
+  explicit UnionFind(size_t n) : parent(n) { for (size_t c = 0; c < n; ++c) parent[c] = (uint32_t)c; }
+  uint32_t find(uint32_t v) { while (parent[v] != v) { parent[v] = parent[parent[v]]; v = parent[v]; } return v; }
+  void unite(uint32_t x, uint32_t y) { const uint32_t a = find(x), b = find(y); if (a != b) parent[a < b ? b : a] = a < b ? a : b; }
+};
+
+// make `dev` the calling thread's device for a scope (an entry point working on a problem that lives on another device than the current one)
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) == hipSuccess && prev != dev) (void)hipSetDevice(dev); else prev = -1; }
+  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- MAGSAC constants / tables (include/gamma_values.cpp; regenerated, see oracle/ref_loss.hpp) ----

@@ -20,21 +20,15 @@ namespace {
 
 // component index per camera (internal numbering), in order of first appearance; cameras without an edge get 0xffffffff
 void component_labels(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j, std::vector<uint32_t>* comp_of, std::vector<uint32_t>* size) {
-  std::vector<uint32_t> parent(n_cams);
+  UnionFind uf(n_cams);
   std::vector<uint8_t> touched(n_cams, 0);
-  for (uint32_t c = 0; c < n_cams; ++c) parent[c] = c;
-  auto find = [&](uint32_t v) { while (parent[v] != v) { parent[v] = parent[parent[v]]; v = parent[v]; } return v; };
-  for (uint64_t e = 0; e < n_edges; ++e) {
-    const uint32_t a = find(edge_i[e]), b = find(edge_j[e]);
-    touched[edge_i[e]] = touched[edge_j[e]] = 1;
-    if (a != b) parent[a < b ? b : a] = a < b ? a : b;
-  }
+  for (uint64_t e = 0; e < n_edges; ++e) { uf.unite(edge_i[e], edge_j[e]); touched[edge_i[e]] = touched[edge_j[e]] = 1; }
   comp_of->assign(n_cams, 0xffffffffu);
   size->clear();
   std::vector<uint32_t> id_of_root(n_cams, 0xffffffffu);
   for (uint32_t c = 0; c < n_cams; ++c) {
     if (!touched[c]) continue;
-    const uint32_t r = find(c);
+    const uint32_t r = uf.find(c);
     if (id_of_root[r] == 0xffffffffu) { id_of_root[r] = (uint32_t)size->size(); size->push_back(0); }
     (*comp_of)[c] = id_of_root[r];
     (*size)[id_of_root[r]]++;

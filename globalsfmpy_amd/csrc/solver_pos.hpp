@@ -40,8 +40,6 @@ using gsfm::PosDev;
 enum { PS_RZ0 = 0, PS_RZA = 1, PS_RZB = 2, PS_PAP = 3, PS_DV = 4, PS_VV = 5, PS_STEP2 = 6, PS_DG = 7, PS_DLD = 8, PS_COST = 9, PS_GMAX = 10,
        PS_XNORM2 = 11, PS_N = 12 };
 
-struct PosDevice { int d; explicit PosDevice(int dev) { (void)hipGetDevice(&d); (void)hipSetDevice(dev); } ~PosDevice() { (void)hipSetDevice(d); } };
-
 PosDev pos_dev(gsfm_pos_problem* P) {
   PosDev a{};
   a.n_cams = P->n_cams; a.n_edges = (uint32_t)P->n_edges;
@@ -422,7 +420,7 @@ void gsfm_pos_options_default(gsfm_pos_options* o) {
 
 void gsfm_pos_problem_destroy(gsfm_pos_problem* P) {
   if (!P) return;
-  PosDevice g(P->device);
+  DeviceGuard g(P->device);
   if (P->stream) { (void)hipStreamSynchronize(P->stream); (void)hipStreamDestroy(P->stream); }
   delete P;
 }
@@ -442,7 +440,7 @@ gsfm_status gsfm_pos_problem_create(uint32_t n_cams, uint64_t n_edges, const uin
 
 gsfm_status gsfm_pos_set_loss(gsfm_pos_problem* P, const gsfm_loss_node* prog, int32_t n) {
   if (!P || (n > 0 && !prog)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
-  PosDevice g(P->device);
+  DeviceGuard g(P->device);
   DevLoss L;
   if (int st = build_dev_loss(prog, n, P->tables, L)) return (gsfm_status)st;
   bool simple = n == 0;
@@ -458,7 +456,7 @@ gsfm_status gsfm_pos_set_loss(gsfm_pos_problem* P, const gsfm_loss_node* prog, i
 
 gsfm_status gsfm_pos_set_loss_callback(gsfm_pos_problem* P, gsfm_loss_callback fn, void* user) {
   if (!P || !fn) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
-  PosDevice g(P->device);
+  DeviceGuard g(P->device);
   if (!P->rho_ext.p && (P->rho_ext.alloc(3 * P->n_edges) != hipSuccess || P->s_dev.alloc(P->n_edges) != hipSuccess))
     return (gsfm_status)fail(GSFM_ERR_HIP, "allocating callback-loss buffers failed");
   P->h_s.resize(P->n_edges); P->h_rho.resize(3 * P->n_edges);
@@ -470,7 +468,7 @@ gsfm_status gsfm_pos_solve(gsfm_pos_problem* P, double* pos, int32_t fixed_cam, 
   if (!P || !pos) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
   if (fixed_cam < -1 || fixed_cam >= (int64_t)P->n_cams || (fixed_cam >= 0 && !P->present[fixed_cam]))
     return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "fixed_cam must be -1 or a camera that appears in an edge");
-  PosDevice g(P->device);
+  DeviceGuard g(P->device);
   gsfm_pos_options o;
   if (opt) o = *opt; else gsfm_pos_options_default(&o);
   gsfm_pos_summary local;
@@ -491,7 +489,7 @@ gsfm_status gsfm_pos_solve(gsfm_pos_problem* P, double* pos, int32_t fixed_cam, 
 
 gsfm_status gsfm_pos_residuals(gsfm_pos_problem* P, const double* pos, double* r_out, double* rho_out) {
   if (!P || !pos) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
-  PosDevice g(P->device);
+  DeviceGuard g(P->device);
   const size_t E = P->n_edges;
   DevBuf<double> d_r, d_rho, d_s;
   if (d_r.alloc(3 * E) != hipSuccess || d_rho.alloc(E) != hipSuccess || d_s.alloc(E) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc residual buffers");
@@ -508,7 +506,7 @@ gsfm_status gsfm_pos_residuals(gsfm_pos_problem* P, const double* pos, double* r
 
 gsfm_status gsfm_pos_linearize(gsfm_pos_problem* P, const double* pos, double* gradient, double* diag_blocks, double* cost) {
   if (!P || !pos) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
-  PosDevice g(P->device);
+  DeviceGuard g(P->device);
   const size_t N = P->n_cams;
   double c = 0.0;
   if (int st = pos_setup_linearize(P, pos, -1, &c)) return (gsfm_status)st;
@@ -530,7 +528,7 @@ gsfm_status gsfm_pos_linearize(gsfm_pos_problem* P, const double* pos, double* g
 gsfm_status gsfm_pos_normal_matvec(gsfm_pos_problem* P, const double* v, double* y) {
   if (!P || !v || !y) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
   if (!P->have_lin) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "call gsfm_pos_linearize or gsfm_pos_step_check first");
-  PosDevice g(P->device);
+  DeviceGuard g(P->device);
   const size_t N = P->n_cams;
   HIPCHK_S(hipMemcpyAsync(P->q.p, v, 24 * N, hipMemcpyHostToDevice, P->stream));
   hipLaunchKernelGGL(k_pos_matvec<false>, pos_row_grid(P->n_cams), dim3(256), 0, P->stream, pos_dev(P), P->q.p, P->q.p, P->S.p, P->D2.p, P->Ap.p);
@@ -545,7 +543,7 @@ gsfm_status gsfm_pos_step_check(gsfm_pos_problem* P, const double* pos, int32_t 
   if (fixed_cam < -1 || fixed_cam >= (int64_t)P->n_cams || (fixed_cam >= 0 && !P->present[fixed_cam]))
     return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "fixed_cam must be -1 or a camera that appears in an edge");
   if (!(radius > 0.0)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "radius must be positive");
-  PosDevice g(P->device);
+  DeviceGuard g(P->device);
   gsfm_pos_options o;
   if (opt) o = *opt; else gsfm_pos_options_default(&o);
   const uint32_t N = P->n_cams, n = 3 * N;
