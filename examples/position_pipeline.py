@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The reference's scripts/sfm_pipeline.py 1DSfM branch through step 7: rotations, FilterRotations(), FilterRelativeTranslation() (the
-1DSfM filter of relative translations; OptimizePairwiseTranslations before it is not built), then camera positions
+"""The reference's scripts/sfm_pipeline.py 1DSfM branch through step 7: rotations, FilterRotations(), OptimizePairwiseTranslations() (every
+pair's position_2 refined with the estimated rotations), FilterRelativeTranslation() (the 1DSfM filter), then camera positions
 (EstimatePosition(HuberLoss(0.1), PositionErrorType.BASELINE) there; NonlinearPositionEstimator.EstimatePositions here) and the PLY
 with the estimated camera positions.
 usage: position_pipeline.py <dataset_dir with EGs.txt, cc.txt> [flags.yaml]"""
@@ -25,6 +25,7 @@ def position_pipeline(dataset_dir, flagfile=None):
     solver.FilterInitialViewGraphAndCalibrateCameras(graph, scene)
     assert solver.EstimateGlobalRotations(HuberLoss(0.1)), solver.LastError()
     solver.FilterRotations()
+    solver.OptimizePairwiseTranslations()
     solver.FilterRelativeTranslation()
     positions = sfm.MapViewIdVector3d()
     estimator = sfm.NonlinearPositionEstimator()

@@ -273,3 +273,6 @@ def declare_position_signatures(lib):
     lib.gsfm_pos_filter_relative_translations.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, _DP, _DP, C.c_int32, _DP, C.c_uint64, C.c_double,
                                                           _DP, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), _DP, _DP, _DP, _U32P, _U32P, _DP]
     lib.gsfm_pos_filter_relative_translations.restype = C.c_int
+    lib.gsfm_pos_refine_relative_translations.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, C.POINTER(C.c_uint64), _DP, _DP, _DP, _DP, _DP,
+                                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), _DP, _DP]
+    lib.gsfm_pos_refine_relative_translations.restype = C.c_int

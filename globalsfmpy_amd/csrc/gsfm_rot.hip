@@ -12,6 +12,7 @@
 #include "spanning_tree.hpp"
 #include "solver_pos.hpp"
 #include "trans_filter.hpp"
+#include "trans_refine.hpp"
 
 // =============================================================================================
 extern "C" {
@@ -396,6 +397,19 @@ gsfm_status gsfm_pos_filter_relative_translations(uint32_t n_cams, uint64_t n_ed
                              axes_out, proj_out, num_passes_out, num_picks_out, kernel_ms);
   } catch (const std::exception& e) {
     return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the translation filter ran out of host resources: ") + e.what());
+  }
+}
+
+gsfm_status gsfm_pos_refine_relative_translations(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j,
+                                                  const uint64_t* match_ptr, const double* matches, const double* intrinsics,
+                                                  const double* rot_aa, const double* rel_t_in, double* rel_t_out, int32_t* status_out,
+                                                  int32_t* iters_out, double* cost_out, double* kernel_ms) {
+  // (a host vector of O(E): an exception must not cross the C boundary)
+  try {
+    return trans_refine_impl(n_cams, n_edges, edge_i, edge_j, match_ptr, matches, intrinsics, rot_aa, rel_t_in, rel_t_out, status_out, iters_out,
+                             cost_out, kernel_ms);
+  } catch (const std::exception& e) {
+    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the translation refinement ran out of host resources: ") + e.what());
   }
 }
 

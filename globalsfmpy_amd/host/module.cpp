@@ -108,6 +108,7 @@ struct ReconstructionEstimatorOptions {
   int num_threads = 1;                                       // reconstruction_estimator_options.h:99
   int min_num_two_view_inliers = 30;                         // :107
   double rotation_filtering_max_difference_degrees = 5.0;    // :122
+  bool refine_relative_translations_after_rotation_estimation = true;   // :129
   bool filter_relative_translations_with_1dsfm = true;       // :143
   int translation_filtering_num_iterations = 48;             // :146
   double translation_filtering_projection_tolerance = 0.1;   // :149
@@ -209,6 +210,12 @@ class GlobalReconstructionEstimator {
     FilterViewPairsFromOrientation(orientations_, options_.rotation_filtering_max_difference_degrees, view_graph_);
     for (ViewId v : RemoveDisconnectedViewPairs(view_graph_)) orientations_.erase(v);
   }
+  // :526-535: every view pair's position_2 refined with the estimated orientations, from the pair's matched features
+  RefineRelativeTranslationsStats OptimizePairwiseTranslations() {
+    if (!view_graph_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
+    if (!options_.refine_relative_translations_after_rotation_estimation || !reconstruction_ || !reconstruction_->matches) return {};
+    return RefineRelativeTranslationsWithKnownRotations(*reconstruction_->matches, orientations_, options_.num_threads, view_graph_);
+  }
   void FilterRelativeTranslation() {  // :537-563 (extract_maximal_rigid_subgraph, off by default, is not built)
     if (!view_graph_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
     if (options_.filter_relative_translations_with_1dsfm) {
@@ -228,6 +235,12 @@ class GlobalReconstructionEstimator {
   gsfm_rot_summary summary_{};
   std::string error_;
 };
+
+py::dict refine_stats_dict(const RefineRelativeTranslationsStats& st) {
+  py::dict d;
+  d["num_refined"] = st.num_refined; d["num_skipped"] = st.num_skipped; d["num_nonfinite"] = st.num_nonfinite; d["kernel_ms"] = st.kernel_ms;
+  return d;
+}
 
 py::dict pos_summary_dict(const gsfm_pos_summary& s) {
   py::dict d;
@@ -250,6 +263,7 @@ void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions
   options.reconstruction_estimator_options.num_threads = options.num_threads;
   get("min_num_inliers_for_valid_match", options.reconstruction_estimator_options.min_num_two_view_inliers);
   get("post_rotation_filtering_degrees", options.reconstruction_estimator_options.rotation_filtering_max_difference_degrees);
+  get("refine_relative_translations_after_rotation_estimation", options.reconstruction_estimator_options.refine_relative_translations_after_rotation_estimation);
   get("filter_relative_translations_with_1dsfm", options.reconstruction_estimator_options.filter_relative_translations_with_1dsfm);
 }
 
@@ -330,6 +344,7 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def_readwrite("num_threads", &ReconstructionEstimatorOptions::num_threads)
       .def_readwrite("min_num_two_view_inliers", &ReconstructionEstimatorOptions::min_num_two_view_inliers)
       .def_readwrite("rotation_filtering_max_difference_degrees", &ReconstructionEstimatorOptions::rotation_filtering_max_difference_degrees)
+      .def_readwrite("refine_relative_translations_after_rotation_estimation", &ReconstructionEstimatorOptions::refine_relative_translations_after_rotation_estimation)
       .def_readwrite("filter_relative_translations_with_1dsfm", &ReconstructionEstimatorOptions::filter_relative_translations_with_1dsfm)
       .def_readwrite("translation_filtering_num_iterations", &ReconstructionEstimatorOptions::translation_filtering_num_iterations)
       .def_readwrite("translation_filtering_projection_tolerance", &ReconstructionEstimatorOptions::translation_filtering_projection_tolerance);
@@ -405,6 +420,11 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def("EstimateGlobalRotationsWithSigmaConsensus", &GlobalReconstructionEstimator::EstimateGlobalRotationsSigmaConsensus,
            py::call_guard<py::gil_scoped_release>())
       .def("FilterRotations", &GlobalReconstructionEstimator::FilterRotations)
+      .def("OptimizePairwiseTranslations", [](GlobalReconstructionEstimator& e) {
+        RefineRelativeTranslationsStats st;
+        { py::gil_scoped_release release; st = e.OptimizePairwiseTranslations(); }
+        return refine_stats_dict(st);
+      })
       .def("FilterRelativeTranslation", &GlobalReconstructionEstimator::FilterRelativeTranslation, py::call_guard<py::gil_scoped_release>())
       .def("LastSummary", [](const GlobalReconstructionEstimator& e) { return summary_dict(e.summary_); })
       .def("LastError", [](const GlobalReconstructionEstimator& e) { return e.error_; });
@@ -483,6 +503,13 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def_readwrite("translation_projection_tolerance", &FilterViewPairsFromRelativeTranslationOptions::translation_projection_tolerance)
       .def_readwrite("seed", &FilterViewPairsFromRelativeTranslationOptions::seed);
   m.def("FilterViewPairsFromRelativeTranslation", &FilterViewPairsFromRelativeTranslation, py::call_guard<py::gil_scoped_release>());
+  // the reference binds neither this function nor its input; here the matches are those the reconstruction carries
+  m.def("RefineRelativeTranslationsWithKnownRotations", [](const Reconstruction& rec, const OrientationMap& o, int num_threads, ViewGraph* vg) {
+    if (!rec.matches) throw std::runtime_error("RefineRelativeTranslationsWithKnownRotations: the reconstruction carries no matched features");
+    RefineRelativeTranslationsStats st;
+    { py::gil_scoped_release release; st = RefineRelativeTranslationsWithKnownRotations(*rec.matches, o, num_threads, vg); }
+    return refine_stats_dict(st);
+  });
   // bind :658, src/compare_reconstructions.cpp:617-647: (view_graph, reconstruction_to_eval, covariances, residuals) -- fills `residuals`
   m.def("residuals_of_relative_rot", [](const ViewGraph& vg, const Reconstruction& rec, const CovarianceMap& cov, std::vector<double>& residuals) {
     gsfm::ResidualsOfRelativeRotations(vg, rec.orientation, cov, &residuals);

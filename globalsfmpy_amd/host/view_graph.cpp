@@ -101,6 +101,10 @@ const TwoViewInfo* ViewGraph::GetEdge(ViewId a, ViewId b) const {
   auto it = edges_.find(Key(a, b));
   return it == edges_.end() ? nullptr : &it->second;
 }
+TwoViewInfo* ViewGraph::GetMutableEdge(ViewId a, ViewId b) {
+  auto it = edges_.find(Key(a, b));
+  return it == edges_.end() ? nullptr : &it->second;
+}
 const std::unordered_set<ViewId>* ViewGraph::GetNeighborIdsForView(ViewId v) const {
   auto it = vertices_.find(v);
   return it == vertices_.end() ? nullptr : &it->second;
@@ -284,6 +288,46 @@ void FilterViewPairsFromRelativeTranslation(const FilterViewPairsFromRelativeTra
                                                                bad.data(), keep.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   if (st != GSFM_OK) throw std::runtime_error(std::string("FilterViewPairsFromRelativeTranslation: ") + gsfm_last_error());
   for (size_t e = 0; e < keys.size(); ++e) if (!keep[e]) view_graph->RemoveEdge(keys[e].first, keys[e].second);
+}
+
+RefineRelativeTranslationsStats RefineRelativeTranslationsWithKnownRotations(const gsfm::EdgeMatches& em,
+                                                                             const std::unordered_map<ViewId, Eigen::Vector3d>& orientations,
+                                                                             int /*num_threads*/, ViewGraph* view_graph) {
+  RefineRelativeTranslationsStats stats;
+  std::vector<ViewId> ids;
+  for (const auto& kv : orientations) ids.push_back(kv.first);
+  std::sort(ids.begin(), ids.end());
+  auto rank = [&ids](ViewId v) { return (uint32_t)(std::lower_bound(ids.begin(), ids.end(), v) - ids.begin()); };
+  std::vector<double> rot(3 * ids.size());
+  for (size_t k = 0; k < ids.size(); ++k) for (int c = 0; c < 3; ++c) rot[3 * k + c] = orientations.at(ids[k])[c];
+  // the edges of `em` (sorted by key) that are still in the graph, with their matches packed in that order
+  std::vector<ViewIdPair> keys;
+  std::vector<uint32_t> ei, ej;
+  std::vector<uint64_t> ptr(1, 0);
+  std::vector<double> m, K, rel;
+  for (size_t e = 0; e < em.edges.size(); ++e) {
+    const ViewIdPair& k = em.edges[e];
+    const TwoViewInfo* info = view_graph->GetEdge(k.first, k.second);
+    if (!info || !orientations.count(k.first) || !orientations.count(k.second)) continue;
+    keys.push_back(k); ei.push_back(rank(k.first)); ej.push_back(rank(k.second));
+    m.insert(m.end(), em.matches.begin() + 4 * em.match_ptr[e], em.matches.begin() + 4 * em.match_ptr[e + 1]);
+    ptr.push_back(m.size() / 4);
+    K.insert(K.end(), em.intrinsics.begin() + 6 * e, em.intrinsics.begin() + 6 * e + 6);
+    for (int c = 0; c < 3; ++c) rel.push_back(info->position_2[c]);
+  }
+  if (keys.empty()) return stats;
+  std::vector<double> out(3 * keys.size());
+  std::vector<int32_t> status(keys.size());
+  const gsfm_status st = gsfm_pos_refine_relative_translations((uint32_t)ids.size(), keys.size(), ei.data(), ej.data(), ptr.data(), m.data(), K.data(),
+                                                               rot.data(), rel.data(), out.data(), status.data(), nullptr, nullptr, &stats.kernel_ms);
+  if (st != GSFM_OK) throw std::runtime_error(std::string("RefineRelativeTranslationsWithKnownRotations: ") + gsfm_last_error());
+  for (size_t e = 0; e < keys.size(); ++e) {
+    if (status[e] == 1) { ++stats.num_skipped; continue; }
+    if (status[e] != 0) { ++stats.num_nonfinite; continue; }
+    ++stats.num_refined;
+    view_graph->GetMutableEdge(keys[e].first, keys[e].second)->position_2 = Eigen::Vector3d(out[3 * e], out[3 * e + 1], out[3 * e + 2]);
+  }
+  return stats;
 }
 
 std::unordered_set<ViewId> RemoveDisconnectedViewPairs(ViewGraph* view_graph) {

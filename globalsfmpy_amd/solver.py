@@ -391,6 +391,39 @@ def filter_relative_translations(n_cams, edge_i, edge_j, rel_t, rot_aa, num_iter
                                "projections": proj, "num_passes": passes, "num_picks": picks, "kernel_ms": ms.value}
 
 
+def refine_relative_translations(n_cams, edge_i, edge_j, match_ptr, matches, intrinsics, rot_aa, rel_t):
+    """gsfm_pos_refine_relative_translations: every view pair's relative translation refined with the known rotations (Theia's
+    OptimizeRelativePositionWithKnownRotation under the definition of include/gsfm_pos.h) on the device, one wavefront per edge.
+    match_ptr: E + 1 offsets into matches (rows of x1 y1 x2 y2 in pixels); intrinsics: E x 6 (f1 u1 v1 f2 u2 v2); rot_aa: N x 3
+    orientations; rel_t: E x 3 position_2 of each pair (returned for skipped and non-finite edges).
+    Returns (rel_t_out E x 3, dict(status (0 refined, 1 skipped, 2 non-finite), iterations, cost, kernel_ms))."""
+    lib = _abi.load_library()
+    n = int(n_cams)
+    ei = np.ascontiguousarray(edge_i, dtype=np.uint32).reshape(-1)
+    ej = np.ascontiguousarray(edge_j, dtype=np.uint32).reshape(-1)
+    mp = np.ascontiguousarray(match_ptr, dtype=np.uint64).reshape(-1)
+    E = ei.shape[0]
+    m = np.ascontiguousarray(matches, dtype=np.float64).reshape(-1, 4)
+    K = np.ascontiguousarray(intrinsics, dtype=np.float64).reshape(E, 6)
+    rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(n, 3)
+    rel = np.ascontiguousarray(rel_t, dtype=np.float64).reshape(-1, 3)
+    if ej.shape[0] != E or rel.shape[0] != E or mp.shape[0] != E + 1:
+        raise ValueError("edge_i, edge_j, rel_t, intrinsics and match_ptr must describe the same edges")
+    if E and int(mp.max()) > m.shape[0]:
+        raise ValueError("match_ptr points past the end of matches")
+    out = np.empty((E, 3))
+    status, iters = np.zeros(E, dtype=np.int32), np.zeros(E, dtype=np.int32)
+    cost = np.zeros(E)
+    ms = C.c_double(0)
+    i32p = C.POINTER(C.c_int32)
+    st = lib.gsfm_pos_refine_relative_translations(n, E, _u32p(ei), _u32p(ej), mp.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(m), _dp(K), _dp(rot),
+                                                   _dp(rel), _dp(out), status.ctypes.data_as(i32p), iters.ctypes.data_as(i32p), _dp(cost),
+                                                   C.byref(ms))
+    if st != 0:
+        raise SolverError("gsfm_pos_refine_relative_translations failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+    return out, {"status": status, "iterations": iters, "cost": cost, "kernel_ms": ms.value}
+
+
 class PositionProblem(ProblemBase):
     """Camera positions from relative translations (include/gsfm_pos.h): the reference's EstimatePositions with BASELINE residuals
     r = (c_j - c_i) / |c_j - c_i| - R(aa_i)^T t_ij on the device.  rel_t: E x 3 position_2 of each view pair (frame of camera i);

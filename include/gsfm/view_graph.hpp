@@ -29,6 +29,7 @@ class ViewGraph {
   bool RemoveEdge(ViewId a, ViewId b);
   bool RemoveView(ViewId v);
   const TwoViewInfo* GetEdge(ViewId a, ViewId b) const;
+  TwoViewInfo* GetMutableEdge(ViewId a, ViewId b);
   const std::unordered_set<ViewId>* GetNeighborIdsForView(ViewId v) const;
   const std::unordered_map<ViewIdPair, TwoViewInfo>& GetAllEdges() const { return edges_; }
   void GetLargestConnectedComponentIds(std::unordered_set<ViewId>* out) const;
@@ -87,6 +88,20 @@ struct FilterViewPairsFromRelativeTranslationOptions {
 // CPU fallback) or the device call fails.
 void FilterViewPairsFromRelativeTranslation(const FilterViewPairsFromRelativeTranslationOptions& options,
                                             const std::unordered_map<ViewId, Eigen::Vector3d>& orientations, ViewGraph* view_graph);
+// thirdparty/TheiaSfM/src/theia/sfm/reconstruction_estimator_utils.cc:244-269 -> optimize_relative_position_with_known_rotation.cc on the
+// device (gsfm_pos_refine_relative_translations, under the definition of include/gsfm_pos.h): every edge of the view graph that has
+// matches in `matches` and whose two views both have an orientation gets its position_2 replaced by the refined unit vector.  Any other
+// edge keeps its position_2 (the reference reads the matches from the reconstruction's tracks and aborts in FindOrDie on a missing
+// orientation), and so does an edge with fewer than 2 matches (skipped) or a non-finite result.  num_threads is accepted and ignored: the
+// edges run side by side on the device, one wavefront each.  Throws std::runtime_error when no device is usable (there is no CPU
+// fallback) or the device call fails.
+struct RefineRelativeTranslationsStats {
+  size_t num_refined = 0, num_skipped = 0, num_nonfinite = 0;
+  double kernel_ms = 0.0;
+};
+RefineRelativeTranslationsStats RefineRelativeTranslationsWithKnownRotations(const gsfm::EdgeMatches& matches,
+                                                                             const std::unordered_map<ViewId, Eigen::Vector3d>& orientations,
+                                                                             int num_threads, ViewGraph* view_graph);
 // thirdparty/TheiaSfM/src/theia/sfm/view_graph/remove_disconnected_view_pairs.cc: keeps the largest component.
 std::unordered_set<ViewId> RemoveDisconnectedViewPairs(ViewGraph* view_graph);
 

@@ -148,6 +148,40 @@ gsfm_status gsfm_pos_filter_relative_translations(uint32_t n_cams, uint64_t n_ed
                                                   double* bad_weight_out, uint8_t* keep_out, uint64_t* n_kept, double* stats_out, double* axes_out,
                                                   double* proj_out, uint32_t* num_passes_out, uint32_t* num_picks_out, double* kernel_ms);
 
+/* Relative translations refined with known rotations: Theia's RefineRelativeTranslationsWithKnownRotations (reconstruction_estimator_utils.cc)
+ * -> OptimizeRelativePositionWithKnownRotation, one small problem per view pair over the pair's matched features, on flat arrays and on
+ * the device.  The reference's random start is overwritten before it is read, so the result is deterministic.  For edge e = (i, j) with
+ * matches m = match_ptr[e] .. match_ptr[e + 1] - 1 (n of them) and intrinsics f1 u1 v1 f2 u2 v2 (those of gsfm_cov_estimate):
+ *   1. features     f1_m = ((x1 - u1) / f1, (y1 - v1) / f1, 1), f2_m likewise from (x2, y2) and the second camera's intrinsics.
+ *   2. constraints  a_m = R1 ((R2^T f2_m) x (R1^T f1_m)), R1 = R(aa_i), R2 = R(aa_j) (Ceres' AngleAxisToRotationMatrix): three components,
+ *      in the frame of camera i like position_2.
+ *   3. IRLS         w_m = 1, cost = 0, inner = 0; at most 100 iterations, stopping once inner reaches 10.  One iteration:
+ *        w_m <- max(w_m, 1e-7);  L = sum_m a_m a_m^T / w_m;
+ *        t = unit eigenvector of the smallest eigenvalue of L (Theia: the last left singular vector; its sign is free and nothing
+ *            here depends on it).  L is divided by its trace first; cyclic Jacobi in fp64 over the pairs (0,1), (0,2), (1,2), a pair
+ *            rotated when |L_pq| > 2^-54 sqrt(|L_pp L_qq|), until a sweep rotates nothing (16 sweeps at most);
+ *        w_m <- |t . a_m|;  new_cost = sum_m w_m (the unfloored weights);
+ *        delta = max(|cost - new_cost|, 1 - t.t);  inner <- inner + 1 if delta <= 1e-5, else 0;  cost <- new_cost.
+ *   4. sign         with Rrel = R2 R1^T, d1 = f1_m, d2 = Rrel^T f2_m a match lies in front of both cameras when
+ *        d2.d2 d1.t - d1.d2 d2.t > 0  and  d1.d2 d1.t - d1.d1 d2.t > 0;   t is negated unless more than n / 2 (integer division) do.
+ *      (When neither t nor -t has such a majority -- a pair whose fit went wrong -- the result is the negated eigenvector, whose sign
+ *      is the eigen-solver's choice; the reference has the same gap.  The Jacobi solve is deterministic, so the bytes still repeat.)
+ * The sums run in a fixed order (lane l of a 64-lane wavefront adds matches l, l + 64, ..., then an xor-butterfly), and an edge's result
+ * depends on that edge's data alone: two calls return the same bytes, and reordering the edges reorders the outputs bit for bit.
+ * rel_t_out (n_edges x 3): the unit vector t, to be stored as the pair's position_2.  status_out per edge:
+ *   0  refined;
+ *   1  skipped: fewer than 2 matches; rel_t_out = rel_t_in, 0 iterations, cost 0;
+ *   2  a non-finite result (the trace of L is not a positive finite number in some iteration -- all-zero constraints, non-finite
+ *      input -- or t or the cost is not finite at the end); rel_t_out = rel_t_in, cost 0, iters_out = the iterations completed.
+ * iters_out (iterations of step 3), cost_out (the final cost of step 3), kernel_ms (device time of the kernel) may be NULL.  matches:
+ * match_ptr[n_edges] rows of x1 y1 x2 y2 in pixels (may be NULL when there are none).  Device memory 56 B per match + O(n_edges + n_cams).
+ * Arguments are checked on the host before any device call (GSFM_ERR_INVALID_ARG: a NULL required pointer, a camera index >= n_cams, a
+ * match_ptr that decreases); without a device GSFM_ERR_NO_DEVICE: there is no host fallback.  No edges: GSFM_OK. */
+gsfm_status gsfm_pos_refine_relative_translations(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j,
+                                                  const uint64_t* match_ptr, const double* matches, const double* intrinsics,
+                                                  const double* rot_aa, const double* rel_t_in, double* rel_t_out, int32_t* status_out,
+                                                  int32_t* iters_out, double* cost_out, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
