@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """The reference's scripts/sfm_pipeline.py 1DSfM branch through step 7: rotations, FilterRotations(), OptimizePairwiseTranslations() (every
 pair's position_2 refined with the estimated rotations), FilterRelativeTranslation() (the 1DSfM filter), then camera positions
-(EstimatePosition(HuberLoss(0.1), PositionErrorType.BASELINE) there; NonlinearPositionEstimator.EstimatePositions here) and the PLY
-with the estimated camera positions.
+(EstimatePosition(HuberLoss(0.1), PositionErrorType.BASELINE) there; NonlinearPositionEstimator.EstimatePositions here), then
+EstimateStructure() (every track triangulated and gated, without the per-track refinement) and the PLY with the estimated tracks' points
+and the estimated camera positions.
 usage: position_pipeline.py <dataset_dir with EGs.txt, cc.txt> [flags.yaml]"""
 import os
 import sys
@@ -32,6 +33,7 @@ def position_pipeline(dataset_dir, flagfile=None):
     assert estimator.EstimatePositions(graph.GetAllEdges(), solver.orientations, positions, HuberLoss(0.1),
                                        sfm.PositionErrorType.BASELINE), estimator.LastError()
     sfm.SetReconstructionFromEstimatedPoses(solver.orientations, positions, scene)
+    solver.EstimateStructure()        # a dataset without tracks.txt has nothing to triangulate
     return scene, estimator
 
 
@@ -40,4 +42,5 @@ if __name__ == "__main__":
     scene, estimator = position_pipeline(dataset, sys.argv[2] if len(sys.argv) > 2 else None)
     print("estimated %d positions (view %d held at the origin); solver summary: %s"
           % (len(scene.EstimatedPositions()), estimator.FixedView(), estimator.LastSummary()))
+    print("estimated %d of %d tracks" % (scene.NumEstimatedTracks(), scene.NumTracks()))
     sfm.WritePlyFile(os.path.join(dataset, "positions_out.ply"), scene, 2)

@@ -250,6 +250,7 @@ def load_library():
     lib.gsfm_magsac_table.argtypes = [C.c_int32, _DP, C.c_int32]; lib.gsfm_magsac_table.restype = C.c_int32
     lib.gsfm_magsac_constants.argtypes = [C.c_int32, _DP, _DP, _DP]; lib.gsfm_magsac_constants.restype = C.c_int
     declare_position_signatures(lib)
+    declare_track_signatures(lib)
     _lib = lib
     return lib
 
@@ -276,3 +277,13 @@ def declare_position_signatures(lib):
     lib.gsfm_pos_refine_relative_translations.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, C.POINTER(C.c_uint64), _DP, _DP, _DP, _DP, _DP,
                                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), _DP, _DP]
     lib.gsfm_pos_refine_relative_translations.restype = C.c_int
+
+
+def declare_track_signatures(lib):
+    """include/gsfm_tracks.h"""
+    u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    lib.gsfm_tracks_triangulate.argtypes = [C.c_uint32, _DP, _DP, _DP, C.POINTER(C.c_uint8), C.c_uint64, u64p, _U32P, _DP, C.c_double, C.c_double,
+                                            _DP, i32p, i32p, _DP, u64p, _DP]
+    lib.gsfm_tracks_triangulate.restype = C.c_int
+    lib.gsfm_tracks_launch_order.argtypes = [C.c_uint64, u64p, _U32P, u64p]
+    lib.gsfm_tracks_launch_order.restype = C.c_int

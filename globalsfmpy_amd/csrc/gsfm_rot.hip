@@ -13,6 +13,7 @@
 #include "solver_pos.hpp"
 #include "trans_filter.hpp"
 #include "trans_refine.hpp"
+#include "triangulate.hpp"
 
 // =============================================================================================
 extern "C" {
@@ -411,6 +412,33 @@ gsfm_status gsfm_pos_refine_relative_translations(uint32_t n_cams, uint64_t n_ed
   } catch (const std::exception& e) {
     return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the translation refinement ran out of host resources: ") + e.what());
   }
+}
+
+gsfm_status gsfm_tracks_triangulate(uint32_t n_cams, const double* rot_aa, const double* cam_pos, const double* intrinsics,
+                                    const uint8_t* cam_estimated, uint64_t n_tracks, const uint64_t* track_ptr, const uint32_t* obs_cam,
+                                    const double* obs_xy, double min_triangulation_angle_degrees, double max_reprojection_error_pixels,
+                                    double* point_out, int32_t* status_out, int32_t* n_views_out, double* mean_sq_err_out,
+                                    uint64_t* counts_out, double* kernel_ms) {
+  // (a host vector of O(n_tracks): an exception must not cross the C boundary)
+  try {
+    return tri_impl(n_cams, rot_aa, cam_pos, intrinsics, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy, min_triangulation_angle_degrees,
+                    max_reprojection_error_pixels, point_out, status_out, n_views_out, mean_sq_err_out, counts_out, kernel_ms);
+  } catch (const std::exception& e) {
+    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the track triangulation ran out of host resources: ") + e.what());
+  }
+}
+
+gsfm_status gsfm_tracks_launch_order(uint64_t n_tracks, const uint64_t* track_ptr, uint32_t* order_out, uint64_t* class_begin_out) {
+  if (!class_begin_out || (n_tracks > 0 && (!track_ptr || !order_out))) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
+  if (n_tracks >= (1ull << 31)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "problem too large (2^31 tracks)");
+  for (uint64_t t = 0; t < n_tracks; ++t)
+    if (track_ptr[t + 1] < track_ptr[t]) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "track_ptr decreases at track " + std::to_string(t));
+  try {
+    tri_bucket(n_tracks, track_ptr, order_out, class_begin_out);
+  } catch (const std::exception& e) {   // (stable_sort's buffer)
+    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the launch order ran out of host resources: ") + e.what());
+  }
+  return GSFM_OK;
 }
 
 int64_t gsfm_rot_count_components(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j) {

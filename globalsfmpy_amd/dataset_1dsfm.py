@@ -90,6 +90,52 @@ def write_synthetic_dataset(path, n_cams=12, n_points=600, seed=0, p_visible=0.6
             "edges": [e for e in edges if e[0] < n_cams and e[1] < n_cams], "num_tracks": len(tracks)}
 
 
+def write_tracks_dataset(path, g, min_common=1):
+    """The scene of synth.make_tracks (cameras, tracks, pixels) in 1DSfM format: every camera is a view with an EXIF focal in list.txt and
+    its principal point in the coords.txt header, every observation a keypoint of its view, every track a line of tracks.txt; EGs.txt holds
+    the exact relative pose of every view pair that shares at least `min_common` tracks.  A track must not see a view twice (track lengths
+    up to n_cams).  Returns {"keypoint": per observation its (view, keypoint index)}."""
+    os.makedirs(path, exist_ok=True)
+    n = g["n_cams"]
+    ptr = g["track_ptr"].astype(np.int64)
+    count = np.zeros(n, dtype=np.int64)
+    key = np.empty(len(g["obs_cam"]), dtype=np.int64)
+    for k, c in enumerate(g["obs_cam"]):
+        key[k] = count[c]
+        count[c] += 1
+    with open(os.path.join(path, "cc.txt"), "w") as f:
+        f.write("\n".join(str(k) for k in range(n)) + "\n")
+    with open(os.path.join(path, "list.txt"), "w") as f:
+        for k in range(n):
+            f.write("images/img%04d.jpg 0 %.17g\n" % (k, g["intrinsics"][k, 0]))
+    with open(os.path.join(path, "coords.txt"), "w") as f:
+        for k in range(n):
+            f.write("#index = %d, name = img%04d.jpg, keys = %d, px = %.1f, py = %.1f, focal = %.3f\n"
+                    % (k, k, count[k], g["intrinsics"][k, 1], g["intrinsics"][k, 2], g["intrinsics"][k, 0]))
+            for i, o in enumerate(np.flatnonzero(g["obs_cam"] == k)):
+                f.write("%d %.17g %.17g 0 0 128 128 128\n" % (i, g["obs_xy"][o, 0], g["obs_xy"][o, 1]))
+    common = {}
+    with open(os.path.join(path, "tracks.txt"), "w") as f:
+        f.write("%d\n" % (len(ptr) - 1))
+        for t in range(len(ptr) - 1):
+            obs = range(ptr[t], ptr[t + 1])
+            views = [int(g["obs_cam"][o]) for o in obs]
+            if len(set(views)) != len(views):
+                raise ValueError("track %d sees a view twice" % t)
+            f.write("%d %s\n" % (len(views), " ".join("%d %d" % (g["obs_cam"][o], key[o]) for o in obs)))
+            for a in views:
+                for b in views:
+                    if a < b:
+                        common[(a, b)] = common.get((a, b), 0) + 1
+    R = synth.aa_to_matrix(g["rot_aa"])
+    with open(os.path.join(path, "EGs.txt"), "w") as f:
+        for (i, j) in sorted(k for k, c in common.items() if c >= min_common):
+            pos = R[i] @ (g["cam_pos"][j] - g["cam_pos"][i])
+            Rf, tf = _S @ (R[j] @ R[i].T).T @ _S, _S @ (pos / np.linalg.norm(pos))     # the reader applies R' = S R_file^T S, t' = S t_file
+            f.write("%d %d %s %s\n" % (i, j, " ".join("%.17g" % v for v in Rf.ravel()), " ".join("%.17g" % v for v in tf)))
+    return {"keypoint": np.c_[g["obs_cam"].astype(np.int64), key]}
+
+
 def read_edge_matches(path):
     """numpy restatement of the host's Read1DSFMTracks + CollectEdgeMatches: per edge of EGs.txt (inside cc.txt, sorted by
     key) the matched features of the common tracks, the intrinsics (EXIF focal else 1.2 px) and rotation_2 / position_2."""

@@ -9,9 +9,11 @@
 #include <cstring>
 #include <fstream>
 #include <sstream>
+#include <stdexcept>
 
 #include "../../include/gsfm/view_graph.hpp"
 #include "../../include/gsfm_rot.h"
+#include "../../include/gsfm_tracks.h"
 
 namespace gsfm {
 
@@ -172,6 +174,87 @@ void CollectEdgeMatches(const Tracks1DSfM& tr, const theia::ViewGraph& vg, EdgeM
     for (int k = 0; k < 3; ++k) { out->rotation[3 * e + k] = info.rotation_2[k]; out->position[3 * e + k] = info.position_2[k]; }
   }
 }
+
+#ifndef GSFM_USE_REAL_THEIA
+void FlattenTracks(const theia::Reconstruction& rec, FlatTracks* out) {
+  *out = FlatTracks();
+  if (!rec.tracks) return;
+  const Tracks1DSfM& tr = *rec.tracks;
+  for (const auto& kv : tr.keypoints) out->views.push_back(kv.first);
+  std::sort(out->views.begin(), out->views.end());
+  const size_t N = out->views.size();
+  out->rot_aa.assign(3 * N, 0.0); out->cam_pos.assign(3 * N, 0.0); out->intrinsics.assign(3 * N, 0.0);
+  out->cam_estimated.assign(N, 0);
+  std::unordered_map<theia::ViewId, uint32_t> index;
+  for (size_t c = 0; c < N; ++c) {
+    const theia::ViewId v = out->views[c];
+    index[v] = (uint32_t)c;
+    const auto pp = tr.principal_point.find(v);
+    const auto fo = tr.focal.find(v);
+    const double u = pp == tr.principal_point.end() ? 0.0 : pp->second[0], w = pp == tr.principal_point.end() ? 0.0 : pp->second[1];
+    double f = fo == tr.focal.end() ? 0.0 : fo->second;
+    if (f == 0.0) f = 1.2 * u;
+    out->intrinsics[3 * c] = f; out->intrinsics[3 * c + 1] = u; out->intrinsics[3 * c + 2] = w;
+    const auto o = rec.orientation.find(v);
+    const auto p = rec.position.find(v);
+    if (!rec.views.count(v) || o == rec.orientation.end() || p == rec.position.end()) continue;
+    out->cam_estimated[c] = 1;
+    for (int k = 0; k < 3; ++k) { out->rot_aa[3 * c + k] = o->second[k]; out->cam_pos[3 * c + k] = p->second[k]; }
+  }
+  out->track_ptr.assign(1, 0);
+  for (const auto& t : tr.tracks) {
+    for (const auto& ob : t) {
+      const Eigen::Vector2d& xy = tr.keypoints.at(ob.first)[ob.second];
+      out->obs_cam.push_back(index.at(ob.first));
+      out->obs_xy.push_back(xy[0]); out->obs_xy.push_back(xy[1]);
+    }
+    out->track_ptr.push_back(out->obs_cam.size());
+  }
+}
+
+EstimateStructureStats EstimateStructure(double min_angle_degrees, double max_error_pixels, theia::Reconstruction* rec) {
+  EstimateStructureStats stats;
+  if (!rec->tracks || rec->tracks->tracks.empty()) return stats;   // a dataset without tracks.txt: nothing to triangulate
+  FlatTracks f;
+  FlattenTracks(*rec, &f);
+  const size_t T = f.track_ptr.size() - 1;
+  std::vector<double> point(3 * T, 0.0);
+  std::vector<int32_t> status(T, 0);
+  const gsfm_status st = gsfm_tracks_triangulate((uint32_t)f.views.size(), f.rot_aa.data(), f.cam_pos.data(), f.intrinsics.data(), f.cam_estimated.data(), T,
+                                                 f.track_ptr.data(), f.obs_cam.data(), f.obs_xy.data(), min_angle_degrees, max_error_pixels, point.data(),
+                                                 status.data(), nullptr, nullptr, stats.counts, &stats.kernel_ms);
+  if (st != GSFM_OK) throw std::runtime_error(std::string("EstimateStructure: ") + gsfm_last_error());
+  rec->track_point.assign(T, Eigen::Vector3d());
+  rec->track_estimated.assign(T, 0);
+  for (size_t t = 0; t < T; ++t) {
+    rec->track_point[t] = Eigen::Vector3d(point[3 * t], point[3 * t + 1], point[3 * t + 2]);   // Theia leaves a rejected track's point in place too
+    rec->track_estimated[t] = status[t] == 0;
+  }
+  stats.num_tracks = T;
+  stats.num_estimated = (size_t)stats.counts[0];
+  return stats;
+}
+
+bool WritePlyFile(const std::string& ply_file, const theia::Reconstruction& rec, int min_num_observations_per_point) {
+  std::ofstream f(ply_file);
+  if (!f.is_open()) return false;
+  std::vector<size_t> tracks;
+  for (size_t t = 0; t < rec.track_estimated.size(); ++t)
+    if (rec.track_estimated[t] && rec.tracks && (int)rec.tracks->tracks[t].size() >= min_num_observations_per_point) tracks.push_back(t);
+  size_t n = tracks.size();
+  for (const auto& kv : rec.orientation) n += rec.views.count(kv.first);
+  f << "ply\nformat ascii 1.0\nelement vertex " << n
+    << "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header" << std::endl;
+  for (size_t t : tracks) f << rec.track_point[t][0] << " " << rec.track_point[t][1] << " " << rec.track_point[t][2] << " 0 0 0\n";
+  for (const auto& kv : rec.orientation) {
+    if (!rec.views.count(kv.first)) continue;
+    auto it = rec.position.find(kv.first);
+    if (it == rec.position.end()) f << "0 0 0 0 255 0\n";
+    else f << it->second[0] << " " << it->second[1] << " " << it->second[2] << " 0 255 0\n";
+  }
+  return (bool)f;
+}
+#endif
 
 bool StoreCovarianceRot(const std::string& dir, const EdgeMatches& all, const theia::ViewGraph& vg, CovarianceMap* cov_out,
                         CalcCovarianceStats* stats, std::string* error) {
@@ -353,3 +436,10 @@ std::vector<std::string> ExpandWildcard(const std::string& pattern) {
 }
 
 }  // namespace gsfm
+
+#ifndef GSFM_USE_REAL_THEIA
+namespace theia {
+int Reconstruction::NumTracks() const { return tracks ? (int)tracks->tracks.size() : 0; }
+int Reconstruction::NumEstimatedTracks() const { return (int)std::count(track_estimated.begin(), track_estimated.end(), (uint8_t)1); }
+}  // namespace theia
+#endif

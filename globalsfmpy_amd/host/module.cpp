@@ -112,6 +112,9 @@ struct ReconstructionEstimatorOptions {
   bool filter_relative_translations_with_1dsfm = true;       // :143
   int translation_filtering_num_iterations = 48;             // :146
   double translation_filtering_projection_tolerance = 0.1;   // :149
+  double min_triangulation_angle_degrees = 4.0;              // :278
+  double triangulation_max_reprojection_error_in_pixels = 15.0;   // :281
+  bool bundle_adjust_tracks = true;                          // :284; read, and NOT honoured: EstimateStructure() does not refine tracks
 };
 struct ReconstructionBuilderOptions {
   int num_threads = 1;
@@ -228,6 +231,14 @@ class GlobalReconstructionEstimator {
     }
     for (ViewId v : RemoveDisconnectedViewPairs(view_graph_)) orientations_.erase(v);
   }
+  // :621-636 with bundle_adjustment = false whatever options_.bundle_adjust_tracks says: every track triangulated by the midpoint method and
+  // gated on angle and reprojection error, over the views SetReconstructionFromEstimatedPoses marked, in one device call
+  gsfm::EstimateStructureStats EstimateStructure() {
+    if (!reconstruction_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
+    structure_ = gsfm::EstimateStructure(options_.min_triangulation_angle_degrees, options_.triangulation_max_reprojection_error_in_pixels, reconstruction_);
+    return structure_;
+  }
+  gsfm::EstimateStructureStats structure_;
   ReconstructionEstimatorOptions options_;
   ViewGraph* view_graph_ = nullptr;
   Reconstruction* reconstruction_ = nullptr;
@@ -239,6 +250,19 @@ class GlobalReconstructionEstimator {
 py::dict refine_stats_dict(const RefineRelativeTranslationsStats& st) {
   py::dict d;
   d["num_refined"] = st.num_refined; d["num_skipped"] = st.num_skipped; d["num_nonfinite"] = st.num_nonfinite; d["kernel_ms"] = st.kernel_ms;
+  return d;
+}
+
+py::dict structure_dict(const gsfm::EstimateStructureStats& st, bool bundle_adjust_tracks) {
+  py::dict d;
+  d["num_tracks"] = st.num_tracks; d["num_estimated"] = st.num_estimated; d["kernel_ms"] = st.kernel_ms;
+  d["counts"] = std::vector<uint64_t>(st.counts, st.counts + 6);
+  d["num_bad_angles"] = st.counts[1] + st.counts[2];                    // what Theia's log calls them
+  d["num_failed_triangulations"] = st.counts[3];
+  d["num_bad_reprojections"] = st.counts[4] + st.counts[5];
+  d["tracks_refined"] = false;
+  d["bundle_adjust_tracks_requested"] = bundle_adjust_tracks;
+  d["note"] = "tracks triangulated without per-track refinement (bundle_adjust_tracks is not honoured)";
   return d;
 }
 
@@ -265,6 +289,9 @@ void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions
   get("post_rotation_filtering_degrees", options.reconstruction_estimator_options.rotation_filtering_max_difference_degrees);
   get("refine_relative_translations_after_rotation_estimation", options.reconstruction_estimator_options.refine_relative_translations_after_rotation_estimation);
   get("filter_relative_translations_with_1dsfm", options.reconstruction_estimator_options.filter_relative_translations_with_1dsfm);
+  get("min_triangulation_angle_degrees", options.reconstruction_estimator_options.min_triangulation_angle_degrees);
+  get("triangulation_reprojection_error_pixels", options.reconstruction_estimator_options.triangulation_max_reprojection_error_in_pixels);
+  get("bundle_adjust_tracks", options.reconstruction_estimator_options.bundle_adjust_tracks);
 }
 
 }  // namespace
@@ -347,7 +374,10 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def_readwrite("refine_relative_translations_after_rotation_estimation", &ReconstructionEstimatorOptions::refine_relative_translations_after_rotation_estimation)
       .def_readwrite("filter_relative_translations_with_1dsfm", &ReconstructionEstimatorOptions::filter_relative_translations_with_1dsfm)
       .def_readwrite("translation_filtering_num_iterations", &ReconstructionEstimatorOptions::translation_filtering_num_iterations)
-      .def_readwrite("translation_filtering_projection_tolerance", &ReconstructionEstimatorOptions::translation_filtering_projection_tolerance);
+      .def_readwrite("translation_filtering_projection_tolerance", &ReconstructionEstimatorOptions::translation_filtering_projection_tolerance)
+      .def_readwrite("min_triangulation_angle_degrees", &ReconstructionEstimatorOptions::min_triangulation_angle_degrees)
+      .def_readwrite("triangulation_max_reprojection_error_in_pixels", &ReconstructionEstimatorOptions::triangulation_max_reprojection_error_in_pixels)
+      .def_readwrite("bundle_adjust_tracks", &ReconstructionEstimatorOptions::bundle_adjust_tracks);
   py::class_<ReconstructionBuilderOptions>(m, "ReconstructionBuilderOptions")
       .def(py::init<>())
       .def_readwrite("num_threads", &ReconstructionBuilderOptions::num_threads)
@@ -358,6 +388,41 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def(py::init<>())
       .def("NumTracks", &Reconstruction::NumTracks)
       .def("NumViews", &Reconstruction::NumViews)
+      .def("NumEstimatedTracks", &Reconstruction::NumEstimatedTracks)
+      // a track is addressed by its index in tracks.txt (Theia's TrackId of a 1DSfM dataset); Track(id)->Point(), IsEstimated(), NumViews()
+      .def("TrackPoint", [](const Reconstruction& r, size_t t) {
+        if (t >= (size_t)r.NumTracks()) throw py::index_error("no such track");
+        return t < r.track_point.size() ? r.track_point[t] : Eigen::Vector3d();
+      })
+      .def("TrackIsEstimated", [](const Reconstruction& r, size_t t) {
+        if (t >= (size_t)r.NumTracks()) throw py::index_error("no such track");
+        return t < r.track_estimated.size() && r.track_estimated[t] != 0;
+      })
+      .def("TrackNumViews", [](const Reconstruction& r, size_t t) {
+        if (t >= (size_t)r.NumTracks()) throw py::index_error("no such track");
+        return (int)r.tracks->tracks[t].size();
+      })
+      .def("EstimatedTrackIds", [](const Reconstruction& r) {
+        std::vector<size_t> ids;
+        for (size_t t = 0; t < r.track_estimated.size(); ++t) if (r.track_estimated[t]) ids.push_back(t);
+        return ids;
+      })
+      // the flat arrays EstimateStructure() hands to gsfm_tracks_triangulate (solver.triangulate_tracks takes the same)
+      .def("FlattenedTracks", [](const Reconstruction& r) -> py::object {
+        if (!r.tracks) return py::none();
+        gsfm::FlatTracks f;
+        gsfm::FlattenTracks(r, &f);
+        auto arr = [](const auto& v, py::ssize_t cols) {
+          using T = typename std::decay_t<decltype(v)>::value_type;
+          py::array_t<T> a = cols > 1 ? py::array_t<T>({(py::ssize_t)(v.size() / cols), cols}) : py::array_t<T>((py::ssize_t)v.size());
+          if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
+          return a;
+        };
+        py::dict d;
+        d["views"] = arr(f.views, 1); d["rot_aa"] = arr(f.rot_aa, 3); d["cam_pos"] = arr(f.cam_pos, 3); d["intrinsics"] = arr(f.intrinsics, 3);
+        d["cam_estimated"] = arr(f.cam_estimated, 1); d["track_ptr"] = arr(f.track_ptr, 1); d["obs_cam"] = arr(f.obs_cam, 1); d["obs_xy"] = arr(f.obs_xy, 2);
+        return d;
+      })
       .def("EstimatedOrientations", [](const Reconstruction& r) { return r.orientation; })
       .def("EstimatedPositions", [](const Reconstruction& r) { return r.position; })
       .def("ViewNames", [](const Reconstruction& r) { return r.view_names; })
@@ -426,6 +491,12 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
         return refine_stats_dict(st);
       })
       .def("FilterRelativeTranslation", &GlobalReconstructionEstimator::FilterRelativeTranslation, py::call_guard<py::gil_scoped_release>())
+      .def("EstimateStructure", [](GlobalReconstructionEstimator& e) {
+        gsfm::EstimateStructureStats st;
+        { py::gil_scoped_release release; st = e.EstimateStructure(); }
+        return structure_dict(st, e.options_.bundle_adjust_tracks);
+      })
+      .def("LastStructureSummary", [](const GlobalReconstructionEstimator& e) { return structure_dict(e.structure_, e.options_.bundle_adjust_tracks); })
       .def("LastSummary", [](const GlobalReconstructionEstimator& e) { return summary_dict(e.summary_); })
       .def("LastError", [](const GlobalReconstructionEstimator& e) { return e.error_; });
 
@@ -439,6 +510,9 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       gsfm::CollectEdgeMatches(tracks, *vg, em.get());
       rec->matches = em;
       for (const auto& kv : tracks.names) if (rec->views.count(kv.first)) rec->view_names[kv.first] = kv.second;
+      rec->track_point.clear();
+      rec->track_estimated.clear();
+      rec->tracks = std::make_shared<gsfm::Tracks1DSfM>(std::move(tracks));   // kept for EstimateStructure()
     }
     for (ViewId v : rec->views) if (!rec->view_names.count(v)) rec->view_names[v] = std::to_string(v);  // no list.txt: the id is the name
     gsfm::ReadCovariance(dir, &cov);
@@ -538,24 +612,11 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
     for (const auto& kv : rec.orientation) f << kv.first << " " << kv.second[0] << " " << kv.second[1] << " " << kv.second[2] << "\n";
     return (bool)f;
   });
-  // bind :631 / Theia io/write_ply_file.cc:74-123: tracks (3-D points) and the positions of the estimated views as green vertices.
-  // There are no tracks: the file holds one green vertex per estimated view, at its estimated position where it has one
-  // (SetReconstructionFromEstimatedPoses), else at the origin (a rotation-only reconstruction) -- the header and vertex format of Theia.
-  m.def("WritePlyFile", [](const std::string& ply_file, const Reconstruction& rec, int /*min_num_observations_per_point*/) {
+  // bind :631 / Theia io/write_ply_file.cc:74-123: the estimated tracks' points, then the positions of the estimated views as green
+  // vertices (gsfm::WritePlyFile).  Without an estimated track the file holds the views alone.
+  m.def("WritePlyFile", [](const std::string& ply_file, const Reconstruction& rec, int min_num_observations_per_point) {
     if (ply_file.empty()) throw std::invalid_argument("WritePlyFile: empty file name");
-    std::ofstream f(ply_file);
-    if (!f.is_open()) return false;
-    size_t n = 0;
-    for (const auto& kv : rec.orientation) n += rec.views.count(kv.first);
-    f << "ply\nformat ascii 1.0\nelement vertex " << n
-      << "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header" << std::endl;
-    for (const auto& kv : rec.orientation) {
-      if (!rec.views.count(kv.first)) continue;
-      auto it = rec.position.find(kv.first);
-      if (it == rec.position.end()) f << "0 0 0 0 255 0\n";
-      else f << it->second[0] << " " << it->second[1] << " " << it->second[2] << " 0 255 0\n";
-    }
-    return (bool)f;
+    return gsfm::WritePlyFile(ply_file, rec, min_num_observations_per_point);
   }, py::call_guard<py::gil_scoped_release>());
   // ---- evaluation (bind :387-394, :396-403, :651-664; orientations only) ----
   py::class_<gsfm::CompareInfo>(m, "CompareInfo")

@@ -424,6 +424,60 @@ def refine_relative_translations(n_cams, edge_i, edge_j, match_ptr, matches, int
     return out, {"status": status, "iterations": iters, "cost": cost, "kernel_ms": ms.value}
 
 
+def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated=None, min_triangulation_angle_degrees=4.0,
+                       max_reprojection_error_pixels=15.0):
+    """gsfm_tracks_triangulate: every track triangulated by the midpoint method and gated on triangulation angle and reprojection error
+    (Theia's TrackEstimator::EstimateTrack without the per-track refinement, under the definition of include/gsfm_tracks.h) on the device,
+    a group of 4, 16 or 64 lanes per track.  rot_aa, cam_pos: N x 3; intrinsics: N x 3 (f u v); track_ptr: T + 1 offsets into obs_cam
+    (camera index) and obs_xy (pixels); cam_estimated: N flags or None (all estimated).  The defaults are the reference pipeline's.
+    Returns dict(points T x 3, status (0 estimated, 1 too few views, 2 angle, 3 Cholesky, 4 behind a camera, 5 reprojection error),
+    n_views, mean_sq_err, counts (6), kernel_ms)."""
+    lib = _abi.load_library()
+    rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(-1, 3)
+    n = rot.shape[0]
+    pos = np.ascontiguousarray(cam_pos, dtype=np.float64).reshape(-1, 3)
+    K = np.ascontiguousarray(intrinsics, dtype=np.float64).reshape(-1, 3)
+    tp = np.ascontiguousarray(track_ptr, dtype=np.uint64).reshape(-1)
+    oc = np.ascontiguousarray(obs_cam, dtype=np.uint32).reshape(-1)
+    xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
+    if pos.shape[0] != n or K.shape[0] != n:
+        raise ValueError("rot_aa, cam_pos and intrinsics must describe the same cameras")
+    if tp.shape[0] < 1 or xy.shape[0] != oc.shape[0]:
+        raise ValueError("track_ptr needs n_tracks + 1 entries, and obs_cam and obs_xy one row per observation")
+    T = tp.shape[0] - 1
+    if int(tp.max()) > oc.shape[0]:
+        raise ValueError("track_ptr points past the end of the observations")
+    est = None
+    if cam_estimated is not None:
+        est = np.ascontiguousarray(np.asarray(cam_estimated) != 0, dtype=np.uint8).reshape(-1)
+        if est.shape[0] != n:
+            raise ValueError("cam_estimated needs one flag per camera")
+    points, status, n_views = np.zeros((T, 3)), np.zeros(T, dtype=np.int32), np.zeros(T, dtype=np.int32)
+    err, counts = np.zeros(T), np.zeros(6, dtype=np.uint64)
+    ms = C.c_double(0)
+    i32p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    st = lib.gsfm_tracks_triangulate(n, _dp(rot), _dp(pos), _dp(K), None if est is None else est.ctypes.data_as(C.POINTER(C.c_uint8)), T,
+                                     tp.ctypes.data_as(u64p), _u32p(oc), _dp(xy), float(min_triangulation_angle_degrees),
+                                     float(max_reprojection_error_pixels), _dp(points), status.ctypes.data_as(i32p), n_views.ctypes.data_as(i32p),
+                                     _dp(err), counts.ctypes.data_as(u64p), C.byref(ms))
+    if st != 0:
+        raise SolverError("gsfm_tracks_triangulate failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+    return {"points": points, "status": status, "n_views": n_views, "mean_sq_err": err, "counts": counts, "kernel_ms": ms.value}
+
+
+def track_launch_order(track_ptr):
+    """gsfm_tracks_launch_order (host code): (order, class_begin) -- the tracks by lane class 4, 16, 64, longest first inside a class."""
+    lib = _abi.load_library()
+    tp = np.ascontiguousarray(track_ptr, dtype=np.uint64).reshape(-1)
+    T = tp.shape[0] - 1
+    order, begin = np.zeros(T, dtype=np.uint32), np.zeros(4, dtype=np.uint64)
+    u64p = C.POINTER(C.c_uint64)
+    st = lib.gsfm_tracks_launch_order(T, tp.ctypes.data_as(u64p), _u32p(order), begin.ctypes.data_as(u64p))
+    if st != 0:
+        raise SolverError("gsfm_tracks_launch_order failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+    return order, begin
+
+
 class PositionProblem(ProblemBase):
     """Camera positions from relative translations (include/gsfm_pos.h): the reference's EstimatePositions with BASELINE residuals
     r = (c_j - c_i) / |c_j - c_i| - R(aa_i)^T t_ij on the device.  rel_t: E x 3 position_2 of each view pair (frame of camera i);

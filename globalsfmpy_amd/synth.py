@@ -285,6 +285,54 @@ def make_position_graph(n_cams, n_edges, seed, outlier_frac=0.0, noise=0.0, exte
     return {"n_cams": int(n_cams), "edge_i": ei, "edge_j": ej, "rel_t": rel_t, "rot_aa": rot_aa, "gt_pos": gt, "is_outlier": is_out}
 
 
+def make_tracks(n_cams, n_tracks, seed, lengths=(2, 3, 4, 5, 8, 13), length_weights=None, noise_px=0.5, outlier_frac=0.0, outlier_px=(50.0, 300.0)):
+    """Returns dict(n_cams, rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, gt_points, is_outlier) for track triangulation
+    (include/gsfm_tracks.h): cameras on a ring of radius 9 to 12 looking at a point cloud in the cube [-2, 2]^3 with a little jitter,
+    pinhole intrinsics f u v; every track is one point, its length drawn from `lengths` (with probabilities `length_weights`, uniform when
+    None); the k-th observation of a track is taken by camera sigma[(a + k) mod n_cams], sigma a fixed permutation and a the track's random
+    offset, so a track's cameras are distinct up to n_cams observations and repeat beyond; pixels carry N(0, noise_px^2) noise and a
+    fraction outlier_frac of the observations is moved by outlier_px[0] .. outlier_px[1] pixels in a random direction.  Seeded (PCG64) and
+    vectorised (10 M observations take seconds)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    ang = rng.uniform(0.0, 2.0 * np.pi, n_cams)
+    rad = rng.uniform(9.0, 12.0, n_cams)
+    cam_pos = np.c_[rad * np.sin(ang), rng.uniform(-1.5, 1.5, n_cams), -rad * np.cos(ang)]
+    z = 0.3 * rng.standard_normal((n_cams, 3)) - cam_pos
+    z /= np.linalg.norm(z, axis=1, keepdims=True)
+    x = np.cross(np.array([0.0, 1.0, 0.0]), z)
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    R = np.stack([x, np.cross(z, x), z], axis=1)                       # world -> camera, rows x y z
+    R = quat_to_matrix(aa_to_quat(0.05 * rng.standard_normal((n_cams, 3)))) @ R
+    rot_aa = np.ascontiguousarray(quat_to_aa(matrix_to_quat(R)))
+    intrinsics = np.c_[rng.uniform(900.0, 1500.0, n_cams), rng.integers(500, 700, n_cams).astype(np.float64),
+                       rng.integers(350, 450, n_cams).astype(np.float64)]
+    lengths = np.asarray(lengths, dtype=np.int64)
+    length = lengths[rng.choice(lengths.size, size=n_tracks, p=length_weights)]
+    track_ptr = np.concatenate([[0], np.cumsum(length)]).astype(np.uint64)
+    n_obs = int(track_ptr[-1])
+    gt = rng.uniform(-2.0, 2.0, (n_tracks, 3))
+    sigma = rng.permutation(n_cams)
+    offset = rng.integers(0, n_cams, n_tracks)
+    track_of = np.repeat(np.arange(n_tracks, dtype=np.int64), length)
+    place = np.arange(n_obs, dtype=np.int64) - np.repeat(track_ptr[:-1].astype(np.int64), length)
+    obs_cam = sigma[(offset[track_of] + place) % n_cams].astype(np.uint32)
+    Rm = aa_to_matrix(rot_aa)                                            # what a consumer of rot_aa computes
+    obs_xy = np.empty((n_obs, 2))
+    for b0 in range(0, n_obs, 1 << 21):
+        sl = slice(b0, min(n_obs, b0 + (1 << 21)))
+        c = obs_cam[sl]
+        p = np.einsum("eij,ej->ei", Rm[c], gt[track_of[sl]] - cam_pos[c])
+        obs_xy[sl] = intrinsics[c, :1] * p[:, :2] / p[:, 2:] + intrinsics[c, 1:]
+    obs_xy += noise_px * rng.standard_normal((n_obs, 2))
+    is_out = rng.random(n_obs) < outlier_frac
+    k = int(is_out.sum())
+    if k:
+        th, r = rng.uniform(0.0, 2.0 * np.pi, k), rng.uniform(outlier_px[0], outlier_px[1], k)
+        obs_xy[is_out] += np.c_[r * np.cos(th), r * np.sin(th)]
+    return {"n_cams": int(n_cams), "rot_aa": rot_aa, "cam_pos": cam_pos, "intrinsics": intrinsics, "track_ptr": track_ptr, "obs_cam": obs_cam,
+            "obs_xy": obs_xy, "gt_points": gt, "is_outlier": is_out}
+
+
 def gauge_normalize(pos, fixed_cam):
     """Positions with translation and scale removed: subtract the fixed camera, divide by the RMS distance from it."""
     p = np.asarray(pos, dtype=np.float64) - np.asarray(pos, dtype=np.float64)[fixed_cam]

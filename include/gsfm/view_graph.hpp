@@ -12,7 +12,7 @@
 
 #include "compat.hpp"
 
-namespace gsfm { struct EdgeMatches; }
+namespace gsfm { struct EdgeMatches; struct Tracks1DSfM; }
 
 namespace theia {
 
@@ -55,7 +55,13 @@ class Reconstruction {
   // (get_matched_features, src/uncertainty.cpp:3-33).  Set by Read1DSFM (when tracks.txt exists) and by
   // AddColmapMatchesToReconstructionBuilder.
   std::shared_ptr<const gsfm::EdgeMatches> matches;
-  int NumTracks() const { return 0; }
+  // The keypoints and tracks of a 1DSfM dataset (Read1DSFM, when tracks.txt exists), and per track of them what EstimateStructure
+  // stored: the triangulated point and whether the track is estimated (both empty until then).
+  std::shared_ptr<const gsfm::Tracks1DSfM> tracks;
+  std::vector<Eigen::Vector3d> track_point;
+  std::vector<uint8_t> track_estimated;
+  int NumTracks() const;
+  int NumEstimatedTracks() const;
   int NumViews() const { return (int)views.size(); }
 };
 #endif
@@ -139,6 +145,37 @@ struct EdgeMatches {
   std::vector<double> rotation, position;
 };
 void CollectEdgeMatches(const Tracks1DSfM& tracks, const theia::ViewGraph& view_graph, EdgeMatches* out);
+
+#ifndef GSFM_USE_REAL_THEIA
+// ---- EstimateStructure without the per-track refinement (src/GSfM_global_reconstruction_estimator.cpp:621-636 -> Theia's
+// TrackEstimator with bundle_adjustment = false), on the device: gsfm_tracks_triangulate under the definition of include/gsfm_tracks.h ----
+// The reconstruction's tracks as that entry point takes them.  Cameras: every view that has keypoints, ascending by view id; a camera is
+// estimated when the reconstruction holds an orientation AND a position for it (SetReconstructionFromEstimatedPoses), others carry zeros.
+// Intrinsics f u v: the EXIF focal of list.txt, else 1.2 x the principal point's x (the rule of CollectEdgeMatches), and the principal
+// point of coords.txt.  Tracks and their observations in the order of tracks.txt.
+struct FlatTracks {
+  std::vector<theia::ViewId> views;                  // camera index -> view id
+  std::vector<double> rot_aa, cam_pos, intrinsics;   // 3 per camera
+  std::vector<uint8_t> cam_estimated;
+  std::vector<uint64_t> track_ptr;
+  std::vector<uint32_t> obs_cam;
+  std::vector<double> obs_xy;
+};
+void FlattenTracks(const theia::Reconstruction& reconstruction, FlatTracks* out);
+struct EstimateStructureStats {
+  size_t num_tracks = 0, num_estimated = 0;
+  uint64_t counts[6] = {0, 0, 0, 0, 0, 0};           // tracks per status of gsfm_tracks_triangulate
+  double kernel_ms = 0.0;
+};
+// One call of gsfm_tracks_triangulate over all tracks; stores point and estimated flag per track in the reconstruction.  A reconstruction
+// without tracks is left alone.  Throws std::runtime_error when no device is usable (there is no CPU fallback) or the device call fails.
+EstimateStructureStats EstimateStructure(double min_triangulation_angle_degrees, double max_reprojection_error_pixels,
+                                         theia::Reconstruction* reconstruction);
+// Theia's io/write_ply_file.cc: the points of the estimated tracks with at least min_num_observations_per_point views (no colour: 0 0 0;
+// ascending track index where Theia walks a hash set), then the estimated views' positions in green.  A view without a position is
+// written at the origin (a rotation-only reconstruction).  Returns false when the file cannot be written.
+bool WritePlyFile(const std::string& ply_file, const theia::Reconstruction& reconstruction, int min_num_observations_per_point);
+#endif
 
 // two_views.txt of scripts/read_colmap_database.py:52-133 as AddColmapMatchesToReconstructionBuilder reads it
 // (src/read_colmap_posegraph.cpp:55-164): three header lines, then per pair

@@ -1,0 +1,78 @@
+/* gsfm_tracks.h -- C ABI of track triangulation on the GPU (libgsfm_rot.so).
+ *
+ * Restates Theia's TrackEstimator::EstimateTrack (sfm/estimate_track.cc) with bundle_adjustment = false, the step behind the reference
+ * pipeline's reconstruction_estimator.EstimateStructure(): gather a track's observations in estimated views, require a sufficient
+ * triangulation angle, triangulate by the midpoint method (triangulation/triangulation.cc: TriangulateMidpoint,
+ * SufficientTriangulationAngle), and gate the point on its reprojection error.  The per-track refinement (BundleAdjustTrack) is NOT part
+ * of this entry.  Flat arrays in, flat arrays out; every track is an independent small problem in fp64.
+ *
+ * Cameras (n_cams): rot_aa (n_cams x 3 angle-axis, world -> camera, R = Ceres' AngleAxisToRotationMatrix), cam_pos (n_cams x 3, the
+ * camera centre in the world), intrinsics (n_cams x 3: f u v, the pinhole model of gsfm_cov_estimate and of the translation refinement),
+ * cam_estimated (n_cams bytes, non-zero = estimated; NULL = every camera is estimated).
+ * Tracks (n_tracks): CSR track_ptr[n_tracks + 1] (track_ptr[0] = 0, non-decreasing), obs_cam[n_obs] (camera index of an observation),
+ * obs_xy[n_obs x 2] (pixels), n_obs = track_ptr[n_tracks].
+ *
+ * Per track, over its observations whose camera is estimated, in the order given (n of them; the others are skipped everywhere):
+ *   1. ray        r = R^T ((x - u) / f, (y - v) / f, 1),  d = r / |r|,  origin o = cam_pos.
+ *   2. n < 2      status 1.
+ *   3. angle      c = cos(min_triangulation_angle_degrees pi / 180), computed once on the host in fp64.  The track passes when some pair
+ *                 i < j has d_i . d_j < c; otherwise status 2.  A NaN compares false.
+ *   4. midpoint   M = sum (I - d d^T),  q = sum (I - d d^T) o = sum (o - d (d . o));  M X = q by a 3 x 3 Cholesky M = L L^T (pivots
+ *                 M00, M11 - L10^2, M22 - L20^2 - L21^2; forward then backward substitution).  A pivot that is not positive or not
+ *                 finite gives status 3.  Theia solves the 4 x 4 homogeneous system A X~ = b; its last row and column are
+ *                 (0, 0, 0, n | n), so the homogeneous coordinate is exactly 1 and the 3 x 3 system above is the same point.  (With
+ *                 finite input the angle test rejects every track whose M is singular, so status 3 is there for completeness.)
+ *   5. gate       per observation p = R (X - o).  Any p_z < 0: status 4.  Else with the reprojection (f p_x / p_z + u, f p_y / p_z + v)
+ *                 the track is accepted, status 0, when the mean over the n observations of the squared pixel error is
+ *                 < max_reprojection_error_pixels^2; anything else is status 5 (a NaN mean and p_z = 0 included).
+ *                 Theia's Camera::ProjectPoint returns the depth p_z / X~_3 = p_z and the track is rejected on a return value < 0: the
+ *                 same rule; p_z = 0 passes Theia's depth test too and fails on the infinite or NaN mean, as here.  Theia stops at the
+ *                 first observation behind its camera; the result does not depend on which one that is.  Departure that decides nothing
+ *                 at the tolerances of interest: Theia rotates with AngleAxisRotatePoint, here p is formed with the matrix R.
+ * status_out per track:  0 estimated;  1 fewer than 2 observations in estimated views;  2 insufficient triangulation angle;
+ *   3 the Cholesky failed;  4 the point lies behind a camera;  5 reprojection error too high.
+ *   Theia's log reports 1 and 2 together as "bad triangulation angles", 3 as failed triangulations, 4 and 5 together as
+ *   "too high reprojection errors".
+ * Outputs: point_out (n_tracks x 3: X for the statuses 0, 4 and 5, zero otherwise), status_out (n_tracks); optional (NULL: not returned)
+ * n_views_out (n_tracks: the count n), mean_sq_err_out (n_tracks: the mean of step 5 over all n observations for the statuses 0, 4 and 5,
+ * zero otherwise), counts_out[6] (tracks per status), kernel_ms (device time of the kernels).
+ *
+ * Order of the sums (part of the definition: it decides the rounding).  A track of `len` observations (its CSR length, estimated or not)
+ * is worked by a group of G lanes:
+ *        len <= 8: G = 4;      9 <= len <= 64: G = 16;      len >= 65: G = 64.
+ * Lane l of the group adds the terms of the observations at places l, l + G, l + 2G, ... of the track, in that order, starting from 0
+ * (the nine sums of M and q in step 4, the squared errors in step 5); the G partial sums are then combined by an xor butterfly with the
+ * offsets G/2, G/4, ..., 1 (v += v of lane l xor offset).  The order depends on the track's own length and data alone: two calls return
+ * the same bytes, and permuting the tracks permutes the outputs bit for bit.  The tracks run in the order gsfm_tracks_launch_order gives;
+ * outputs are written at the caller's index.
+ *
+ * Device memory 20 B per observation (+ 24 B per observation when a track of 65 or more observations exists) + O(n_tracks + n_cams).
+ * Arguments are checked on the host before any device call (GSFM_ERR_INVALID_ARG: a NULL required pointer, track_ptr[0] != 0, a track_ptr
+ * that decreases, a camera index >= n_cams, an angle or an error bound that is negative or not finite); without a device
+ * GSFM_ERR_NO_DEVICE: there is no host fallback.  No tracks: GSFM_OK. */
+#ifndef GSFM_TRACKS_H_
+#define GSFM_TRACKS_H_
+
+#include <stdint.h>
+#include "gsfm_rot.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+gsfm_status gsfm_tracks_triangulate(uint32_t n_cams, const double* rot_aa, const double* cam_pos, const double* intrinsics,
+                                    const uint8_t* cam_estimated, uint64_t n_tracks, const uint64_t* track_ptr, const uint32_t* obs_cam,
+                                    const double* obs_xy, double min_triangulation_angle_degrees, double max_reprojection_error_pixels,
+                                    double* point_out, int32_t* status_out, int32_t* n_views_out, double* mean_sq_err_out,
+                                    uint64_t* counts_out, double* kernel_ms);
+
+/* The launch order of gsfm_tracks_triangulate, host code only (no device is touched): order_out[n_tracks] lists the tracks of lane class
+ * G = 4, then 16, then 64, inside a class by descending length and equal lengths by ascending index; class_begin_out[4] holds the three
+ * slices' bounds in order_out.  GSFM_ERR_INVALID_ARG for a NULL pointer (n_tracks > 0), a decreasing track_ptr or 2^31 or more tracks. */
+gsfm_status gsfm_tracks_launch_order(uint64_t n_tracks, const uint64_t* track_ptr, uint32_t* order_out, uint64_t* class_begin_out);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif  /* GSFM_TRACKS_H_ */
