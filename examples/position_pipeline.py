@@ -2,7 +2,7 @@
 """The reference's scripts/sfm_pipeline.py 1DSfM branch through step 7: rotations, FilterRotations(), OptimizePairwiseTranslations() (every
 pair's position_2 refined with the estimated rotations), FilterRelativeTranslation() (the 1DSfM filter), then camera positions
 (EstimatePosition(HuberLoss(0.1), PositionErrorType.BASELINE) there; NonlinearPositionEstimator.EstimatePositions here), then
-EstimateStructure() (every track triangulated and gated, without the per-track refinement) and the PLY with the estimated tracks' points
+EstimateStructure(refine=True) (every track triangulated, refined per track when the flags say bundle_adjust_tracks, and gated) and the PLY with the estimated tracks' points
 and the estimated camera positions.
 usage: position_pipeline.py <dataset_dir with EGs.txt, cc.txt> [flags.yaml]"""
 import os
@@ -33,7 +33,7 @@ def position_pipeline(dataset_dir, flagfile=None):
     assert estimator.EstimatePositions(graph.GetAllEdges(), solver.orientations, positions, HuberLoss(0.1),
                                        sfm.PositionErrorType.BASELINE), estimator.LastError()
     sfm.SetReconstructionFromEstimatedPoses(solver.orientations, positions, scene)
-    solver.EstimateStructure()        # a dataset without tracks.txt has nothing to triangulate
+    solver.EstimateStructure(refine=True)        # a dataset without tracks.txt has nothing to triangulate
     return scene, estimator
 
 

@@ -114,6 +114,17 @@ class PosSummary(C.Structure):
         return d
 
 
+class TrackRefineOptions(C.Structure):
+    """gsfm_tracks_refine_options (include/gsfm_tracks.h)"""
+    _fields_ = [
+        ("refine", C.c_int32), ("max_num_iterations", C.c_int32),
+        ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
+        ("parameter_tolerance", C.c_double), ("min_relative_decrease", C.c_double),
+        ("initial_trust_region_radius", C.c_double), ("max_trust_region_radius", C.c_double),
+        ("min_trust_region_radius", C.c_double),
+    ]
+
+
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 ALL_REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 LOSS_CALLBACK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_double, C.POINTER(C.c_double))
@@ -287,3 +298,9 @@ def declare_track_signatures(lib):
     lib.gsfm_tracks_triangulate.restype = C.c_int
     lib.gsfm_tracks_launch_order.argtypes = [C.c_uint64, u64p, _U32P, u64p]
     lib.gsfm_tracks_launch_order.restype = C.c_int
+    lib.gsfm_tracks_refine_default_options.argtypes = [C.POINTER(TrackRefineOptions)]
+    lib.gsfm_tracks_refine_default_options.restype = None
+    lib.gsfm_tracks_triangulate_refine.argtypes = [C.c_uint32, _DP, _DP, _DP, C.POINTER(C.c_uint8), C.c_uint64, u64p, _U32P, _DP, C.c_double, C.c_double,
+                                                   C.POINTER(TrackRefineOptions), C.POINTER(LossNode), C.c_int32,
+                                                   _DP, i32p, i32p, _DP, i32p, _DP, _DP, i32p, u64p, _DP]
+    lib.gsfm_tracks_triangulate_refine.restype = C.c_int

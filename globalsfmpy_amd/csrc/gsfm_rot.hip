@@ -14,6 +14,7 @@
 #include "trans_filter.hpp"
 #include "trans_refine.hpp"
 #include "triangulate.hpp"
+#include "track_refine.hpp"
 
 // =============================================================================================
 extern "C" {
@@ -425,6 +426,30 @@ gsfm_status gsfm_tracks_triangulate(uint32_t n_cams, const double* rot_aa, const
                     max_reprojection_error_pixels, point_out, status_out, n_views_out, mean_sq_err_out, counts_out, kernel_ms);
   } catch (const std::exception& e) {
     return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the track triangulation ran out of host resources: ") + e.what());
+  }
+}
+
+void gsfm_tracks_refine_default_options(gsfm_tracks_refine_options* o) {
+  if (!o) return;
+  o->refine = 1; o->max_num_iterations = 100;
+  o->function_tolerance = 1e-6; o->gradient_tolerance = 1e-10; o->parameter_tolerance = 1e-8; o->min_relative_decrease = 1e-3;
+  o->initial_trust_region_radius = 1e4; o->max_trust_region_radius = 1e12; o->min_trust_region_radius = 1e-32;
+}
+
+gsfm_status gsfm_tracks_triangulate_refine(uint32_t n_cams, const double* rot_aa, const double* cam_pos, const double* intrinsics,
+                                           const uint8_t* cam_estimated, uint64_t n_tracks, const uint64_t* track_ptr, const uint32_t* obs_cam,
+                                           const double* obs_xy, double min_triangulation_angle_degrees, double max_reprojection_error_pixels,
+                                           const gsfm_tracks_refine_options* options, const gsfm_loss_node* loss_program, int32_t n_loss_nodes,
+                                           double* point_out, int32_t* status_out, int32_t* n_views_out, double* mean_sq_err_out,
+                                           int32_t* iterations_out, double* initial_cost_out, double* final_cost_out, int32_t* termination_out,
+                                           uint64_t* counts_out, double* kernel_ms) {
+  // (a host vector of O(n_tracks): an exception must not cross the C boundary)
+  try {
+    return tri_refine_impl(n_cams, rot_aa, cam_pos, intrinsics, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy, min_triangulation_angle_degrees,
+                           max_reprojection_error_pixels, options, loss_program, n_loss_nodes, point_out, status_out, n_views_out, mean_sq_err_out,
+                           iterations_out, initial_cost_out, final_cost_out, termination_out, counts_out, kernel_ms);
+  } catch (const std::exception& e) {
+    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the track refinement ran out of host resources: ") + e.what());
   }
 }
 

@@ -1,8 +1,11 @@
 // Host side of gsfm_tracks_triangulate (include/gsfm_tracks.h): validation, the lane classes and the launch order inside a class
 // (longest track first), one device slab and the launches of triangulate_kernels.hpp.  Part of libgsfm_rot.so's one translation unit.
+// gsfm_tracks_triangulate_refine (track_refine.hpp) runs through the same function with a TriRefineHook: the same checks, slab and launch
+// order, k_tri_refine_tracks in place of k_tri_tracks and four more outputs.
 #pragma once
 #include "host_common.hpp"
 #include "triangulate_kernels.hpp"
+#include "track_refine_kernels.hpp"
 #include "../../include/gsfm_tracks.h"
 
 namespace {
@@ -25,12 +28,23 @@ void tri_bucket(uint64_t n_tracks, const uint64_t* track_ptr, uint32_t* order, u
     });
 }
 
+// What gsfm_tracks_triangulate_refine adds to a call: the kernel's options and loss leaf (proto: its TriArgs and output pointers are filled
+// here) and the host outputs (each may be NULL).  With a hook the statuses run to 6 and counts_out holds 7 entries.
+struct TriRefineHook {
+  gsfm::TriRefineArgs proto;
+  int32_t* iterations_out;
+  int32_t* termination_out;
+  double* initial_cost_out;
+  double* final_cost_out;
+};
+
 gsfm_status tri_impl(uint32_t n_cams, const double* rot_aa, const double* cam_pos, const double* intrinsics, const uint8_t* cam_estimated,
                      uint64_t n_tracks, const uint64_t* track_ptr, const uint32_t* obs_cam, const double* obs_xy,
                      double min_triangulation_angle_degrees, double max_reprojection_error_pixels, double* point_out, int32_t* status_out,
-                     int32_t* n_views_out, double* mean_sq_err_out, uint64_t* counts_out, double* kernel_ms) {
+                     int32_t* n_views_out, double* mean_sq_err_out, uint64_t* counts_out, double* kernel_ms, const TriRefineHook* rf = nullptr) {
+  const int n_status = rf ? 7 : 6;
   if (kernel_ms) *kernel_ms = 0.0;
-  if (counts_out) for (int k = 0; k < 6; ++k) counts_out[k] = 0;
+  if (counts_out) for (int k = 0; k < n_status; ++k) counts_out[k] = 0;
   if (!(min_triangulation_angle_degrees >= 0.0) || !std::isfinite(min_triangulation_angle_degrees))
     return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "min_triangulation_angle_degrees must be finite and not negative");
   if (!(max_reprojection_error_pixels >= 0.0) || !std::isfinite(max_reprojection_error_pixels))
@@ -65,7 +79,8 @@ gsfm_status tri_impl(uint32_t n_cams, const double* rot_aa, const double* cam_po
   auto take = [&](size_t bytes) { const size_t o = off; off += up(bytes); return o; };
   const size_t o_ord = take(4 * T), o_ptr = take(8 * (T + 1)), o_cam = take(4 * O), o_xy = take(16 * O), o_rot = take(24 * N), o_pos = take(24 * N),
                o_k = take(24 * N), o_est = take(N), o_rec = take(8 * GSFM_TRI_CAM_DOUBLES * N), o_plane = take(long_class ? 24 * O : 0),
-               o_pt = take(24 * T), o_st = take(4 * T), o_nv = take(4 * T), o_err = take(8 * T), total = off;
+               o_pt = take(24 * T), o_st = take(4 * T), o_nv = take(4 * T), o_err = take(8 * T), o_it = take(rf ? 4 * T : 0), o_term = take(rf ? 4 * T : 0),
+               o_c0 = take(rf ? 8 * T : 0), o_c1 = take(rf ? 8 * T : 0), total = off;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)free_b < (double)total * 1.02 + (64u << 20))
     return (gsfm_status)fail(GSFM_ERR_HIP, "not enough free device memory for the track triangulation (" + std::to_string((long long)(total >> 20)) +
@@ -97,23 +112,37 @@ gsfm_status tri_impl(uint32_t n_cams, const double* rot_aa, const double* cam_po
   if (N > 0)
     hipLaunchKernelGGL(k_tri_cameras, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, n_cams, (const double*)(base + o_rot), (const double*)(base + o_pos),
                        (const double*)(base + o_k), cam_estimated ? (const uint8_t*)(base + o_est) : (const uint8_t*)nullptr, (double*)(base + o_rec));
-  auto launch = [&](int c, auto kernel, unsigned groups_per_block, unsigned block) {
+  TriRefineArgs ra{};
+  if (rf) {
+    ra = rf->proto;
+    ra.iterations = (int32_t*)(base + o_it); ra.termination = (int32_t*)(base + o_term);
+    ra.initial_cost = (double*)(base + o_c0); ra.final_cost = (double*)(base + o_c1);
+  }
+  auto launch = [&](int c, auto kernel, auto refine_kernel, unsigned groups_per_block, unsigned block) {
     a.n_slots = cb[c + 1] - cb[c];
     if (a.n_slots == 0) return;
     a.order = (const uint32_t*)(base + o_ord) + cb[c];
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((a.n_slots + groups_per_block - 1) / groups_per_block)), dim3(block), 0, s, a);
+    const dim3 grid((unsigned)((a.n_slots + groups_per_block - 1) / groups_per_block));
+    if (rf) { ra.tri = a; hipLaunchKernelGGL(refine_kernel, grid, dim3(block), 0, s, ra); }
+    else hipLaunchKernelGGL(kernel, grid, dim3(block), 0, s, a);
   };
-  launch(2, k_tri_tracks<64>, 1, 64);   // the long tracks start first
-  launch(1, k_tri_tracks<16>, GSFM_TRI_BLOCK / 16, GSFM_TRI_BLOCK);
-  launch(0, k_tri_tracks<4>, GSFM_TRI_BLOCK / 4, GSFM_TRI_BLOCK);
+  launch(2, k_tri_tracks<64>, k_tri_refine_tracks<64>, 1, 64);   // the long tracks start first
+  launch(1, k_tri_tracks<16>, k_tri_refine_tracks<16>, GSFM_TRI_BLOCK / 16, GSFM_TRI_BLOCK);
+  launch(0, k_tri_tracks<4>, k_tri_refine_tracks<4>, GSFM_TRI_BLOCK / 4, GSFM_TRI_BLOCK);
   HIPCHK_S(hipEventRecord(Gd.ev[1], s));
   HIPCHK_S(hipMemcpyAsync(point_out, base + o_pt, 24 * T, hipMemcpyDeviceToHost, s));
   HIPCHK_S(hipMemcpyAsync(status_out, base + o_st, 4 * T, hipMemcpyDeviceToHost, s));
   if (n_views_out) HIPCHK_S(hipMemcpyAsync(n_views_out, base + o_nv, 4 * T, hipMemcpyDeviceToHost, s));
   if (mean_sq_err_out) HIPCHK_S(hipMemcpyAsync(mean_sq_err_out, base + o_err, 8 * T, hipMemcpyDeviceToHost, s));
+  if (rf) {
+    if (rf->iterations_out) HIPCHK_S(hipMemcpyAsync(rf->iterations_out, base + o_it, 4 * T, hipMemcpyDeviceToHost, s));
+    if (rf->termination_out) HIPCHK_S(hipMemcpyAsync(rf->termination_out, base + o_term, 4 * T, hipMemcpyDeviceToHost, s));
+    if (rf->initial_cost_out) HIPCHK_S(hipMemcpyAsync(rf->initial_cost_out, base + o_c0, 8 * T, hipMemcpyDeviceToHost, s));
+    if (rf->final_cost_out) HIPCHK_S(hipMemcpyAsync(rf->final_cost_out, base + o_c1, 8 * T, hipMemcpyDeviceToHost, s));
+  }
   HIPCHK_S(hipStreamSynchronize(s));
   HIPCHK_S(hipGetLastError());
-  if (counts_out) for (size_t t = 0; t < T; ++t) if (status_out[t] >= 0 && status_out[t] < 6) ++counts_out[status_out[t]];
+  if (counts_out) for (size_t t = 0; t < T; ++t) if (status_out[t] >= 0 && status_out[t] < n_status) ++counts_out[status_out[t]];
   if (kernel_ms) { float ms = 0; (void)hipEventElapsedTime(&ms, Gd.ev[0], Gd.ev[1]); *kernel_ms = ms; }
   return GSFM_OK;
 }

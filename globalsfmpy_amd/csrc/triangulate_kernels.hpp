@@ -17,7 +17,8 @@
 //                   solve   the 3 x 3 Cholesky in every lane;
 //                   gate    lane l re-reads its observations' pixels and camera records: depth sign and squared pixel error, butterfly.
 // The ray store is written and read by different lanes of ONE wavefront: a work-group fence orders the two.  No atomics, nothing waits
-// for another work-group, no host round trip.  A track's arithmetic depends on its own length and data alone (the class, the lane
+// for another work-group, no host round trip.  Front (pass 1, angle, solve) and gate are __device__ functions: k_tri_refine_tracks
+// (track_refine_kernels.hpp) runs the same text around its refinement.  A track's arithmetic depends on its own length and data alone (the class, the lane
 // stride and the butterfly are functions of the length), so two calls return the same bytes and so does a call with the tracks permuted.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -83,23 +84,37 @@ __device__ __forceinline__ bool tri_group_any(bool flag, int lane_in_wave) {
   return ((b >> (lane_in_wave & ~(G - 1))) & ((1ull << (G & 63)) - 1ull)) != 0ull;
 }
 
-template <int G>
-__global__ void __launch_bounds__(G == 64 ? 64 : GSFM_TRI_BLOCK) k_tri_tracks(TriArgs a) {
-  constexpr int BLOCK = G == 64 ? 64 : GSFM_TRI_BLOCK;
-  constexpr int GROUPS = BLOCK / G;
-  constexpr int CAP = G == 4 ? GSFM_TRI_LEN_G4 : GSFM_TRI_LEN_G16;          // the longest track of the class (LDS classes)
-  __shared__ double lds_rays[G == 64 ? 1 : 3 * GROUPS * CAP];
-  const int group = threadIdx.x / G, l = threadIdx.x % G, lane_in_wave = threadIdx.x & 63;
-  const uint64_t slot = (uint64_t)blockIdx.x * GROUPS + group;
-  const bool live = slot < a.n_slots;                                        // a dead group runs along on an empty track and stores nothing
-  const uint64_t t = live ? a.order[slot] : 0;
-  const uint64_t ob = live ? a.track_ptr[t] : 0, oe = live ? a.track_ptr[t + 1] : 0;
-  const uint32_t len = (uint32_t)(oe - ob);
-  // the ray store: index k is the observation's place in the track
+// The track of a lane's group and the group's ray store (index k of the store is the observation's place in the track).  A dead group (the
+// last block's spare slots) runs along on an empty track and stores nothing.
+struct TriTrack {
+  bool live;
+  uint64_t t, ob;
+  uint32_t len;
   double* rx, * ry, * rz;
-  if (G == 64) { rx = a.plane + ob; ry = rx + a.n_obs; rz = ry + a.n_obs; }
-  else { rx = lds_rays + 3 * CAP * group; ry = rx + CAP; rz = ry + CAP; }
+};
+template <int G>
+__device__ __forceinline__ TriTrack tri_track(const TriArgs& a, double* lds_rays, int group) {
+  constexpr int GROUPS = (G == 64 ? 64 : GSFM_TRI_BLOCK) / G;
+  constexpr int CAP = G == 4 ? GSFM_TRI_LEN_G4 : GSFM_TRI_LEN_G16;          // the longest track of the class (LDS classes)
+  TriTrack k;
+  const uint64_t slot = (uint64_t)blockIdx.x * GROUPS + group;
+  k.live = slot < a.n_slots;
+  k.t = k.live ? a.order[slot] : 0;
+  k.ob = k.live ? a.track_ptr[k.t] : 0;
+  const uint64_t oe = k.live ? a.track_ptr[k.t + 1] : 0;
+  k.len = (uint32_t)(oe - k.ob);
+  if (G == 64) { k.rx = a.plane + k.ob; k.ry = k.rx + a.n_obs; k.rz = k.ry + a.n_obs; }
+  else { k.rx = lds_rays + 3 * CAP * group; k.ry = k.rx + CAP; k.rz = k.ry + CAP; }
+  return k;
+}
 
+// Steps 1 to 4 of include/gsfm_tracks.h, the text both track kernels run: the rays and the sums, the angle test, the midpoint.  Returns the
+// status (0: X holds the midpoint; 1, 2, 3: X is zero); n is the count of observations in estimated views.  The same values in every lane.
+template <int G>
+__device__ __forceinline__ int tri_front(const TriArgs& a, const TriTrack& tk, int l, int lane_in_wave, double* X, int& n) {
+  const uint64_t ob = tk.ob;
+  const uint32_t len = tk.len;
+  double* const rx = tk.rx, * const ry = tk.ry, * const rz = tk.rz;
   // ---- pass 1: rays, once, and the sums of M = sum (I - d d^T), q = sum (I - d d^T) o ----
   double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // M: xx xy xz yy yz zz, q: x y z
   int mine = 0;
@@ -122,12 +137,12 @@ __global__ void __launch_bounds__(G == 64 ? 64 : GSFM_TRI_BLOCK) k_tri_tracks(Tr
     rx[k] = d0; ry[k] = d1; rz[k] = d2;
   }
   __threadfence_block();   // the rays are read by the group's other lanes below
-  const int n = tri_group_allsum_int<G>(mine);
+  n = tri_group_allsum_int<G>(mine);
 #pragma unroll
   for (int k = 0; k < 9; ++k) s[k] = tri_group_allsum<G>(s[k]);
 
   int status = 0;
-  double X[3] = {0.0, 0.0, 0.0}, mean = 0.0;
+  X[0] = 0.0; X[1] = 0.0; X[2] = 0.0;
   if (n < 2) status = 1;
   else {
     // ---- the angle: some pair i < j with d_i . d_j < cos(min angle) ----
@@ -157,29 +172,49 @@ __global__ void __launch_bounds__(G == 64 ? 64 : GSFM_TRI_BLOCK) k_tri_tracks(Tr
       X[2] = y2 / l22; X[1] = (y1 - l21 * X[2]) / l11; X[0] = (y0 - l10 * X[1] - l20 * X[2]) / l00;
     }
   }
-  if (status == 0) {
-    // ---- the gate: every observation in front of its camera, mean squared pixel error below the bound ----
-    double err = 0.0;
-    bool behind = false;
-    for (uint32_t k = l; k < len; k += G) {
-      const double* cam = a.cams + (uint64_t)GSFM_TRI_CAM_DOUBLES * a.obs_cam[ob + k];
-      if (cam[15] == 0.0) continue;
-      const double2 xy = a.obs_xy[ob + k];
-      const double v0 = X[0] - cam[9], v1 = X[1] - cam[10], v2 = X[2] - cam[11];
-      const double px = cam[0] * v0 + cam[1] * v1 + cam[2] * v2, py = cam[3] * v0 + cam[4] * v1 + cam[5] * v2, pz = cam[6] * v0 + cam[7] * v1 + cam[8] * v2;
-      behind |= pz < 0.0;
-      const double ex = cam[12] * px / pz + cam[13] - xy.x, ey = cam[12] * py / pz + cam[14] - xy.y;
-      err += ex * ex + ey * ey;
-    }
-    mean = tri_group_allsum<G>(err) / (double)n;
-    if (tri_group_any<G>(behind, lane_in_wave)) status = 4;
-    else if (!(mean < a.max_sq_err)) status = 5;
+  return status;
+}
+
+// Step 5, the gate on the point X of a track whose status is 0 so far: every observation in front of its camera, mean squared pixel error
+// below the bound.  Returns the status 0, 4 or 5 and the mean.
+template <int G>
+__device__ __forceinline__ int tri_gate(const TriArgs& a, const TriTrack& tk, int l, int lane_in_wave, const double* X, int n, double& mean) {
+  const uint64_t ob = tk.ob;
+  const uint32_t len = tk.len;
+  double err = 0.0;
+  bool behind = false;
+  for (uint32_t k = l; k < len; k += G) {
+    const double* cam = a.cams + (uint64_t)GSFM_TRI_CAM_DOUBLES * a.obs_cam[ob + k];
+    if (cam[15] == 0.0) continue;
+    const double2 xy = a.obs_xy[ob + k];
+    const double v0 = X[0] - cam[9], v1 = X[1] - cam[10], v2 = X[2] - cam[11];
+    const double px = cam[0] * v0 + cam[1] * v1 + cam[2] * v2, py = cam[3] * v0 + cam[4] * v1 + cam[5] * v2, pz = cam[6] * v0 + cam[7] * v1 + cam[8] * v2;
+    behind |= pz < 0.0;
+    const double ex = cam[12] * px / pz + cam[13] - xy.x, ey = cam[12] * py / pz + cam[14] - xy.y;
+    err += ex * ex + ey * ey;
   }
-  if (live && l == 0) {
-    a.point[3 * t] = X[0]; a.point[3 * t + 1] = X[1]; a.point[3 * t + 2] = X[2];
-    a.status[t] = status;
-    a.n_views[t] = n;
-    a.mean_sq_err[t] = mean;
+  mean = tri_group_allsum<G>(err) / (double)n;
+  if (tri_group_any<G>(behind, lane_in_wave)) return 4;
+  return mean < a.max_sq_err ? 0 : 5;
+}
+
+template <int G>
+__global__ void __launch_bounds__(G == 64 ? 64 : GSFM_TRI_BLOCK) k_tri_tracks(TriArgs a) {
+  constexpr int BLOCK = G == 64 ? 64 : GSFM_TRI_BLOCK;
+  constexpr int GROUPS = BLOCK / G;
+  constexpr int CAP = G == 4 ? GSFM_TRI_LEN_G4 : GSFM_TRI_LEN_G16;
+  __shared__ double lds_rays[G == 64 ? 1 : 3 * GROUPS * CAP];
+  const int group = threadIdx.x / G, l = threadIdx.x % G, lane_in_wave = threadIdx.x & 63;
+  const TriTrack tk = tri_track<G>(a, lds_rays, group);
+  double X[3], mean = 0.0;
+  int n;
+  int status = tri_front<G>(a, tk, l, lane_in_wave, X, n);
+  if (status == 0) status = tri_gate<G>(a, tk, l, lane_in_wave, X, n, mean);
+  if (tk.live && l == 0) {
+    a.point[3 * tk.t] = X[0]; a.point[3 * tk.t + 1] = X[1]; a.point[3 * tk.t + 2] = X[2];
+    a.status[tk.t] = status;
+    a.n_views[tk.t] = n;
+    a.mean_sq_err[tk.t] = mean;
   }
 }
 

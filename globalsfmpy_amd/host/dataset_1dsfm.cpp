@@ -212,17 +212,46 @@ void FlattenTracks(const theia::Reconstruction& rec, FlatTracks* out) {
   }
 }
 
-EstimateStructureStats EstimateStructure(double min_angle_degrees, double max_error_pixels, theia::Reconstruction* rec) {
+EstimateStructureStats EstimateStructure(double min_angle_degrees, double max_error_pixels, theia::Reconstruction* rec, const TrackRefinement* refinement) {
   EstimateStructureStats stats;
+  gsfm_loss_node loss{};
+  if (refinement) {
+    const std::string& name = refinement->loss_function;
+    if (name == "TRIVIAL") loss.kind = GSFM_LOSS_TRIVIAL;
+    else if (name == "HUBER") loss.kind = GSFM_LOSS_HUBER;
+    else if (name == "SOFTLONE") loss.kind = GSFM_LOSS_SOFT_L1;
+    else throw std::runtime_error("EstimateStructure: the track refinement has no loss " + name + " (TRIVIAL, HUBER, SOFTLONE)");
+    loss.p[0] = refinement->loss_width;
+  }
   if (!rec->tracks || rec->tracks->tracks.empty()) return stats;   // a dataset without tracks.txt: nothing to triangulate
   FlatTracks f;
   FlattenTracks(*rec, &f);
   const size_t T = f.track_ptr.size() - 1;
   std::vector<double> point(3 * T, 0.0);
   std::vector<int32_t> status(T, 0);
-  const gsfm_status st = gsfm_tracks_triangulate((uint32_t)f.views.size(), f.rot_aa.data(), f.cam_pos.data(), f.intrinsics.data(), f.cam_estimated.data(), T,
-                                                 f.track_ptr.data(), f.obs_cam.data(), f.obs_xy.data(), min_angle_degrees, max_error_pixels, point.data(),
-                                                 status.data(), nullptr, nullptr, stats.counts, &stats.kernel_ms);
+  gsfm_status st;
+  if (refinement) {
+    gsfm_tracks_refine_options o;
+    gsfm_tracks_refine_default_options(&o);
+    o.max_num_iterations = refinement->max_num_iterations;
+    std::vector<int32_t> iterations(T, 0), termination(T, -1);
+    uint64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};
+    st = gsfm_tracks_triangulate_refine((uint32_t)f.views.size(), f.rot_aa.data(), f.cam_pos.data(), f.intrinsics.data(), f.cam_estimated.data(), T,
+                                        f.track_ptr.data(), f.obs_cam.data(), f.obs_xy.data(), min_angle_degrees, max_error_pixels, &o, &loss, 1,
+                                        point.data(), status.data(), nullptr, nullptr, iterations.data(), nullptr, nullptr, termination.data(), counts,
+                                        &stats.kernel_ms);
+    for (int k = 0; k < 6; ++k) stats.counts[k] = counts[k];
+    stats.tracks_refined = true;
+    stats.num_refinement_failed = counts[6];
+    size_t refined = 0, sum = 0;
+    for (size_t t = 0; t < T; ++t)
+      if (termination[t] >= 0) { ++refined; sum += (size_t)iterations[t]; stats.max_iterations = std::max(stats.max_iterations, (int)iterations[t]); }
+    stats.mean_iterations = refined ? (double)sum / (double)refined : 0.0;
+  } else {
+    st = gsfm_tracks_triangulate((uint32_t)f.views.size(), f.rot_aa.data(), f.cam_pos.data(), f.intrinsics.data(), f.cam_estimated.data(), T,
+                                 f.track_ptr.data(), f.obs_cam.data(), f.obs_xy.data(), min_angle_degrees, max_error_pixels, point.data(),
+                                 status.data(), nullptr, nullptr, stats.counts, &stats.kernel_ms);
+  }
   if (st != GSFM_OK) throw std::runtime_error(std::string("EstimateStructure: ") + gsfm_last_error());
   rec->track_point.assign(T, Eigen::Vector3d());
   rec->track_estimated.assign(T, 0);

@@ -114,7 +114,9 @@ struct ReconstructionEstimatorOptions {
   double translation_filtering_projection_tolerance = 0.1;   // :149
   double min_triangulation_angle_degrees = 4.0;              // :278
   double triangulation_max_reprojection_error_in_pixels = 15.0;   // :281
-  bool bundle_adjust_tracks = true;                          // :284; read, and NOT honoured: EstimateStructure() does not refine tracks
+  bool bundle_adjust_tracks = true;                          // :284; honoured by EstimateStructure(refine=True) only: the default call does not refine tracks
+  std::string bundle_adjustment_loss_function_type = "TRIVIAL";   // :248 (LossFunctionType::TRIVIAL); the YAML's bundle_adjustment_robust_loss_function
+  double bundle_adjustment_robust_loss_width = 10.0;         // :251
 };
 struct ReconstructionBuilderOptions {
   int num_threads = 1;
@@ -233,11 +235,20 @@ class GlobalReconstructionEstimator {
   }
   // :621-636 with bundle_adjustment = false whatever options_.bundle_adjust_tracks says: every track triangulated by the midpoint method and
   // gated on angle and reprojection error, over the views SetReconstructionFromEstimatedPoses marked, in one device call
-  gsfm::EstimateStructureStats EstimateStructure() {
+  // refine = true honours options_.bundle_adjust_tracks: Theia's BundleAdjustTrack between the midpoint and the gate, in the same device call,
+  // with the loss of bundle_adjustment_loss_function_type / bundle_adjustment_robust_loss_width
+  gsfm::EstimateStructureStats EstimateStructure(bool refine = false) {
     if (!reconstruction_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
-    structure_ = gsfm::EstimateStructure(options_.min_triangulation_angle_degrees, options_.triangulation_max_reprojection_error_in_pixels, reconstruction_);
+    gsfm::TrackRefinement r;
+    r.loss_function = options_.bundle_adjustment_loss_function_type;
+    r.loss_width = options_.bundle_adjustment_robust_loss_width;
+    const bool refined = refine && options_.bundle_adjust_tracks;
+    structure_ = gsfm::EstimateStructure(options_.min_triangulation_angle_degrees, options_.triangulation_max_reprojection_error_in_pixels, reconstruction_,
+                                         refined ? &r : nullptr);
+    structure_refine_asked_ = refine;
     return structure_;
   }
+  bool structure_refine_asked_ = false;
   gsfm::EstimateStructureStats structure_;
   ReconstructionEstimatorOptions options_;
   ViewGraph* view_graph_ = nullptr;
@@ -253,7 +264,7 @@ py::dict refine_stats_dict(const RefineRelativeTranslationsStats& st) {
   return d;
 }
 
-py::dict structure_dict(const gsfm::EstimateStructureStats& st, bool bundle_adjust_tracks) {
+py::dict structure_dict(const gsfm::EstimateStructureStats& st, bool bundle_adjust_tracks, bool refine_asked = false) {
   py::dict d;
   d["num_tracks"] = st.num_tracks; d["num_estimated"] = st.num_estimated; d["kernel_ms"] = st.kernel_ms;
   d["counts"] = std::vector<uint64_t>(st.counts, st.counts + 6);
@@ -263,6 +274,14 @@ py::dict structure_dict(const gsfm::EstimateStructureStats& st, bool bundle_adju
   d["tracks_refined"] = false;
   d["bundle_adjust_tracks_requested"] = bundle_adjust_tracks;
   d["note"] = "tracks triangulated without per-track refinement (bundle_adjust_tracks is not honoured)";
+  if (refine_asked) {   // EstimateStructure(refine=True): the option decides
+    d["tracks_refined"] = st.tracks_refined;
+    d["num_refinement_failed"] = st.num_refinement_failed;
+    d["mean_iterations"] = st.mean_iterations;
+    d["max_iterations"] = st.max_iterations;
+    d["note"] = st.tracks_refined ? "tracks triangulated and refined per track (bundle_adjust_tracks)"
+                                  : "tracks triangulated without per-track refinement (bundle_adjust_tracks is false)";
+  }
   return d;
 }
 
@@ -292,6 +311,8 @@ void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions
   get("min_triangulation_angle_degrees", options.reconstruction_estimator_options.min_triangulation_angle_degrees);
   get("triangulation_reprojection_error_pixels", options.reconstruction_estimator_options.triangulation_max_reprojection_error_in_pixels);
   get("bundle_adjust_tracks", options.reconstruction_estimator_options.bundle_adjust_tracks);
+  get("bundle_adjustment_robust_loss_function", options.reconstruction_estimator_options.bundle_adjustment_loss_function_type);
+  get("bundle_adjustment_robust_loss_width", options.reconstruction_estimator_options.bundle_adjustment_robust_loss_width);
 }
 
 }  // namespace
@@ -377,7 +398,9 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def_readwrite("translation_filtering_projection_tolerance", &ReconstructionEstimatorOptions::translation_filtering_projection_tolerance)
       .def_readwrite("min_triangulation_angle_degrees", &ReconstructionEstimatorOptions::min_triangulation_angle_degrees)
       .def_readwrite("triangulation_max_reprojection_error_in_pixels", &ReconstructionEstimatorOptions::triangulation_max_reprojection_error_in_pixels)
-      .def_readwrite("bundle_adjust_tracks", &ReconstructionEstimatorOptions::bundle_adjust_tracks);
+      .def_readwrite("bundle_adjust_tracks", &ReconstructionEstimatorOptions::bundle_adjust_tracks)
+      .def_readwrite("bundle_adjustment_loss_function_type", &ReconstructionEstimatorOptions::bundle_adjustment_loss_function_type)
+      .def_readwrite("bundle_adjustment_robust_loss_width", &ReconstructionEstimatorOptions::bundle_adjustment_robust_loss_width);
   py::class_<ReconstructionBuilderOptions>(m, "ReconstructionBuilderOptions")
       .def(py::init<>())
       .def_readwrite("num_threads", &ReconstructionBuilderOptions::num_threads)
@@ -491,12 +514,12 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
         return refine_stats_dict(st);
       })
       .def("FilterRelativeTranslation", &GlobalReconstructionEstimator::FilterRelativeTranslation, py::call_guard<py::gil_scoped_release>())
-      .def("EstimateStructure", [](GlobalReconstructionEstimator& e) {
+      .def("EstimateStructure", [](GlobalReconstructionEstimator& e, bool refine) {
         gsfm::EstimateStructureStats st;
-        { py::gil_scoped_release release; st = e.EstimateStructure(); }
-        return structure_dict(st, e.options_.bundle_adjust_tracks);
-      })
-      .def("LastStructureSummary", [](const GlobalReconstructionEstimator& e) { return structure_dict(e.structure_, e.options_.bundle_adjust_tracks); })
+        { py::gil_scoped_release release; st = e.EstimateStructure(refine); }
+        return structure_dict(st, e.options_.bundle_adjust_tracks, refine);
+      }, py::arg("refine") = false)
+      .def("LastStructureSummary", [](const GlobalReconstructionEstimator& e) { return structure_dict(e.structure_, e.options_.bundle_adjust_tracks, e.structure_refine_asked_); })
       .def("LastSummary", [](const GlobalReconstructionEstimator& e) { return summary_dict(e.summary_); })
       .def("LastError", [](const GlobalReconstructionEstimator& e) { return e.error_; });
 

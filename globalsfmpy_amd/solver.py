@@ -425,13 +425,17 @@ def refine_relative_translations(n_cams, edge_i, edge_j, match_ptr, matches, int
 
 
 def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated=None, min_triangulation_angle_degrees=4.0,
-                       max_reprojection_error_pixels=15.0):
+                       max_reprojection_error_pixels=15.0, refine=False, loss=None, max_num_iterations=100):
     """gsfm_tracks_triangulate: every track triangulated by the midpoint method and gated on triangulation angle and reprojection error
     (Theia's TrackEstimator::EstimateTrack without the per-track refinement, under the definition of include/gsfm_tracks.h) on the device,
     a group of 4, 16 or 64 lanes per track.  rot_aa, cam_pos: N x 3; intrinsics: N x 3 (f u v); track_ptr: T + 1 offsets into obs_cam
     (camera index) and obs_xy (pixels); cam_estimated: N flags or None (all estimated).  The defaults are the reference pipeline's.
     Returns dict(points T x 3, status (0 estimated, 1 too few views, 2 angle, 3 Cholesky, 4 behind a camera, 5 reprojection error),
-    n_views, mean_sq_err, counts (6), kernel_ms)."""
+    n_views, mean_sq_err, counts (6), kernel_ms).
+    refine=True: gsfm_tracks_triangulate_refine -- between the midpoint and the gate every track's point is refined by Levenberg-Marquardt
+    with the cameras held (Theia's BundleAdjustTrack).  loss: None (Ceres' NULL loss), a list of (kind, p0, p1, p2) nodes or an object with
+    .native_program(); one Trivial / Huber / SoftLOne / Tukey / GemanMcClure leaf.  The dict then also holds iterations, initial_cost,
+    final_cost, termination (per track, -1 = not refined), counts has 7 entries and status 6 is "refinement failed"."""
     lib = _abi.load_library()
     rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(-1, 3)
     n = rot.shape[0]
@@ -453,9 +457,34 @@ def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, 
         if est.shape[0] != n:
             raise ValueError("cam_estimated needs one flag per camera")
     points, status, n_views = np.zeros((T, 3)), np.zeros(T, dtype=np.int32), np.zeros(T, dtype=np.int32)
-    err, counts = np.zeros(T), np.zeros(6, dtype=np.uint64)
     ms = C.c_double(0)
     i32p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    if refine:
+        if loss is None:
+            nodes = []
+        elif isinstance(loss, (list, tuple)):
+            nodes = list(loss)
+        elif hasattr(loss, "native_program") and loss.native_program() is not None:
+            nodes = loss.native_program()
+        else:
+            raise TypeError("the track refinement needs a loss with a native descriptor, got %r" % (loss,))
+        prog, n_nodes = _abi.make_program(nodes)
+        opt = _abi.TrackRefineOptions()
+        lib.gsfm_tracks_refine_default_options(C.byref(opt))
+        opt.refine, opt.max_num_iterations = 1, int(max_num_iterations)
+        err, counts = np.zeros(T), np.zeros(7, dtype=np.uint64)
+        iters, term = np.zeros(T, dtype=np.int32), np.full(T, -1, dtype=np.int32)
+        cost0, cost1 = np.zeros(T), np.zeros(T)
+        st = lib.gsfm_tracks_triangulate_refine(n, _dp(rot), _dp(pos), _dp(K), None if est is None else est.ctypes.data_as(C.POINTER(C.c_uint8)), T,
+                                                tp.ctypes.data_as(u64p), _u32p(oc), _dp(xy), float(min_triangulation_angle_degrees),
+                                                float(max_reprojection_error_pixels), C.byref(opt), prog, n_nodes, _dp(points),
+                                                status.ctypes.data_as(i32p), n_views.ctypes.data_as(i32p), _dp(err), iters.ctypes.data_as(i32p),
+                                                _dp(cost0), _dp(cost1), term.ctypes.data_as(i32p), counts.ctypes.data_as(u64p), C.byref(ms))
+        if st != 0:
+            raise SolverError("gsfm_tracks_triangulate_refine failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+        return {"points": points, "status": status, "n_views": n_views, "mean_sq_err": err, "counts": counts, "kernel_ms": ms.value,
+                "iterations": iters, "initial_cost": cost0, "final_cost": cost1, "termination": term}
+    err, counts = np.zeros(T), np.zeros(6, dtype=np.uint64)
     st = lib.gsfm_tracks_triangulate(n, _dp(rot), _dp(pos), _dp(K), None if est is None else est.ctypes.data_as(C.POINTER(C.c_uint8)), T,
                                      tp.ctypes.data_as(u64p), _u32p(oc), _dp(xy), float(min_triangulation_angle_degrees),
                                      float(max_reprojection_error_pixels), _dp(points), status.ctypes.data_as(i32p), n_views.ctypes.data_as(i32p),

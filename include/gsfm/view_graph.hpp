@@ -166,11 +166,23 @@ struct EstimateStructureStats {
   size_t num_tracks = 0, num_estimated = 0;
   uint64_t counts[6] = {0, 0, 0, 0, 0, 0};           // tracks per status of gsfm_tracks_triangulate
   double kernel_ms = 0.0;
+  // the refined call (gsfm_tracks_triangulate_refine) only
+  bool tracks_refined = false;
+  uint64_t num_refinement_failed = 0;                // status 6
+  double mean_iterations = 0.0;                      // over the refined tracks
+  int max_iterations = 0;
 };
-// One call of gsfm_tracks_triangulate over all tracks; stores point and estimated flag per track in the reconstruction.  A reconstruction
+// The per-track refinement EstimateStructure may run (Theia's BundleAdjustTrack under the definition of include/gsfm_tracks.h): the loss
+// as BundleAdjustmentOptions names it (TRIVIAL, HUBER, SOFTLONE; anything else throws std::runtime_error) and its width.
+struct TrackRefinement {
+  std::string loss_function = "TRIVIAL";
+  double loss_width = 10.0;
+  int max_num_iterations = 100;
+};
+// One call of gsfm_tracks_triangulate -- with `refinement`, of gsfm_tracks_triangulate_refine -- over all tracks; stores point and estimated flag per track in the reconstruction.  A reconstruction
 // without tracks is left alone.  Throws std::runtime_error when no device is usable (there is no CPU fallback) or the device call fails.
 EstimateStructureStats EstimateStructure(double min_triangulation_angle_degrees, double max_reprojection_error_pixels,
-                                         theia::Reconstruction* reconstruction);
+                                         theia::Reconstruction* reconstruction, const TrackRefinement* refinement = nullptr);
 // Theia's io/write_ply_file.cc: the points of the estimated tracks with at least min_num_observations_per_point views (no colour: 0 0 0;
 // ascending track index where Theia walks a hash set), then the estimated views' positions in green.  A view without a position is
 // written at the origin (a rotation-only reconstruction).  Returns false when the file cannot be written.

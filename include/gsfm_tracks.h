@@ -71,6 +71,82 @@ gsfm_status gsfm_tracks_triangulate(uint32_t n_cams, const double* rot_aa, const
  * slices' bounds in order_out.  GSFM_ERR_INVALID_ARG for a NULL pointer (n_tracks > 0), a decreasing track_ptr or 2^31 or more tracks. */
 gsfm_status gsfm_tracks_launch_order(uint64_t n_tracks, const uint64_t* track_ptr, uint32_t* order_out, uint64_t* class_begin_out);
 
+/* ---- Triangulation WITH the per-track refinement: gsfm_tracks_triangulate_refine ----
+ *
+ * Restates EstimateTrack with bundle_adjustment = true: between the midpoint (step 4) and the gate (step 5) Theia runs BundleAdjustTrack
+ * (sfm/bundle_adjustment/bundle_adjust_track.cc), a Levenberg-Marquardt on the point alone with every camera held constant, and gates
+ * the refined point.  The arguments of gsfm_tracks_triangulate, the options below and a loss; the steps 1 to 4 are those above, to the
+ * bit, and so is step 5 on the point it is given.
+ *
+ * The loss is a descriptor of gsfm_rot.h, passed as gsfm_pos_set_loss takes one: loss_program / n_loss_nodes, n_loss_nodes = 0 being
+ * Ceres' NULL loss.  Accepted: ONE leaf of the kinds GSFM_LOSS_TRIVIAL (Theia's TRIVIAL), GSFM_LOSS_HUBER (p0 = a; the reference's YAML:
+ * HUBER, width 10), GSFM_LOSS_SOFT_L1, GSFM_LOSS_TUKEY, GSFM_LOSS_GEMAN_MCCLURE; a width (p0) that is not positive, a parameter that is
+ * not finite, every other leaf (MAGSAC among them) and every program of more than one node are GSFM_ERR_INVALID_ARG.
+ *
+ * Per track that has status 0 after step 4, with the midpoint X_0:
+ *   parameters  the three inhomogeneous coordinates X.  DEPARTURE: Theia optimises the homogeneous 4-vector without a local
+ *               parameterisation; its scale direction is a gauge of the cost, so the minimiser is the same projective point.
+ *   residual    per observation in an estimated view, in the track's order: p = R (X - o), r = (f p_x / p_z + u - x, f p_y / p_z + v - y),
+ *               s = |r|^2; cost = 1/2 sum rho(s).  Jacobian J = (f / p_z) [[1, 0, -p_x / p_z], [0, 1, -p_y / p_z]] R.  Robustified by
+ *               Ceres' Corrector (corrector.cc): with (rho, rho', rho'')(s), J <- sqrt(rho') (J - alpha / s r r^T J), r <- sqrt(rho') /
+ *               (1 - alpha) r, alpha = 1 - sqrt(1 + 2 s rho'' / rho') where s > 0 and rho'' > 0, else alpha = 0.
+ *   a pass      at a point: the ten sums S = J^T J (xx xy xz yy yz zz), g = J^T r (x y z) and the cost, of the corrected J and r.
+ *   start       pass at X_0.  Jacobi scaling c_k = 1 / (1 + sqrt(S_kk)), kept for the whole solve.  radius = initial_trust_region_radius,
+ *               decrease factor 2, iteration count 0.  A cost that is not finite: FAILURE.  max |g_k| <= gradient_tolerance: GRADIENT_
+ *               TOLERANCE.  max_num_iterations = 0: NO_CONVERGENCE.  (In this order; the termination codes are gsfm_rot_termination's.)
+ *   iteration   count += 1.  In the scaled space A = diag(c) S diag(c), b = diag(c) g, D2_k = min(max(A_kk, 1e-6), 1e32):
+ *               (A + diag(D2) / radius) e = -b by the 3 x 3 Cholesky of step 4 (pivots as there), d = diag(c) e.
+ *               model change m = -d . g - 1/2 d^T S d  (= -(J d)^T (r + J d / 2)).  A pivot that is not positive or not finite, or an m
+ *               that is not finite or not > 0, or a trial cost (pass at X + d) that is not finite, is an INVALID step: the fifth in
+ *               a row is FAILURE, otherwise radius /= decrease factor, decrease factor *= 2.
+ *               Valid step: |d| <= parameter_tolerance (|X| + parameter_tolerance): PARAMETER_TOLERANCE.  Else |cost - trial cost| <=
+ *               function_tolerance cost: FUNCTION_TOLERANCE.  (A terminating step is not applied.)  Else q = (cost - trial cost) / m:
+ *               q > min_relative_decrease accepts -- X += d, the trial's pass is the iterate's, radius = min(max_trust_region_radius,
+ *               radius / max(1/3, 1 - (2 q - 1)^3)), decrease factor = 2; otherwise radius /= decrease factor, decrease factor *= 2.
+ *               Then: count >= max_num_iterations: NO_CONVERGENCE; else after an accepted step max |g_k| <= gradient_tolerance:
+ *               GRADIENT_TOLERANCE; else radius <= min_trust_region_radius: FAILURE.
+ *               These are the rules of Ceres 1.14's TrustRegionMinimizer with the LEVENBERG_MARQUARDT strategy, as gsfm_rot_solve and
+ *               gsfm_pos_solve restate them.  DEPARTURES: Theia's solve is DENSE_QR on the 2n x 4 Jacobian where this solves the
+ *               normal equations; Theia rotates with AngleAxisRotatePoint where p is formed with the matrix R, as in step 5.
+ *   status      FAILURE is the new status 6, "refinement failed" (Theia: !summary.success; the track is dropped and counted nowhere in its
+ *               log): point and mean are zero.  Every other termination goes on to step 5 with the refined X; 0, 4 and 5 mean what they
+ *               mean above.
+ * options->refine = 0 skips all of this: the call is gsfm_tracks_triangulate's, with its kernels and its bytes.  options = NULL: the
+ * defaults, gsfm_tracks_refine_default_options (refine = 1; the tolerances of Theia's BundleAdjustmentOptions and of Ceres).
+ * max_num_iterations is clamped to 0 .. 1000.  Tolerances that are negative or not finite, radii that are not positive and finite (the
+ * minimum may be 0): GSFM_ERR_INVALID_ARG.
+ *
+ * Order of the sums (part of the definition).  The ten sums of a pass are taken exactly like those of steps 4 and 5: lane l of the
+ * track's group of G lanes adds the terms of the observations at places l, l + G, ... in that order, starting from 0 (the cost's term is
+ * rho(s) / 2), then the xor butterfly.  Every scalar decision is taken on the butterfly's sums, which are the same in all lanes: a track's
+ * iterates depend on its own length and data alone, whatever shares its wavefront -- two calls return the same bytes, permuting the tracks
+ * permutes the outputs bit for bit, and a track run alone returns what it returns inside a batch.
+ *
+ * Outputs: those of gsfm_tracks_triangulate, and optional (NULL: not returned) per track iterations_out (the count), initial_cost_out (the
+ * cost at X_0), final_cost_out (the cost at the X that went to step 5), termination_out (gsfm_rot_termination) -- 0, 0, 0 and -1 for a
+ * track that was not refined (status 1, 2, 3, or refine = 0); counts_out[7] (tracks per status).  Device memory: 24 B per track more. */
+typedef struct {
+  int32_t refine;                      /* 0: no refinement */
+  int32_t max_num_iterations;          /* 100 */
+  double function_tolerance;           /* 1e-6 */
+  double gradient_tolerance;           /* 1e-10 */
+  double parameter_tolerance;          /* 1e-8 */
+  double min_relative_decrease;        /* 1e-3 */
+  double initial_trust_region_radius;  /* 1e4 */
+  double max_trust_region_radius;      /* 1e12 (Theia's BundleAdjustmentOptions) */
+  double min_trust_region_radius;      /* 1e-32 */
+} gsfm_tracks_refine_options;
+
+void gsfm_tracks_refine_default_options(gsfm_tracks_refine_options* options);
+
+gsfm_status gsfm_tracks_triangulate_refine(uint32_t n_cams, const double* rot_aa, const double* cam_pos, const double* intrinsics,
+                                           const uint8_t* cam_estimated, uint64_t n_tracks, const uint64_t* track_ptr, const uint32_t* obs_cam,
+                                           const double* obs_xy, double min_triangulation_angle_degrees, double max_reprojection_error_pixels,
+                                           const gsfm_tracks_refine_options* options, const gsfm_loss_node* loss_program, int32_t n_loss_nodes,
+                                           double* point_out, int32_t* status_out, int32_t* n_views_out, double* mean_sq_err_out,
+                                           int32_t* iterations_out, double* initial_cost_out, double* final_cost_out, int32_t* termination_out,
+                                           uint64_t* counts_out, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
