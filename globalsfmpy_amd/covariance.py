@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from .solver import SolverError, _dp
+from .solver import _dp, _raise_if_failed
 
 
 def _call(fn, match_ptr, matches, intrinsics, rot, trans, max_iterations, with_ms):
@@ -30,8 +30,7 @@ def estimate_rotation_covariances(match_ptr, matches, intrinsics, rot, trans, ma
     """Device path. Returns dict(cov (E,3,3), rotation, translation, status, iterations, kernel_ms)."""
     lib = _abi.load_library()
     code, out = _call(lib.gsfm_cov_estimate, match_ptr, matches, intrinsics, rot, trans, max_iterations, True)
-    if code != 0:
-        raise SolverError("gsfm_cov_estimate failed with status %d: %s" % (code, lib.gsfm_last_error().decode("utf-8", "replace")))
+    _raise_if_failed(lib, "gsfm_cov_estimate", code)
     return out
 
 

@@ -1,7 +1,9 @@
 // C-ABI implementation (include/gsfm_rot.h): problem assembly, Levenberg-Marquardt control with
 // Ceres 1.14 trust-region semantics, block-Jacobi PCG orchestration.  All arithmetic on the edges
 // and cameras runs in the kernels of kernels.hpp; the host only sequences launches and reads a
-// handful of scalars per LM iteration.  Built with hipcc --offload-arch=gfx950 into libgsfm_rot.so.
+// handful of scalars per LM iteration.  The one-shot calls (host arrays in, host arrays out) are
+// one line each here: their bodies are the *_impl functions of the headers below, all on the
+// scratch owner of flat_call.hpp.  Built with hipcc --offload-arch=gfx950 into libgsfm_rot.so.
 #include "host_common.hpp"
 #include "solver_launch.hpp"
 #include "solver_pcg.hpp"
@@ -9,7 +11,10 @@
 #include "solver_components.hpp"
 #include "solver_lm.hpp"
 #include "problem_create.hpp"
+#include "edge_norms.hpp"
 #include "spanning_tree.hpp"
+#include "dense_check.hpp"
+#include "cov_estimate.hpp"
 #include "solver_pos.hpp"
 #include "trans_filter.hpp"
 #include "trans_refine.hpp"
@@ -337,82 +342,31 @@ gsfm_status gsfm_rot_loss_eval(gsfm_rot_problem* P, const double* s, uint64_t n,
 gsfm_status gsfm_rot_edge_sq_norms(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j, const double* rel_aa,
                                    const double* cov6, const double* rot_aa, double max_sq_norm, double* s_out, uint8_t* keep_out,
                                    uint64_t* n_kept, double* kernel_ms) {
-  if (n_cams == 0 || n_edges == 0) { if (n_kept) *n_kept = 0; return GSFM_OK; }
-  if (!edge_i || !edge_j || !rel_aa || !rot_aa || !s_out) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
-  for (uint64_t e = 0; e < n_edges; ++e) if (edge_i[e] >= n_cams || edge_j[e] >= n_cams) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "edge with an out-of-range camera index");
-  // (no host fallback: like every entry point of this library the sweep runs on the device or fails loudly)
-  if (const char* why = no_device_reason("the edge sweep")) return (gsfm_status)fail(GSFM_ERR_NO_DEVICE, why);
-  // One device slab, one private stream, stream-ordered copies: no hipDeviceSynchronize (it would stall every problem's stream of the
-  // process) and nothing to leak on an error path (the guard below owns stream, events and slab).
-  struct Guard {
-    hipStream_t s = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr; void* slab = nullptr;
-    ~Guard() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); if (slab) (void)hipFree(slab); if (s) (void)hipStreamDestroy(s); }
-  } G;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t o_i = 0, o_j = o_i + up(4 * n_edges), o_rel = o_j + up(4 * n_edges), o_cov = o_rel + up(24 * n_edges), o_rot = o_cov + (cov6 ? up(48 * n_edges) : 0),
-               o_s = o_rot + up(24 * (size_t)n_cams), o_q = o_s + up(8 * n_edges), o_keep = o_q + up(32 * (size_t)n_cams), o_cnt = o_keep + (keep_out ? up(n_edges) : 0), total = o_cnt + 256;
-  HIPCHK_S(hipStreamCreateWithFlags(&G.s, hipStreamNonBlocking));
-  HIPCHK_S(hipEventCreate(&G.e0)); HIPCHK_S(hipEventCreate(&G.e1));
-  if (hipMalloc(&G.slab, total) != hipSuccess) { G.slab = nullptr; return (gsfm_status)fail(GSFM_ERR_HIP, "allocating the edge sweep buffers failed"); }
-  char* base = (char*)G.slab;
-  HIPCHK_S(hipMemcpyAsync(base + o_i, edge_i, 4 * n_edges, hipMemcpyHostToDevice, G.s)); HIPCHK_S(hipMemcpyAsync(base + o_j, edge_j, 4 * n_edges, hipMemcpyHostToDevice, G.s));
-  HIPCHK_S(hipMemcpyAsync(base + o_rel, rel_aa, 24 * n_edges, hipMemcpyHostToDevice, G.s)); HIPCHK_S(hipMemcpyAsync(base + o_rot, rot_aa, 24 * (size_t)n_cams, hipMemcpyHostToDevice, G.s));
-  if (cov6) HIPCHK_S(hipMemcpyAsync(base + o_cov, cov6, 48 * n_edges, hipMemcpyHostToDevice, G.s));
-  HIPCHK_S(hipMemsetAsync(base + o_cnt, 0, 8, G.s));
-  hipLaunchKernelGGL(k_cam_cache, dim3(grid_for(n_cams)), dim3(GSFM_BLOCK), 0, G.s, (const double*)(base + o_rot), n_cams, 3, (double2*)(base + o_q));
-  EdgeSweepArgs a{};
-  a.n = n_edges; a.ei = (const uint32_t*)(base + o_i); a.ej = (const uint32_t*)(base + o_j); a.rel_aa = (const double*)(base + o_rel); a.cov6 = cov6 ? (const double*)(base + o_cov) : nullptr;
-  a.q = (const double2*)(base + o_q); a.max_sq = max_sq_norm; a.s_out = (double*)(base + o_s); a.keep = keep_out ? (uint8_t*)(base + o_keep) : nullptr; a.n_kept = (unsigned long long*)(base + o_cnt);
-  HIPCHK_S(hipEventRecord(G.e0, G.s));
-  hipLaunchKernelGGL(k_edge_sweep, dim3(grid_for(n_edges)), dim3(GSFM_BLOCK), 0, G.s, a);
-  HIPCHK_S(hipEventRecord(G.e1, G.s));
-  HIPCHK_S(hipMemcpyAsync(s_out, base + o_s, 8 * n_edges, hipMemcpyDeviceToHost, G.s));
-  if (keep_out) HIPCHK_S(hipMemcpyAsync(keep_out, base + o_keep, n_edges, hipMemcpyDeviceToHost, G.s));
-  unsigned long long cnt = 0;
-  HIPCHK_S(hipMemcpyAsync(&cnt, base + o_cnt, 8, hipMemcpyDeviceToHost, G.s));
-  HIPCHK_S(hipStreamSynchronize(G.s));
-  HIPCHK_S(hipGetLastError());
-  float ms = 0; (void)hipEventElapsedTime(&ms, G.e0, G.e1);
-  if (kernel_ms) *kernel_ms = ms;
-  if (n_kept) *n_kept = keep_out ? (uint64_t)cnt : n_edges;
-  return GSFM_OK;
+  return guarded("the edge sweep", edge_sq_norms_impl, n_cams, n_edges, edge_i, edge_j, rel_aa, cov6, rot_aa, max_sq_norm, s_out, keep_out, n_kept,
+                 kernel_ms);
 }
 
 gsfm_status gsfm_rot_init_spanning_tree(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j, const double* rel_aa,
                                         const int32_t* weight, double* rot_aa_out, int64_t* parent_edge_out, uint32_t* root_out,
                                         uint32_t* n_tree_cams_out, uint32_t* depth_out, double* kernel_ms) {
-  // (host vectors of O(E) / O(n) and host threads: an exception must not cross the C boundary)
-  try {
-    return init_spanning_tree_impl(n_cams, n_edges, edge_i, edge_j, rel_aa, weight, rot_aa_out, parent_edge_out, root_out, n_tree_cams_out, depth_out, kernel_ms);
-  } catch (const std::exception& e) {
-    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("spanning-tree initialisation ran out of host resources: ") + e.what());
-  }
+  return guarded("spanning-tree initialisation", init_spanning_tree_impl, n_cams, n_edges, edge_i, edge_j, rel_aa, weight, rot_aa_out,
+                 parent_edge_out, root_out, n_tree_cams_out, depth_out, kernel_ms);
 }
 
 gsfm_status gsfm_pos_filter_relative_translations(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j, const double* rel_t,
                                                   const double* rot_aa, int32_t n_axes, const double* axes, uint64_t seed, double tolerance,
                                                   double* bad_weight_out, uint8_t* keep_out, uint64_t* n_kept, double* stats_out, double* axes_out,
                                                   double* proj_out, uint32_t* num_passes_out, uint32_t* num_picks_out, double* kernel_ms) {
-  // (host vectors of O(E) and host threads: an exception must not cross the C boundary)
-  try {
-    return trans_filter_impl(n_cams, n_edges, edge_i, edge_j, rel_t, rot_aa, n_axes, axes, seed, tolerance, bad_weight_out, keep_out, n_kept, stats_out,
-                             axes_out, proj_out, num_passes_out, num_picks_out, kernel_ms);
-  } catch (const std::exception& e) {
-    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the translation filter ran out of host resources: ") + e.what());
-  }
+  return guarded("the translation filter", trans_filter_impl, n_cams, n_edges, edge_i, edge_j, rel_t, rot_aa, n_axes, axes, seed, tolerance,
+                 bad_weight_out, keep_out, n_kept, stats_out, axes_out, proj_out, num_passes_out, num_picks_out, kernel_ms);
 }
 
 gsfm_status gsfm_pos_refine_relative_translations(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j,
                                                   const uint64_t* match_ptr, const double* matches, const double* intrinsics,
                                                   const double* rot_aa, const double* rel_t_in, double* rel_t_out, int32_t* status_out,
                                                   int32_t* iters_out, double* cost_out, double* kernel_ms) {
-  // (a host vector of O(E): an exception must not cross the C boundary)
-  try {
-    return trans_refine_impl(n_cams, n_edges, edge_i, edge_j, match_ptr, matches, intrinsics, rot_aa, rel_t_in, rel_t_out, status_out, iters_out,
-                             cost_out, kernel_ms);
-  } catch (const std::exception& e) {
-    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the translation refinement ran out of host resources: ") + e.what());
-  }
+  return guarded("the translation refinement", trans_refine_impl, n_cams, n_edges, edge_i, edge_j, match_ptr, matches, intrinsics, rot_aa, rel_t_in,
+                 rel_t_out, status_out, iters_out, cost_out, kernel_ms);
 }
 
 gsfm_status gsfm_tracks_triangulate(uint32_t n_cams, const double* rot_aa, const double* cam_pos, const double* intrinsics,
@@ -420,13 +374,9 @@ gsfm_status gsfm_tracks_triangulate(uint32_t n_cams, const double* rot_aa, const
                                     const double* obs_xy, double min_triangulation_angle_degrees, double max_reprojection_error_pixels,
                                     double* point_out, int32_t* status_out, int32_t* n_views_out, double* mean_sq_err_out,
                                     uint64_t* counts_out, double* kernel_ms) {
-  // (a host vector of O(n_tracks): an exception must not cross the C boundary)
-  try {
-    return tri_impl(n_cams, rot_aa, cam_pos, intrinsics, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy, min_triangulation_angle_degrees,
-                    max_reprojection_error_pixels, point_out, status_out, n_views_out, mean_sq_err_out, counts_out, kernel_ms);
-  } catch (const std::exception& e) {
-    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the track triangulation ran out of host resources: ") + e.what());
-  }
+  return guarded("the track triangulation", tri_impl, n_cams, rot_aa, cam_pos, intrinsics, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy,
+                 min_triangulation_angle_degrees, max_reprojection_error_pixels, point_out, status_out, n_views_out, mean_sq_err_out, counts_out,
+                 kernel_ms, nullptr);
 }
 
 void gsfm_tracks_refine_default_options(gsfm_tracks_refine_options* o) {
@@ -443,27 +393,20 @@ gsfm_status gsfm_tracks_triangulate_refine(uint32_t n_cams, const double* rot_aa
                                            double* point_out, int32_t* status_out, int32_t* n_views_out, double* mean_sq_err_out,
                                            int32_t* iterations_out, double* initial_cost_out, double* final_cost_out, int32_t* termination_out,
                                            uint64_t* counts_out, double* kernel_ms) {
-  // (a host vector of O(n_tracks): an exception must not cross the C boundary)
-  try {
-    return tri_refine_impl(n_cams, rot_aa, cam_pos, intrinsics, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy, min_triangulation_angle_degrees,
-                           max_reprojection_error_pixels, options, loss_program, n_loss_nodes, point_out, status_out, n_views_out, mean_sq_err_out,
-                           iterations_out, initial_cost_out, final_cost_out, termination_out, counts_out, kernel_ms);
-  } catch (const std::exception& e) {
-    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the track refinement ran out of host resources: ") + e.what());
-  }
+  return guarded("the track refinement", tri_refine_impl, n_cams, rot_aa, cam_pos, intrinsics, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy,
+                 min_triangulation_angle_degrees, max_reprojection_error_pixels, options, loss_program, n_loss_nodes, point_out, status_out,
+                 n_views_out, mean_sq_err_out, iterations_out, initial_cost_out, final_cost_out, termination_out, counts_out, kernel_ms);
 }
 
 gsfm_status gsfm_tracks_launch_order(uint64_t n_tracks, const uint64_t* track_ptr, uint32_t* order_out, uint64_t* class_begin_out) {
-  if (!class_begin_out || (n_tracks > 0 && (!track_ptr || !order_out))) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
-  if (n_tracks >= (1ull << 31)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "problem too large (2^31 tracks)");
-  for (uint64_t t = 0; t < n_tracks; ++t)
-    if (track_ptr[t + 1] < track_ptr[t]) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "track_ptr decreases at track " + std::to_string(t));
-  try {
+  return guarded("the launch order", [&] {   // (the messages' strings, stable_sort's buffer)
+    if (!class_begin_out || (n_tracks > 0 && (!track_ptr || !order_out))) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
+    if (n_tracks >= (1ull << 31)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "problem too large (2^31 tracks)");
+    for (uint64_t t = 0; t < n_tracks; ++t)
+      if (track_ptr[t + 1] < track_ptr[t]) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "track_ptr decreases at track " + std::to_string(t));
     tri_bucket(n_tracks, track_ptr, order_out, class_begin_out);
-  } catch (const std::exception& e) {   // (stable_sort's buffer)
-    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string("the launch order ran out of host resources: ") + e.what());
-  }
-  return GSFM_OK;
+    return GSFM_OK;
+  });
 }
 
 int64_t gsfm_rot_count_components(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j) {
@@ -633,87 +576,7 @@ gsfm_status gsfm_rot_trial_lin_check(gsfm_rot_problem* P, const double* rot, con
 
 gsfm_status gsfm_rot_dense_factor_check(int32_t schedule, uint32_t n_items, const uint32_t* n, const double* A, const double* b, const int32_t* active,
                                         double* x_out, double* L_out, int32_t* info_out) {
-  if (!n || !A || !b || !x_out || !info_out || n_items == 0) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument or no matrix");
-  if (schedule < 0 || schedule > 2) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "schedule: 0 (look2), 1 (fused) or 2 (batch)");
-  if (schedule != 2 && (n_items != 1 || active)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "the single schedules take one matrix and no activity flags");
-  // the product's own limits: the single step up to GSFM_DENSE_MAX_T block rows (GSFM_CHOL_FUSED_MAX_T fused), a batch item up to dense_cholesky_max_cams cameras
-  const uint32_t maxT = schedule == 0 ? GSFM_DENSE_MAX_T : schedule == 1 ? GSFM_CHOL_FUSED_MAX_T : 0;
-  const uint64_t max_n = schedule == 2 ? 3 * (uint64_t)std::max(default_options().dense_cholesky_max_cams, 0) : (uint64_t)maxT * GSFM_CB;
-  for (uint32_t i = 0; i < n_items; ++i) {
-    if (n[i] == 0) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "a matrix with no unknowns");
-    if (n[i] > max_n) return (gsfm_status)fail(GSFM_ERR_UNSUPPORTED, "matrix beyond the size the exact step supports on this schedule");
-  }
-  if (const char* why = no_device_reason("the dense factorisation check")) return (gsfm_status)fail(GSFM_ERR_NO_DEVICE, why);
-  // host side of the assembly kernels' layout (k_dense_assemble, k_comp_assemble): the lower triangle in tiles, identity on the padding
-  // diagonal n .. 32 T - 1, the right-hand side in the first row of block row T; then one slab: A of all items, L, x, info, activity, items
-  std::vector<uint32_t> T(n_items);
-  std::vector<size_t> offA(n_items), offL(n_items), offX(n_items), offIn(n_items);
-  size_t words = 0, in_words = 0;
-  uint32_t Tmax = 0;
-  for (uint32_t i = 0; i < n_items; ++i) { T[i] = (n[i] + GSFM_CB - 1) / GSFM_CB; Tmax = std::max(Tmax, T[i]); offA[i] = words; words += chol_num_tiles(T[i]) * GSFM_TILE_ELEMS; offIn[i] = in_words; in_words += (size_t)n[i] * n[i]; }
-  const size_t a_words = words;
-  for (uint32_t i = 0; i < n_items; ++i) { offL[i] = words; words += chol_num_tiles(T[i]) * GSFM_TILE_ELEMS; }
-  for (uint32_t i = 0; i < n_items; ++i) { offX[i] = words; words += (size_t)T[i] * GSFM_CB; }
-  std::vector<double> hA;
-  try { hA.assign(a_words, 0.0); } catch (const std::exception&) { return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "out of host memory"); }
-  size_t b_off = 0;
-  for (uint32_t i = 0; i < n_items; ++i) {
-    double* At = hA.data() + offA[i];
-    const double* Ai = A + offIn[i];
-    auto elem = [&](uint32_t g, uint32_t h) -> double& { return At[chol_tile_off(g / GSFM_CB, h / GSFM_CB) + (g % GSFM_CB) * GSFM_CB + h % GSFM_CB]; };
-    for (uint32_t g = 0; g < n[i]; ++g) for (uint32_t h = 0; h <= g; ++h) elem(g, h) = Ai[(size_t)g * n[i] + h];
-    for (uint32_t g = n[i]; g < T[i] * GSFM_CB; ++g) elem(g, g) = 1.0;
-    for (uint32_t g = 0; g < n[i]; ++g) At[chol_tile_off(T[i], g / GSFM_CB) + g % GSFM_CB] = b[b_off + g];
-    b_off += n[i];
-  }
-  struct Guard {
-    hipStream_t s = nullptr; void* slab = nullptr;
-    ~Guard() { if (slab) (void)hipFree(slab); if (s) (void)hipStreamDestroy(s); }
-  } G;
-  auto up = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
-  const size_t o_info = up(8 * words), o_act = o_info + up(4 * (size_t)n_items), o_items = o_act + up(4 * (size_t)n_items), total = o_items + up(sizeof(CholBatchItem) * n_items);
-  HIPCHK_S(hipStreamCreateWithFlags(&G.s, hipStreamNonBlocking));
-  if (hipMalloc(&G.slab, total) != hipSuccess) { G.slab = nullptr; return (gsfm_status)fail(GSFM_ERR_HIP, "allocating the factorisation check buffers failed"); }
-  char* base = (char*)G.slab;
-  double* dw = (double*)base;
-  int* dinfo = (int*)(base + o_info);
-  int* dact = (int*)(base + o_act);
-  HIPCHK_S(hipMemsetAsync(base, 0, total, G.s));
-  HIPCHK_S(hipMemcpyAsync(dw, hA.data(), 8 * a_words, hipMemcpyHostToDevice, G.s));
-  if (schedule == 2) {
-    std::vector<int> act(n_items, 1);
-    if (active) for (uint32_t i = 0; i < n_items; ++i) act[i] = active[i] != 0;
-    std::vector<CholBatchItem> items(n_items);
-    for (uint32_t i = 0; i < n_items; ++i) items[i] = CholBatchItem{dw + offA[i], dw + offL[i], dw + offX[i], T[i], n[i], dinfo + i, dact + i};
-    HIPCHK_S(hipMemcpyAsync(dact, act.data(), 4 * (size_t)n_items, hipMemcpyHostToDevice, G.s));
-    HIPCHK_S(hipMemcpyAsync(base + o_items, items.data(), sizeof(CholBatchItem) * n_items, hipMemcpyHostToDevice, G.s));
-    HIPCHK_S(hipStreamSynchronize(G.s));   // (the staging vectors die with this scope)
-    enqueue_chol_batch((const CholBatchItem*)(base + o_items), n_items, Tmax, G.s, false);
-  } else {
-    enqueue_chol_solve(dw + offA[0], dw + offL[0], dw + offX[0], n[0], T[0], dinfo, G.s, schedule == 1);
-  }
-  HIPCHK_S(hipGetLastError());
-  std::vector<double> hw(words - a_words);
-  std::vector<int> hinfo(n_items);
-  HIPCHK_S(hipMemcpyAsync(hw.data(), dw + a_words, 8 * hw.size(), hipMemcpyDeviceToHost, G.s));
-  HIPCHK_S(hipMemcpyAsync(hinfo.data(), dinfo, 4 * (size_t)n_items, hipMemcpyDeviceToHost, G.s));
-  HIPCHK_S(hipStreamSynchronize(G.s));
-  HIPCHK_S(hipGetLastError());
-  size_t x_off = 0, l_off = 0;
-  for (uint32_t i = 0; i < n_items; ++i) {
-    info_out[i] = hinfo[i];
-    const double* Lt = hw.data() + (offL[i] - a_words);
-    const double* xt = hw.data() + (offX[i] - a_words);
-    for (uint32_t g = 0; g < n[i]; ++g) x_out[x_off + g] = xt[g];
-    x_off += n[i];
-    if (L_out) {
-      double* Li = L_out + l_off;
-      for (uint32_t g = 0; g < n[i]; ++g) for (uint32_t h = 0; h < n[i]; ++h)
-        Li[(size_t)g * n[i] + h] = h <= g ? Lt[chol_tile_off(g / GSFM_CB, h / GSFM_CB) + (g % GSFM_CB) * GSFM_CB + h % GSFM_CB] : 0.0;
-      l_off += (size_t)n[i] * n[i];
-    }
-  }
-  return GSFM_OK;
+  return guarded("the dense factorisation check", dense_factor_check_impl, schedule, n_items, n, A, b, active, x_out, L_out, info_out);
 }
 
 gsfm_status gsfm_rot_time_kernels(gsfm_rot_problem* P, const double* rot, int32_t reps, double* out_ms4) {
@@ -781,43 +644,8 @@ gsfm_status gsfm_rot_sweep_bytes(gsfm_rot_problem* P, double* algorithmic, doubl
 gsfm_status gsfm_cov_estimate(uint64_t n_edges, const uint64_t* match_ptr, const double* matches, const double* intrinsics,
                               const double* rot_in, const double* trans_in, int32_t max_iterations, double* cov9_out,
                               double* rot_out, double* trans_out, int32_t* status_out, int32_t* iters_out, double* kernel_ms) {
-  if (!match_ptr || !matches || !intrinsics || !rot_in || !trans_in || !cov9_out || !rot_out || !trans_out || !status_out)
-    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
-  if (n_edges == 0) return GSFM_OK;
-  if (const char* why = no_device_reason("the covariance estimator")) return (gsfm_status)fail(GSFM_ERR_NO_DEVICE, why);
-  const uint64_t n_matches = match_ptr[n_edges];
-  for (uint64_t e = 0; e < n_edges; ++e) if (match_ptr[e + 1] < match_ptr[e]) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "match_ptr must be non-decreasing");
-  DevBuf<uint64_t> d_ptr; DevBuf<double4> d_m; DevBuf<double> d_K, d_r, d_t, d_cov, d_ro, d_to; DevBuf<int> d_st, d_it;
-  bool ok = d_ptr.alloc(n_edges + 1) == hipSuccess && d_m.alloc(std::max<uint64_t>(n_matches, 1)) == hipSuccess && d_K.alloc(6 * n_edges) == hipSuccess &&
-            d_r.alloc(3 * n_edges) == hipSuccess && d_t.alloc(3 * n_edges) == hipSuccess && d_cov.alloc(9 * n_edges) == hipSuccess &&
-            d_ro.alloc(3 * n_edges) == hipSuccess && d_to.alloc(3 * n_edges) == hipSuccess && d_st.alloc(n_edges) == hipSuccess && d_it.alloc(n_edges) == hipSuccess;
-  if (!ok) return (gsfm_status)fail(GSFM_ERR_HIP, "allocating covariance buffers failed");
-  HIPCHK_S(hipMemcpy(d_ptr.p, match_ptr, 8 * (n_edges + 1), hipMemcpyHostToDevice));
-  if (n_matches) HIPCHK_S(hipMemcpy(d_m.p, matches, 32 * n_matches, hipMemcpyHostToDevice));
-  HIPCHK_S(hipMemcpy(d_K.p, intrinsics, 48 * n_edges, hipMemcpyHostToDevice));
-  HIPCHK_S(hipMemcpy(d_r.p, rot_in, 24 * n_edges, hipMemcpyHostToDevice));
-  HIPCHK_S(hipMemcpy(d_t.p, trans_in, 24 * n_edges, hipMemcpyHostToDevice));
-  CovArgs a{};
-  a.n_edges = n_edges; a.match_ptr = d_ptr.p; a.matches = d_m.p; a.intr = d_K.p; a.rot_in = d_r.p; a.trans_in = d_t.p;
-  a.max_iterations = max_iterations; a.cov9 = d_cov.p; a.rot_out = d_ro.p; a.trans_out = d_to.p; a.status = d_st.p; a.iters = d_it.p;
-  hipEvent_t e0, e1;
-  HIPCHK_S(hipEventCreate(&e0)); HIPCHK_S(hipEventCreate(&e1));
-  const int grid = (int)((n_edges + (GSFM_BLOCK / 64) - 1) / (GSFM_BLOCK / 64));
-  HIPCHK_S(hipEventRecord(e0, 0));
-  hipLaunchKernelGGL(k_cov_estimate, dim3(grid), dim3(GSFM_BLOCK), 0, 0, a);
-  HIPCHK_S(hipEventRecord(e1, 0));
-  HIPCHK_S(hipDeviceSynchronize());
-  HIPCHK_S(hipGetLastError());
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  if (kernel_ms) *kernel_ms = ms;
-  HIPCHK_S(hipMemcpy(cov9_out, d_cov.p, 72 * n_edges, hipMemcpyDeviceToHost));
-  HIPCHK_S(hipMemcpy(rot_out, d_ro.p, 24 * n_edges, hipMemcpyDeviceToHost));
-  HIPCHK_S(hipMemcpy(trans_out, d_to.p, 24 * n_edges, hipMemcpyDeviceToHost));
-  HIPCHK_S(hipMemcpy(status_out, d_st.p, 4 * n_edges, hipMemcpyDeviceToHost));
-  if (iters_out) HIPCHK_S(hipMemcpy(iters_out, d_it.p, 4 * n_edges, hipMemcpyDeviceToHost));
-  return GSFM_OK;
+  return guarded("the covariance estimator", cov_estimate_impl, n_edges, match_ptr, matches, intrinsics, rot_in, trans_in, max_iterations, cov9_out,
+                 rot_out, trans_out, status_out, iters_out, kernel_ms);
 }
 
 int32_t gsfm_magsac_table(int32_t nu, double* out, int32_t cap) {

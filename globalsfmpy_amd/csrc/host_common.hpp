@@ -35,6 +35,17 @@ namespace {
 thread_local std::string g_err;
 int fail(gsfm_status st, const std::string& msg) { g_err = msg; return st; }
 
+// A C-ABI entry whose body allocates host vectors or starts host threads runs it through this, as guarded(who, body, the body's
+// arguments...): an exception (std::bad_alloc, std::system_error) must not cross the C boundary.
+template <typename F, typename... Args>
+gsfm_status guarded(const char* who, F&& body, Args&&... args) {
+  try {
+    return body(std::forward<Args>(args)...);
+  } catch (const std::exception& e) {
+    return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, std::string(who) + " ran out of host resources: " + e.what());
+  }
+}
+
 // NULL when a device is usable, else the message for GSFM_ERR_NO_DEVICE (kept in a thread-local buffer).
 const char* no_device_reason(const char* who) {
   int ndev = 0;

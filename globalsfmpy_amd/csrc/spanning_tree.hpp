@@ -1,7 +1,7 @@
-// Host side of gsfm_rot_init_spanning_tree (include/gsfm_rot.h): validation, one device slab, the launch sequence of tree_kernels.hpp.
+// Host side of gsfm_rot_init_spanning_tree (include/gsfm_rot.h): validation, one device slab (flat_call.hpp), the launch sequence of tree_kernels.hpp.
 // Part of libgsfm_rot.so's one translation unit (included from gsfm_rot.hip after host_common.hpp).
 #pragma once
-#include "host_common.hpp"
+#include "flat_call.hpp"
 #include "tree_kernels.hpp"
 
 namespace {
@@ -41,68 +41,56 @@ gsfm_status init_spanning_tree_impl(uint32_t n_cams, uint64_t n_edges, const uin
   }
   if (const char* why = no_device_reason("the spanning-tree initialisation")) return (gsfm_status)fail(GSFM_ERR_NO_DEVICE, why);
 
-  // One device slab, one private stream, stream-ordered copies, no hipDeviceSynchronize; the guard owns everything on every path.
-  struct Guard {
-    hipStream_t s = nullptr; hipEvent_t ev[6] = {}; void* slab = nullptr;
-    ~Guard() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); if (slab) (void)hipFree(slab); if (s) (void)hipStreamDestroy(s); }
-  } G;
   const size_t E = n_edges;
   const int R = ceil_log2(N) + 1;   // Boruvka rounds: the components that still have an outgoing edge at least halve every round
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += up(bytes); return o; };
-  const size_t o_i = take(4 * E), o_j = take(4 * E), o_w = weight ? take(4 * E) : 0, o_recA = take(16 * E), o_recB = take(16 * E),
-               o_cnt = take(4 * (size_t)(R + 2)), o_comp = take(4 * N), o_par = take(4 * N), o_best = take(8 * N), o_size = take(4 * N),
-               o_minv = take(4 * N), o_forest = take(4 * N), o_pick = take(8), o_sc = take(16), o_tlist = take(4 * N), o_head = take(4 * N),
-               o_link = take(8 * N), o_nxt0 = take(8 * N), o_nxt1 = take(8 * N), o_dist0 = take(8 * N), o_dist1 = take(8 * N),
-               o_P0 = take(4 * N), o_P1 = take(4 * N), o_D0 = take(4 * N), o_D1 = take(4 * N), o_A0 = take(32 * N), o_A1 = take(32 * N),
-               o_pe = take(4 * N), o_rel = take(24 * N), o_rot = take(24 * N), o_pout = take(8 * N), o_maxd = take(4), total = off;
-  HIPCHK_S(hipStreamCreateWithFlags(&G.s, hipStreamNonBlocking));
-  for (hipEvent_t& e : G.ev) HIPCHK_S(hipEventCreate(&e));
-  if (hipMalloc(&G.slab, total) != hipSuccess) { G.slab = nullptr; return (gsfm_status)fail(GSFM_ERR_HIP, "allocating the spanning-tree buffers failed"); }
-  char* base = (char*)G.slab;
-  auto U = [&](size_t o) { return (uint32_t*)(base + o); };
-  const hipStream_t s = G.s;
+  FlatLayout L;
+  const auto s_i = L.take<uint32_t>(E), s_j = L.take<uint32_t>(E); const auto s_w = L.take<int32_t>(weight ? E : 0);
+  const auto s_recA = L.take<MstEdge>(E), s_recB = L.take<MstEdge>(E);
+  const auto s_cnt = L.take<uint32_t>((size_t)(R + 2)), s_comp = L.take<uint32_t>(N), s_par = L.take<uint32_t>(N); const auto s_best = L.take<unsigned long long>(N);
+  const auto s_size = L.take<uint32_t>(N), s_minv = L.take<uint32_t>(N), s_forest = L.take<uint32_t>(N); const auto s_pick = L.take<unsigned long long>(1);
+  const auto s_sc = L.take<uint32_t>(4), s_tlist = L.take<uint32_t>(N), s_head = L.take<uint32_t>(N), s_link = L.take<uint32_t>(2 * N),
+             s_nxt0 = L.take<uint32_t>(2 * N), s_nxt1 = L.take<uint32_t>(2 * N), s_dist0 = L.take<uint32_t>(2 * N), s_dist1 = L.take<uint32_t>(2 * N),
+             s_P0 = L.take<uint32_t>(N), s_P1 = L.take<uint32_t>(N), s_D0 = L.take<uint32_t>(N), s_D1 = L.take<uint32_t>(N);
+  const auto s_A0 = L.take<Quat>(N), s_A1 = L.take<Quat>(N); const auto s_pe = L.take<uint32_t>(N);
+  const auto s_rel = L.take<double>(3 * N), s_rot = L.take<double>(3 * N); const auto s_pout = L.take<long long>(N); const auto s_maxd = L.take<uint32_t>(1);
+  FlatCall fc;
+  if (int st = fc.commit(L, "the spanning-tree initialisation", 3)) return (gsfm_status)st;
+  const hipStream_t s = fc.s;
   // 12 B per edge go up (the relative rotations of the n_c - 1 tree edges follow once the tree is known)
-  HIPCHK_S(hipMemcpyAsync(base + o_i, edge_i, 4 * E, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_j, edge_j, 4 * E, hipMemcpyHostToDevice, s));
-  if (weight) HIPCHK_S(hipMemcpyAsync(base + o_w, weight, 4 * E, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemsetAsync(base + o_cnt, 0, 4 * (size_t)(R + 2), s));
-  HIPCHK_S(hipMemsetAsync(base + o_best, 0, 8 * N, s));
-  HIPCHK_S(hipMemsetAsync(base + o_size, 0, 4 * N, s));
-  HIPCHK_S(hipMemsetAsync(base + o_minv, 0xff, 4 * N, s));
-  HIPCHK_S(hipMemsetAsync(base + o_head, 0xff, 4 * N, s));
-  HIPCHK_S(hipMemsetAsync(base + o_pick, 0, 8, s));
-  HIPCHK_S(hipMemsetAsync(base + o_sc, 0, 16, s));
-  HIPCHK_S(hipMemsetAsync(base + o_maxd, 0, 4, s));
-  const uint32_t* ei = U(o_i); const uint32_t* ej = U(o_j);
-  const int32_t* w = weight ? (const int32_t*)(base + o_w) : nullptr;
-  uint32_t* cnt = U(o_cnt); uint32_t* comp = U(o_comp); uint32_t* par = U(o_par); uint32_t* sc = U(o_sc);
-  unsigned long long* best = (unsigned long long*)(base + o_best);
-  MstEdge* rec[2] = {(MstEdge*)(base + o_recA), (MstEdge*)(base + o_recB)};
+  HIPCHK_S(fc.upload(s_i, edge_i, E)); HIPCHK_S(fc.upload(s_j, edge_j, E));
+  if (weight) HIPCHK_S(fc.upload(s_w, weight, E));
+  HIPCHK_S(fc.zero(s_cnt, (size_t)(R + 2))); HIPCHK_S(fc.zero(s_best, N)); HIPCHK_S(fc.zero(s_size, N));
+  HIPCHK_S(hipMemsetAsync(fc.ptr(s_minv), 0xff, 4 * N, s)); HIPCHK_S(hipMemsetAsync(fc.ptr(s_head), 0xff, 4 * N, s));
+  HIPCHK_S(fc.zero(s_pick, 1)); HIPCHK_S(fc.zero(s_sc, 4)); HIPCHK_S(fc.zero(s_maxd, 1));
+  const uint32_t* ei = fc.ptr(s_i); const uint32_t* ej = fc.ptr(s_j);
+  const int32_t* w = weight ? fc.ptr(s_w) : nullptr;
+  uint32_t* cnt = fc.ptr(s_cnt); uint32_t* comp = fc.ptr(s_comp); uint32_t* par = fc.ptr(s_par); uint32_t* sc = fc.ptr(s_sc);
+  unsigned long long* best = fc.ptr(s_best);
+  MstEdge* rec[2] = {fc.ptr(s_recA), fc.ptr(s_recB)};
+  uint32_t* size = fc.ptr(s_size); uint32_t* minv = fc.ptr(s_minv); uint32_t* forest = fc.ptr(s_forest); uint32_t* tlist_d = fc.ptr(s_tlist);
+  uint32_t* head = fc.ptr(s_head); uint32_t* link = fc.ptr(s_link); uint32_t* pe = fc.ptr(s_pe);
   const dim3 blk(256), gN(grid_for(N)), gE((unsigned)std::min<size_t>(grid_for(E), 4096));
 
   // ---- phase 1: the maximum spanning forest, the largest component, its tree edges --------------------------------------------------
-  HIPCHK_S(hipEventRecord(G.ev[0], s));
+  HIPCHK_S(fc.begin_span());
   hipLaunchKernelGGL(k_mst_init, gN, blk, 0, s, n_cams, comp);
   for (int r = 0; r <= R; ++r) {   // round R only counts the edges that still join two components: none, or the rounds were too few
     hipLaunchKernelGGL(k_mst_propose, gE, blk, 0, s, ei, ej, w, (uint64_t)E, r ? (const MstEdge*)rec[(r - 1) & 1] : nullptr, r ? (const uint32_t*)(cnt + r - 1) : nullptr,
                        (const uint32_t*)comp, best, rec[r & 1], cnt + r);
     if (r == R) break;
-    hipLaunchKernelGGL(k_mst_hook, gN, blk, 0, s, n_cams, ei, ej, (const uint32_t*)comp, (const unsigned long long*)best, par, U(o_forest), cnt + R + 1);
+    hipLaunchKernelGGL(k_mst_hook, gN, blk, 0, s, n_cams, ei, ej, (const uint32_t*)comp, (const unsigned long long*)best, par, forest, cnt + R + 1);
     hipLaunchKernelGGL(k_mst_jump, gN, blk, 0, s, n_cams, comp, par, best);
   }
-  hipLaunchKernelGGL(k_comp_count, gN, blk, 0, s, n_cams, (const uint32_t*)comp, U(o_size), U(o_minv));
-  hipLaunchKernelGGL(k_comp_pick, gN, blk, 0, s, n_cams, (const uint32_t*)comp, (const uint32_t*)U(o_size), (const uint32_t*)U(o_minv), (unsigned long long*)(base + o_pick));
-  hipLaunchKernelGGL(k_comp_chosen, dim3(1), dim3(1), 0, s, (const uint32_t*)comp, (const unsigned long long*)(base + o_pick), sc);
-  hipLaunchKernelGGL(k_tree_list, gN, blk, 0, s, (const uint32_t*)U(o_forest), (const uint32_t*)(cnt + R + 1), ei, ej, (const uint32_t*)comp, sc, U(o_tlist), U(o_head), U(o_link));
-  HIPCHK_S(hipEventRecord(G.ev[1], s));
+  hipLaunchKernelGGL(k_comp_count, gN, blk, 0, s, n_cams, (const uint32_t*)comp, size, minv);
+  hipLaunchKernelGGL(k_comp_pick, gN, blk, 0, s, n_cams, (const uint32_t*)comp, (const uint32_t*)size, (const uint32_t*)minv, fc.ptr(s_pick));
+  hipLaunchKernelGGL(k_comp_chosen, dim3(1), dim3(1), 0, s, (const uint32_t*)comp, (const unsigned long long*)fc.ptr(s_pick), sc);
+  hipLaunchKernelGGL(k_tree_list, gN, blk, 0, s, (const uint32_t*)forest, (const uint32_t*)(cnt + R + 1), ei, ej, (const uint32_t*)comp, sc, tlist_d, head, link);
+  HIPCHK_S(fc.end_span());
   std::vector<uint32_t> h_cnt((size_t)R + 2), h_sc(4), tlist(N);
-  HIPCHK_S(hipMemcpyAsync(h_cnt.data(), cnt, 4 * (size_t)(R + 2), hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipMemcpyAsync(h_sc.data(), sc, 16, hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipMemcpyAsync(tlist.data(), U(o_tlist), 4 * N, hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipStreamSynchronize(s));
-  HIPCHK_S(hipGetLastError());
+  HIPCHK_S(fc.download(h_cnt.data(), s_cnt, (size_t)(R + 2)));
+  HIPCHK_S(fc.download(h_sc.data(), s_sc, 4));
+  HIPCHK_S(fc.download(tlist.data(), s_tlist, N));
+  HIPCHK_S(fc.sync());
   if (h_cnt[R] != 0) return (gsfm_status)fail(GSFM_ERR_HIP, "spanning tree: edges between components remain after the last Boruvka round");
   const uint32_t root = h_sc[1], n_c = h_sc[2], m = h_sc[3];
   if (n_c < 2) { empty_outputs(); return (gsfm_status)fail(GSFM_ERR_EMPTY, "the largest connected component has one camera"); }
@@ -110,40 +98,35 @@ gsfm_status init_spanning_tree_impl(uint32_t n_cams, uint64_t n_edges, const uin
 
   // ---- phase 2: root the tree (Euler tour, list ranking) while the host gathers the tree edges' relative rotations ------------------
   const dim3 gD(grid_for(2 * (size_t)m)), gM(grid_for(m));
-  uint32_t* nxt[2] = {U(o_nxt0), U(o_nxt1)}; uint32_t* dist[2] = {U(o_dist0), U(o_dist1)};
-  HIPCHK_S(hipEventRecord(G.ev[2], s));
-  hipLaunchKernelGGL(k_tree_tour, gD, blk, 0, s, (const uint32_t*)sc, (const uint32_t*)U(o_tlist), ei, ej, (const uint32_t*)U(o_head), (const uint32_t*)U(o_link), nxt[0], dist[0]);
+  uint32_t* nxt[2] = {fc.ptr(s_nxt0), fc.ptr(s_nxt1)}; uint32_t* dist[2] = {fc.ptr(s_dist0), fc.ptr(s_dist1)};
+  HIPCHK_S(fc.begin_span());
+  hipLaunchKernelGGL(k_tree_tour, gD, blk, 0, s, (const uint32_t*)sc, (const uint32_t*)tlist_d, ei, ej, (const uint32_t*)head, (const uint32_t*)link, nxt[0], dist[0]);
   const int RR = ceil_log2(2 * (uint64_t)m);
   for (int r = 0; r < RR; ++r)
     hipLaunchKernelGGL(k_tree_rank, gD, blk, 0, s, (const uint32_t*)sc, (const uint32_t*)nxt[r & 1], (const uint32_t*)dist[r & 1], nxt[(r + 1) & 1], dist[(r + 1) & 1]);
-  HIPCHK_S(hipEventRecord(G.ev[3], s));
+  HIPCHK_S(fc.end_span());
   std::vector<double> rel((size_t)3 * m);
   for (uint32_t k = 0; k < m; ++k) { const double* a = rel_aa + 3 * (size_t)tlist[k]; rel[3 * (size_t)k] = a[0]; rel[3 * (size_t)k + 1] = a[1]; rel[3 * (size_t)k + 2] = a[2]; }
-  HIPCHK_S(hipMemcpyAsync(base + o_rel, rel.data(), 24 * (size_t)m, hipMemcpyHostToDevice, s));
+  HIPCHK_S(fc.upload(s_rel, rel.data(), 3 * (size_t)m));
 
   // ---- phase 3: orient, compose by pointer doubling, write out -------------------------------------------------------------------
-  uint32_t* P[2] = {U(o_P0), U(o_P1)}; uint32_t* D[2] = {U(o_D0), U(o_D1)}; Quat* A[2] = {(Quat*)(base + o_A0), (Quat*)(base + o_A1)};
-  HIPCHK_S(hipEventRecord(G.ev[4], s));
-  hipLaunchKernelGGL(k_tree_orient, gM, blk, 0, s, (const uint32_t*)sc, (const uint32_t*)U(o_tlist), ei, ej, (const uint32_t*)dist[RR & 1], (const double*)(base + o_rel),
-                     P[0], D[0], A[0], U(o_pe));
+  uint32_t* P[2] = {fc.ptr(s_P0), fc.ptr(s_P1)}; uint32_t* D[2] = {fc.ptr(s_D0), fc.ptr(s_D1)}; Quat* A[2] = {fc.ptr(s_A0), fc.ptr(s_A1)};
+  HIPCHK_S(fc.begin_span());
+  hipLaunchKernelGGL(k_tree_orient, gM, blk, 0, s, (const uint32_t*)sc, (const uint32_t*)tlist_d, ei, ej, (const uint32_t*)dist[RR & 1], (const double*)fc.ptr(s_rel),
+                     P[0], D[0], A[0], pe);
   const int RD = ceil_log2(n_c);
   for (int r = 0; r < RD; ++r)
     hipLaunchKernelGGL(k_tree_double, gN, blk, 0, s, n_cams, (const uint32_t*)comp, (const uint32_t*)sc, (const uint32_t*)P[r & 1], (const uint32_t*)D[r & 1],
                        (const Quat*)A[r & 1], P[(r + 1) & 1], D[(r + 1) & 1], A[(r + 1) & 1]);
   hipLaunchKernelGGL(k_tree_out, gN, blk, 0, s, n_cams, (const uint32_t*)comp, (const uint32_t*)sc, (const Quat*)A[RD & 1], (const uint32_t*)D[RD & 1],
-                     (const uint32_t*)U(o_pe), (const uint32_t*)U(o_tlist), (double*)(base + o_rot), (long long*)(base + o_pout), U(o_maxd));
-  HIPCHK_S(hipEventRecord(G.ev[5], s));
+                     (const uint32_t*)pe, (const uint32_t*)tlist_d, fc.ptr(s_rot), fc.ptr(s_pout), fc.ptr(s_maxd));
+  HIPCHK_S(fc.end_span());
   uint32_t maxd = 0;
-  HIPCHK_S(hipMemcpyAsync(rot_aa_out, base + o_rot, 24 * N, hipMemcpyDeviceToHost, s));
-  if (parent_edge_out) HIPCHK_S(hipMemcpyAsync(parent_edge_out, base + o_pout, 8 * N, hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipMemcpyAsync(&maxd, U(o_maxd), 4, hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipStreamSynchronize(s));
-  HIPCHK_S(hipGetLastError());
-  if (kernel_ms) {
-    float a = 0, b = 0, c = 0;
-    (void)hipEventElapsedTime(&a, G.ev[0], G.ev[1]); (void)hipEventElapsedTime(&b, G.ev[2], G.ev[3]); (void)hipEventElapsedTime(&c, G.ev[4], G.ev[5]);
-    *kernel_ms = (double)a + b + c;
-  }
+  HIPCHK_S(fc.download(rot_aa_out, s_rot, 3 * N));
+  if (parent_edge_out) HIPCHK_S(fc.download(parent_edge_out, s_pout, N));
+  HIPCHK_S(fc.download(&maxd, s_maxd, 1));
+  HIPCHK_S(fc.sync());
+  if (kernel_ms) *kernel_ms = fc.kernel_ms();
   if (root_out) *root_out = root;
   if (n_tree_cams_out) *n_tree_cams_out = n_c;
   if (depth_out) *depth_out = maxd;

@@ -1,7 +1,7 @@
 // Host side of gsfm_pos_filter_relative_translations (include/gsfm_pos.h): validation, the per-camera CSR, the axes' generator, one
-// device slab and the launch sequence of trans_filter_kernels.hpp.  Part of libgsfm_rot.so's one translation unit.
+// device slab (flat_call.hpp) and the launch sequence of trans_filter_kernels.hpp.  Part of libgsfm_rot.so's one translation unit.
 #pragma once
-#include "host_common.hpp"
+#include "flat_call.hpp"
 #include "spanning_tree.hpp"
 #include "trans_filter_kernels.hpp"
 #include "../../include/gsfm_pos.h"
@@ -81,10 +81,6 @@ gsfm_status trans_filter_impl(uint32_t n_cams, uint64_t n_edges, const uint32_t*
     }
   }
 
-  struct Guard {
-    hipStream_t s = nullptr; hipEvent_t ev[4] = {}; void* slab = nullptr;
-    ~Guard() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); if (slab) (void)hipFree(slab); if (s) (void)hipStreamDestroy(s); }
-  } Gd;
   // LDS while the 28 B per camera (and the group maxima) fit one workgroup's share, global memory beyond
   int dev = 0; hipDeviceProp_t prop;
   HIPCHK_S(hipGetDevice(&dev));
@@ -96,84 +92,66 @@ gsfm_status trans_filter_impl(uint32_t n_cams, uint64_t n_edges, const uint32_t*
     (void)hipGetLastError();
     use_lds = false;   // (the same kernel on global-memory state: the same result)
   }
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += up(bytes); return o; };
-  const size_t o_i = take(4 * E), o_j = take(4 * E), o_rel = take(24 * E), o_rot = take(24 * N), o_dir = take(24 * E), o_ptr = take(4 * (N + 1)),
-               o_nbr = take(4 * ND), o_ent = take(4 * ND), o_part = take(8 * 3 * GSFM_TF_PARTS), o_stats = take(48), o_axes = take(24 * A),
-               o_pass = take(4 * A * N), o_cnt = take(8 * A), o_bad = take(8 * E), o_keep = take(E), o_kept = take(8),
-               o_proj = proj_out ? take(8 * E * A) : 0, o_gq = use_lds ? 0 : take(16 * A * N), o_gmax = use_lds ? 0 : take(8 * A * G),
-               o_gu = use_lds ? 0 : take(4 * A * (2 * N + 2 * G)), total = off;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)free_b < (double)total * 1.02 + (64u << 20))
-    return (gsfm_status)fail(GSFM_ERR_HIP, "not enough free device memory for the translation filter (" + std::to_string((long long)(total >> 20)) + " MiB needed, " +
-                             std::to_string((long long)(free_b >> 20)) + " MiB free)");
-  (void)hipGetLastError();
-  HIPCHK_S(hipStreamCreateWithFlags(&Gd.s, hipStreamNonBlocking));
-  for (hipEvent_t& e : Gd.ev) HIPCHK_S(hipEventCreate(&e));
-  if (hipMalloc(&Gd.slab, total) != hipSuccess) { Gd.slab = nullptr; (void)hipGetLastError(); return (gsfm_status)fail(GSFM_ERR_HIP, "allocating the translation filter's buffers failed"); }
-  char* base = (char*)Gd.slab;
-  const hipStream_t s = Gd.s;
-  HIPCHK_S(hipMemcpyAsync(base + o_i, edge_i, 4 * E, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_j, edge_j, 4 * E, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_rel, rel_t, 24 * E, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_rot, rot_aa, 24 * N, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_ptr, row_ptr.data(), 4 * (N + 1), hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_nbr, nbr.data(), 4 * ND, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_ent, ent.data(), 4 * ND, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemsetAsync(base + o_kept, 0, 8, s));
-  const uint32_t* d_i = (const uint32_t*)(base + o_i); const uint32_t* d_j = (const uint32_t*)(base + o_j);
-  double* d_dir = (double*)(base + o_dir); double* d_part = (double*)(base + o_part); double* d_stats = (double*)(base + o_stats);
-  double* d_axes = (double*)(base + o_axes);
+  FlatLayout L;
+  const auto s_i = L.take<uint32_t>(E), s_j = L.take<uint32_t>(E);
+  const auto s_rel = L.take<double>(3 * E), s_rot = L.take<double>(3 * N), s_dir = L.take<double>(3 * E);
+  const auto s_ptr = L.take<uint32_t>(N + 1), s_nbr = L.take<uint32_t>(ND), s_ent = L.take<uint32_t>(ND);
+  const auto s_part = L.take<double>(3 * GSFM_TF_PARTS), s_stats = L.take<double>(6), s_axes = L.take<double>(3 * A);
+  const auto s_pass = L.take<uint32_t>(A * N), s_cnt = L.take<uint32_t>(2 * A); const auto s_bad = L.take<double>(E); const auto s_keep = L.take<uint8_t>(E);
+  const auto s_kept = L.take<unsigned long long>(1); const auto s_proj = L.take<double>(proj_out ? E * A : 0);
+  const auto s_gq = L.take<unsigned long long>(use_lds ? 0 : 2 * A * N); const auto s_gmax = L.take<double>(use_lds ? 0 : A * G);
+  const auto s_gu = L.take<uint32_t>(use_lds ? 0 : A * (2 * N + 2 * G));
+  FlatCall fc;
+  if (int st = fc.commit(L, "the translation filter", 2)) return (gsfm_status)st;
+  const hipStream_t s = fc.s;
+  HIPCHK_S(fc.upload(s_i, edge_i, E)); HIPCHK_S(fc.upload(s_j, edge_j, E));
+  HIPCHK_S(fc.upload(s_rel, rel_t, 3 * E)); HIPCHK_S(fc.upload(s_rot, rot_aa, 3 * N));
+  HIPCHK_S(fc.upload(s_ptr, row_ptr.data(), N + 1)); HIPCHK_S(fc.upload(s_nbr, nbr.data(), ND)); HIPCHK_S(fc.upload(s_ent, ent.data(), ND));
+  HIPCHK_S(fc.zero(s_kept, 1));
+  const uint32_t* d_i = fc.ptr(s_i); const uint32_t* d_j = fc.ptr(s_j);
+  double* d_dir = fc.ptr(s_dir); double* d_part = fc.ptr(s_part); double* d_stats = fc.ptr(s_stats); double* d_axes = fc.ptr(s_axes);
   const dim3 blk(256), gE((unsigned)((E + 255) / 256));
 
   // ---- directions, mean, variance ---------------------------------------------------------------------------------------------------
-  HIPCHK_S(hipEventRecord(Gd.ev[0], s));
-  hipLaunchKernelGGL(k_tf_directions, gE, blk, 0, s, (uint32_t)E, d_i, (const double*)(base + o_rot), (const double*)(base + o_rel), d_dir);
+  HIPCHK_S(fc.begin_span());
+  hipLaunchKernelGGL(k_tf_directions, gE, blk, 0, s, (uint32_t)E, d_i, (const double*)fc.ptr(s_rot), (const double*)fc.ptr(s_rel), d_dir);
   hipLaunchKernelGGL(k_tf_moment, dim3(GSFM_TF_PARTS), blk, 0, s, (const double*)d_dir, (uint32_t)E, (const double*)nullptr, 0, d_part);
   hipLaunchKernelGGL(k_tf_moment_final, dim3(1), blk, 0, s, (const double*)d_part, (double)E, d_stats);
   hipLaunchKernelGGL(k_tf_moment, dim3(GSFM_TF_PARTS), blk, 0, s, (const double*)d_dir, (uint32_t)E, (const double*)d_stats, 1, d_part);
   hipLaunchKernelGGL(k_tf_moment_final, dim3(1), blk, 0, s, (const double*)d_part, (double)E - 1.0, d_stats + 3);
-  HIPCHK_S(hipEventRecord(Gd.ev[1], s));
+  HIPCHK_S(fc.end_span());
   double stats[6] = {0, 0, 0, 0, 0, 0};
   std::vector<double> h_axes(3 * A);
   if (axes) std::memcpy(h_axes.data(), axes, 24 * A);
   if (!axes || stats_out) {
-    HIPCHK_S(hipMemcpyAsync(stats, d_stats, 48, hipMemcpyDeviceToHost, s));
-    HIPCHK_S(hipStreamSynchronize(s));
-    HIPCHK_S(hipGetLastError());
+    HIPCHK_S(fc.download(stats, s_stats, 6));
+    HIPCHK_S(fc.sync());
     if (!axes) tf_generate_axes(stats, n_axes, seed, h_axes.data());
   }
-  HIPCHK_S(hipMemcpyAsync(d_axes, h_axes.data(), 24 * A, hipMemcpyHostToDevice, s));
+  HIPCHK_S(fc.upload(s_axes, h_axes.data(), 3 * A));
 
   // ---- projections (on request), the orderings, the bad weights ------------------------------------------------------------------------
   TfOrderArgs a{};
   a.n_cams = n_cams; a.n_groups = (uint32_t)G;
-  a.row_ptr = (const uint32_t*)(base + o_ptr); a.nbr = (const uint32_t*)(base + o_nbr); a.ent = (const uint32_t*)(base + o_ent);
-  a.dir_e = d_dir; a.axes = d_axes; a.pass_out = (uint32_t*)(base + o_pass); a.counts = (uint32_t*)(base + o_cnt);
-  if (!use_lds) { a.g_q = (unsigned long long*)(base + o_gq); a.g_gmax = (double*)(base + o_gmax); a.g_u32 = (uint32_t*)(base + o_gu); }
-  HIPCHK_S(hipEventRecord(Gd.ev[2], s));
-  if (proj_out) hipLaunchKernelGGL(k_tf_proj, gE, blk, 0, s, (uint32_t)E, (const double*)d_dir, (const double*)d_axes, (int)n_axes, (double*)(base + o_proj));
+  a.row_ptr = fc.ptr(s_ptr); a.nbr = fc.ptr(s_nbr); a.ent = fc.ptr(s_ent);
+  a.dir_e = d_dir; a.axes = d_axes; a.pass_out = fc.ptr(s_pass); a.counts = fc.ptr(s_cnt);
+  if (!use_lds) { a.g_q = fc.ptr(s_gq); a.g_gmax = fc.ptr(s_gmax); a.g_u32 = fc.ptr(s_gu); }
+  HIPCHK_S(fc.begin_span());
+  if (proj_out) hipLaunchKernelGGL(k_tf_proj, gE, blk, 0, s, (uint32_t)E, (const double*)d_dir, (const double*)d_axes, (int)n_axes, fc.ptr(s_proj));
   if (use_lds) hipLaunchKernelGGL(k_tf_order<true>, dim3((unsigned)A), dim3(256), tf_lds_bytes(n_cams), s, a);
   else hipLaunchKernelGGL(k_tf_order<false>, dim3((unsigned)A), dim3(1024), 0, s, a);
   hipLaunchKernelGGL(k_tf_bad, gE, blk, 0, s, (uint32_t)E, n_cams, d_i, d_j, (const double*)d_dir, (const double*)d_axes, (int)n_axes,
-                     (const uint32_t*)(base + o_pass), tolerance * (double)n_axes, (double*)(base + o_bad), (uint8_t*)(base + o_keep),
-                     (unsigned long long*)(base + o_kept));
-  HIPCHK_S(hipEventRecord(Gd.ev[3], s));
+                     (const uint32_t*)fc.ptr(s_pass), tolerance * (double)n_axes, fc.ptr(s_bad), fc.ptr(s_keep), fc.ptr(s_kept));
+  HIPCHK_S(fc.end_span());
   std::vector<uint32_t> counts(2 * A);
   unsigned long long kept = 0;
-  HIPCHK_S(hipMemcpyAsync(bad_weight_out, base + o_bad, 8 * E, hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipMemcpyAsync(keep_out, base + o_keep, E, hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipMemcpyAsync(&kept, base + o_kept, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipMemcpyAsync(counts.data(), base + o_cnt, 8 * A, hipMemcpyDeviceToHost, s));
-  if (proj_out) HIPCHK_S(hipMemcpyAsync(proj_out, base + o_proj, 8 * E * A, hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipStreamSynchronize(s));
-  HIPCHK_S(hipGetLastError());
-  if (kernel_ms) {
-    float t0 = 0, t1 = 0;
-    (void)hipEventElapsedTime(&t0, Gd.ev[0], Gd.ev[1]); (void)hipEventElapsedTime(&t1, Gd.ev[2], Gd.ev[3]);
-    *kernel_ms = (double)t0 + t1;
-  }
+  HIPCHK_S(fc.download(bad_weight_out, s_bad, E));
+  HIPCHK_S(fc.download(keep_out, s_keep, E));
+  HIPCHK_S(fc.download(&kept, s_kept, 1));
+  HIPCHK_S(fc.download(counts.data(), s_cnt, 2 * A));
+  if (proj_out) HIPCHK_S(fc.download(proj_out, s_proj, E * A));
+  HIPCHK_S(fc.sync());
+  if (kernel_ms) *kernel_ms = fc.kernel_ms();
   if (n_kept) *n_kept = kept;
   if (stats_out) std::memcpy(stats_out, stats, 48);
   if (axes_out) std::memcpy(axes_out, h_axes.data(), 24 * A);

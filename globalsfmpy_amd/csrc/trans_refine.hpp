@@ -1,7 +1,7 @@
 // Host side of gsfm_pos_refine_relative_translations (include/gsfm_pos.h): validation, the launch order (edges by descending match
-// count), one device slab and the one launch of trans_refine_kernels.hpp.  Part of libgsfm_rot.so's one translation unit.
+// count), one device slab (flat_call.hpp) and the one launch of trans_refine_kernels.hpp.  Part of libgsfm_rot.so's one translation unit.
 #pragma once
-#include "host_common.hpp"
+#include "flat_call.hpp"
 #include "trans_refine_kernels.hpp"
 #include "../../include/gsfm_pos.h"
 
@@ -31,50 +31,34 @@ gsfm_status trans_refine_impl(uint32_t n_cams, uint64_t n_edges, const uint32_t*
     return match_ptr[x + 1] - match_ptr[x] > match_ptr[y + 1] - match_ptr[y];
   });
 
-  struct Guard {
-    hipStream_t s = nullptr; hipEvent_t ev[2] = {}; void* slab = nullptr;
-    ~Guard() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); if (slab) (void)hipFree(slab); if (s) (void)hipStreamDestroy(s); }
-  } Gd;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += up(bytes); return o; };
-  const size_t o_ord = take(4 * E), o_i = take(4 * E), o_j = take(4 * E), o_ptr = take(8 * (E + 1)), o_m = take(32 * M), o_k = take(48 * E),
-               o_rot = take(24 * N), o_in = take(24 * E), o_plane = take(24 * M), o_out = take(24 * E), o_st = take(4 * E), o_it = take(4 * E),
-               o_cost = take(8 * E), total = off;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)free_b < (double)total * 1.02 + (64u << 20))
-    return (gsfm_status)fail(GSFM_ERR_HIP, "not enough free device memory for the translation refinement (" + std::to_string((long long)(total >> 20)) +
-                             " MiB needed, " + std::to_string((long long)(free_b >> 20)) + " MiB free)");
-  (void)hipGetLastError();
-  HIPCHK_S(hipStreamCreateWithFlags(&Gd.s, hipStreamNonBlocking));
-  for (hipEvent_t& e : Gd.ev) HIPCHK_S(hipEventCreate(&e));
-  if (hipMalloc(&Gd.slab, total) != hipSuccess) { Gd.slab = nullptr; (void)hipGetLastError(); return (gsfm_status)fail(GSFM_ERR_HIP, "allocating the translation refinement's buffers failed"); }
-  char* base = (char*)Gd.slab;
-  const hipStream_t s = Gd.s;
-  HIPCHK_S(hipMemcpyAsync(base + o_ord, order.data(), 4 * E, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_i, edge_i, 4 * E, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_j, edge_j, 4 * E, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_ptr, match_ptr, 8 * (E + 1), hipMemcpyHostToDevice, s));
-  if (M > 0) HIPCHK_S(hipMemcpyAsync(base + o_m, matches, 32 * M, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_k, intrinsics, 48 * E, hipMemcpyHostToDevice, s));
-  if (N > 0) HIPCHK_S(hipMemcpyAsync(base + o_rot, rot_aa, 24 * N, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_in, rel_t_in, 24 * E, hipMemcpyHostToDevice, s));
+  FlatLayout L;
+  const auto s_ord = L.take<uint32_t>(E), s_i = L.take<uint32_t>(E), s_j = L.take<uint32_t>(E);
+  const auto s_ptr = L.take<uint64_t>(E + 1); const auto s_m = L.take<double4>(M);
+  const auto s_k = L.take<double>(6 * E), s_rot = L.take<double>(3 * N), s_in = L.take<double>(3 * E), s_plane = L.take<double>(3 * M),
+             s_out = L.take<double>(3 * E);
+  const auto s_st = L.take<int32_t>(E), s_it = L.take<int32_t>(E); const auto s_cost = L.take<double>(E);
+  FlatCall fc;
+  if (int st = fc.commit(L, "the translation refinement", 1)) return (gsfm_status)st;
+  HIPCHK_S(fc.upload(s_ord, order.data(), E)); HIPCHK_S(fc.upload(s_i, edge_i, E)); HIPCHK_S(fc.upload(s_j, edge_j, E));
+  HIPCHK_S(fc.upload(s_ptr, match_ptr, E + 1));
+  if (M > 0) HIPCHK_S(fc.upload(s_m, matches, M));
+  HIPCHK_S(fc.upload(s_k, intrinsics, 6 * E));
+  if (N > 0) HIPCHK_S(fc.upload(s_rot, rot_aa, 3 * N));
+  HIPCHK_S(fc.upload(s_in, rel_t_in, 3 * E));
   TrArgs a{};
   a.n_edges = E; a.n_matches = M;
-  a.order = (const uint32_t*)(base + o_ord); a.edge_i = (const uint32_t*)(base + o_i); a.edge_j = (const uint32_t*)(base + o_j);
-  a.match_ptr = (const uint64_t*)(base + o_ptr); a.matches = (const double4*)(base + o_m); a.intr = (const double*)(base + o_k);
-  a.rot_aa = (const double*)(base + o_rot); a.rel_t_in = (const double*)(base + o_in); a.plane = (double*)(base + o_plane);
-  a.rel_t_out = (double*)(base + o_out); a.status = (int32_t*)(base + o_st); a.iters = (int32_t*)(base + o_it); a.cost = (double*)(base + o_cost);
-  HIPCHK_S(hipEventRecord(Gd.ev[0], s));
-  hipLaunchKernelGGL(k_tr_refine, dim3((unsigned)E), dim3(64), 0, s, a);
-  HIPCHK_S(hipEventRecord(Gd.ev[1], s));
-  HIPCHK_S(hipMemcpyAsync(rel_t_out, base + o_out, 24 * E, hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipMemcpyAsync(status_out, base + o_st, 4 * E, hipMemcpyDeviceToHost, s));
-  if (iters_out) HIPCHK_S(hipMemcpyAsync(iters_out, base + o_it, 4 * E, hipMemcpyDeviceToHost, s));
-  if (cost_out) HIPCHK_S(hipMemcpyAsync(cost_out, base + o_cost, 8 * E, hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipStreamSynchronize(s));
-  HIPCHK_S(hipGetLastError());
-  if (kernel_ms) { float ms = 0; (void)hipEventElapsedTime(&ms, Gd.ev[0], Gd.ev[1]); *kernel_ms = ms; }
+  a.order = fc.ptr(s_ord); a.edge_i = fc.ptr(s_i); a.edge_j = fc.ptr(s_j); a.match_ptr = fc.ptr(s_ptr); a.matches = fc.ptr(s_m); a.intr = fc.ptr(s_k);
+  a.rot_aa = fc.ptr(s_rot); a.rel_t_in = fc.ptr(s_in); a.plane = fc.ptr(s_plane);
+  a.rel_t_out = fc.ptr(s_out); a.status = fc.ptr(s_st); a.iters = fc.ptr(s_it); a.cost = fc.ptr(s_cost);
+  HIPCHK_S(fc.begin_span());
+  hipLaunchKernelGGL(k_tr_refine, dim3((unsigned)E), dim3(64), 0, fc.s, a);
+  HIPCHK_S(fc.end_span());
+  HIPCHK_S(fc.download(rel_t_out, s_out, 3 * E));
+  HIPCHK_S(fc.download(status_out, s_st, E));
+  if (iters_out) HIPCHK_S(fc.download(iters_out, s_it, E));
+  if (cost_out) HIPCHK_S(fc.download(cost_out, s_cost, E));
+  HIPCHK_S(fc.sync());
+  if (kernel_ms) *kernel_ms = fc.kernel_ms();
   return GSFM_OK;
 }
 

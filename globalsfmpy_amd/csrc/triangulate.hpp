@@ -1,9 +1,10 @@
 // Host side of gsfm_tracks_triangulate (include/gsfm_tracks.h): validation, the lane classes and the launch order inside a class
-// (longest track first), one device slab and the launches of triangulate_kernels.hpp.  Part of libgsfm_rot.so's one translation unit.
+// (longest track first), one device slab (flat_call.hpp) and the launches of triangulate_kernels.hpp.  Part of libgsfm_rot.so's one
+// translation unit.
 // gsfm_tracks_triangulate_refine (track_refine.hpp) runs through the same function with a TriRefineHook: the same checks, slab and launch
 // order, k_tri_refine_tracks in place of k_tri_tracks and four more outputs.
 #pragma once
-#include "host_common.hpp"
+#include "flat_call.hpp"
 #include "triangulate_kernels.hpp"
 #include "track_refine_kernels.hpp"
 #include "../../include/gsfm_tracks.h"
@@ -70,58 +71,45 @@ gsfm_status tri_impl(uint32_t n_cams, const double* rot_aa, const double* cam_po
   const bool long_class = cb[3] > cb[2];
   const double cos_min_angle = std::cos(min_triangulation_angle_degrees * M_PI / 180.0);
 
-  struct Guard {
-    hipStream_t s = nullptr; hipEvent_t ev[2] = {}; void* slab = nullptr;
-    ~Guard() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); if (slab) (void)hipFree(slab); if (s) (void)hipStreamDestroy(s); }
-  } Gd;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += up(bytes); return o; };
-  const size_t o_ord = take(4 * T), o_ptr = take(8 * (T + 1)), o_cam = take(4 * O), o_xy = take(16 * O), o_rot = take(24 * N), o_pos = take(24 * N),
-               o_k = take(24 * N), o_est = take(N), o_rec = take(8 * GSFM_TRI_CAM_DOUBLES * N), o_plane = take(long_class ? 24 * O : 0),
-               o_pt = take(24 * T), o_st = take(4 * T), o_nv = take(4 * T), o_err = take(8 * T), o_it = take(rf ? 4 * T : 0), o_term = take(rf ? 4 * T : 0),
-               o_c0 = take(rf ? 8 * T : 0), o_c1 = take(rf ? 8 * T : 0), total = off;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)free_b < (double)total * 1.02 + (64u << 20))
-    return (gsfm_status)fail(GSFM_ERR_HIP, "not enough free device memory for the track triangulation (" + std::to_string((long long)(total >> 20)) +
-                             " MiB needed, " + std::to_string((long long)(free_b >> 20)) + " MiB free)");
-  (void)hipGetLastError();
-  HIPCHK_S(hipStreamCreateWithFlags(&Gd.s, hipStreamNonBlocking));
-  for (hipEvent_t& e : Gd.ev) HIPCHK_S(hipEventCreate(&e));
-  if (hipMalloc(&Gd.slab, total) != hipSuccess) { Gd.slab = nullptr; (void)hipGetLastError(); return (gsfm_status)fail(GSFM_ERR_HIP, "allocating the track triangulation's buffers failed"); }
-  char* base = (char*)Gd.slab;
-  const hipStream_t s = Gd.s;
-  HIPCHK_S(hipMemcpyAsync(base + o_ord, order.data(), 4 * T, hipMemcpyHostToDevice, s));
-  HIPCHK_S(hipMemcpyAsync(base + o_ptr, track_ptr, 8 * (T + 1), hipMemcpyHostToDevice, s));
+  FlatLayout L;
+  const auto s_ord = L.take<uint32_t>(T); const auto s_ptr = L.take<uint64_t>(T + 1); const auto s_cam = L.take<uint32_t>(O); const auto s_xy = L.take<double2>(O);
+  const auto s_rot = L.take<double>(3 * N), s_pos = L.take<double>(3 * N), s_k = L.take<double>(3 * N); const auto s_est = L.take<uint8_t>(N);
+  const auto s_rec = L.take<double>(GSFM_TRI_CAM_DOUBLES * N), s_plane = L.take<double>(long_class ? 3 * O : 0), s_pt = L.take<double>(3 * T);
+  const auto s_st = L.take<int32_t>(T), s_nv = L.take<int32_t>(T); const auto s_err = L.take<double>(T);
+  const auto s_it = L.take<int32_t>(rf ? T : 0), s_term = L.take<int32_t>(rf ? T : 0); const auto s_c0 = L.take<double>(rf ? T : 0), s_c1 = L.take<double>(rf ? T : 0);
+  FlatCall fc;
+  if (int st = fc.commit(L, "the track triangulation", 1)) return (gsfm_status)st;
+  const hipStream_t s = fc.s;
+  HIPCHK_S(fc.upload(s_ord, order.data(), T));
+  HIPCHK_S(fc.upload(s_ptr, track_ptr, T + 1));
   if (O > 0) {
-    HIPCHK_S(hipMemcpyAsync(base + o_cam, obs_cam, 4 * O, hipMemcpyHostToDevice, s));
-    HIPCHK_S(hipMemcpyAsync(base + o_xy, obs_xy, 16 * O, hipMemcpyHostToDevice, s));
+    HIPCHK_S(fc.upload(s_cam, obs_cam, O));
+    HIPCHK_S(fc.upload(s_xy, obs_xy, O));
   }
   if (N > 0) {
-    HIPCHK_S(hipMemcpyAsync(base + o_rot, rot_aa, 24 * N, hipMemcpyHostToDevice, s));
-    HIPCHK_S(hipMemcpyAsync(base + o_pos, cam_pos, 24 * N, hipMemcpyHostToDevice, s));
-    HIPCHK_S(hipMemcpyAsync(base + o_k, intrinsics, 24 * N, hipMemcpyHostToDevice, s));
-    if (cam_estimated) HIPCHK_S(hipMemcpyAsync(base + o_est, cam_estimated, N, hipMemcpyHostToDevice, s));
+    HIPCHK_S(fc.upload(s_rot, rot_aa, 3 * N));
+    HIPCHK_S(fc.upload(s_pos, cam_pos, 3 * N));
+    HIPCHK_S(fc.upload(s_k, intrinsics, 3 * N));
+    if (cam_estimated) HIPCHK_S(fc.upload(s_est, cam_estimated, N));
   }
   TriArgs a{};
-  a.track_ptr = (const uint64_t*)(base + o_ptr); a.obs_cam = (const uint32_t*)(base + o_cam); a.obs_xy = (const double2*)(base + o_xy);
-  a.cams = (const double*)(base + o_rec); a.plane = (double*)(base + o_plane); a.n_obs = O;
+  a.track_ptr = fc.ptr(s_ptr); a.obs_cam = fc.ptr(s_cam); a.obs_xy = fc.ptr(s_xy);
+  a.cams = fc.ptr(s_rec); a.plane = fc.ptr(s_plane); a.n_obs = O;
   a.cos_min_angle = cos_min_angle; a.max_sq_err = max_reprojection_error_pixels * max_reprojection_error_pixels;
-  a.point = (double*)(base + o_pt); a.status = (int32_t*)(base + o_st); a.n_views = (int32_t*)(base + o_nv); a.mean_sq_err = (double*)(base + o_err);
-  HIPCHK_S(hipEventRecord(Gd.ev[0], s));
+  a.point = fc.ptr(s_pt); a.status = fc.ptr(s_st); a.n_views = fc.ptr(s_nv); a.mean_sq_err = fc.ptr(s_err);
+  HIPCHK_S(fc.begin_span());
   if (N > 0)
-    hipLaunchKernelGGL(k_tri_cameras, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, n_cams, (const double*)(base + o_rot), (const double*)(base + o_pos),
-                       (const double*)(base + o_k), cam_estimated ? (const uint8_t*)(base + o_est) : (const uint8_t*)nullptr, (double*)(base + o_rec));
+    hipLaunchKernelGGL(k_tri_cameras, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, n_cams, (const double*)fc.ptr(s_rot), (const double*)fc.ptr(s_pos),
+                       (const double*)fc.ptr(s_k), cam_estimated ? (const uint8_t*)fc.ptr(s_est) : (const uint8_t*)nullptr, fc.ptr(s_rec));
   TriRefineArgs ra{};
   if (rf) {
     ra = rf->proto;
-    ra.iterations = (int32_t*)(base + o_it); ra.termination = (int32_t*)(base + o_term);
-    ra.initial_cost = (double*)(base + o_c0); ra.final_cost = (double*)(base + o_c1);
+    ra.iterations = fc.ptr(s_it); ra.termination = fc.ptr(s_term); ra.initial_cost = fc.ptr(s_c0); ra.final_cost = fc.ptr(s_c1);
   }
   auto launch = [&](int c, auto kernel, auto refine_kernel, unsigned groups_per_block, unsigned block) {
     a.n_slots = cb[c + 1] - cb[c];
     if (a.n_slots == 0) return;
-    a.order = (const uint32_t*)(base + o_ord) + cb[c];
+    a.order = fc.ptr(s_ord) + cb[c];
     const dim3 grid((unsigned)((a.n_slots + groups_per_block - 1) / groups_per_block));
     if (rf) { ra.tri = a; hipLaunchKernelGGL(refine_kernel, grid, dim3(block), 0, s, ra); }
     else hipLaunchKernelGGL(kernel, grid, dim3(block), 0, s, a);
@@ -129,21 +117,20 @@ gsfm_status tri_impl(uint32_t n_cams, const double* rot_aa, const double* cam_po
   launch(2, k_tri_tracks<64>, k_tri_refine_tracks<64>, 1, 64);   // the long tracks start first
   launch(1, k_tri_tracks<16>, k_tri_refine_tracks<16>, GSFM_TRI_BLOCK / 16, GSFM_TRI_BLOCK);
   launch(0, k_tri_tracks<4>, k_tri_refine_tracks<4>, GSFM_TRI_BLOCK / 4, GSFM_TRI_BLOCK);
-  HIPCHK_S(hipEventRecord(Gd.ev[1], s));
-  HIPCHK_S(hipMemcpyAsync(point_out, base + o_pt, 24 * T, hipMemcpyDeviceToHost, s));
-  HIPCHK_S(hipMemcpyAsync(status_out, base + o_st, 4 * T, hipMemcpyDeviceToHost, s));
-  if (n_views_out) HIPCHK_S(hipMemcpyAsync(n_views_out, base + o_nv, 4 * T, hipMemcpyDeviceToHost, s));
-  if (mean_sq_err_out) HIPCHK_S(hipMemcpyAsync(mean_sq_err_out, base + o_err, 8 * T, hipMemcpyDeviceToHost, s));
+  HIPCHK_S(fc.end_span());
+  HIPCHK_S(fc.download(point_out, s_pt, 3 * T));
+  HIPCHK_S(fc.download(status_out, s_st, T));
+  if (n_views_out) HIPCHK_S(fc.download(n_views_out, s_nv, T));
+  if (mean_sq_err_out) HIPCHK_S(fc.download(mean_sq_err_out, s_err, T));
   if (rf) {
-    if (rf->iterations_out) HIPCHK_S(hipMemcpyAsync(rf->iterations_out, base + o_it, 4 * T, hipMemcpyDeviceToHost, s));
-    if (rf->termination_out) HIPCHK_S(hipMemcpyAsync(rf->termination_out, base + o_term, 4 * T, hipMemcpyDeviceToHost, s));
-    if (rf->initial_cost_out) HIPCHK_S(hipMemcpyAsync(rf->initial_cost_out, base + o_c0, 8 * T, hipMemcpyDeviceToHost, s));
-    if (rf->final_cost_out) HIPCHK_S(hipMemcpyAsync(rf->final_cost_out, base + o_c1, 8 * T, hipMemcpyDeviceToHost, s));
+    if (rf->iterations_out) HIPCHK_S(fc.download(rf->iterations_out, s_it, T));
+    if (rf->termination_out) HIPCHK_S(fc.download(rf->termination_out, s_term, T));
+    if (rf->initial_cost_out) HIPCHK_S(fc.download(rf->initial_cost_out, s_c0, T));
+    if (rf->final_cost_out) HIPCHK_S(fc.download(rf->final_cost_out, s_c1, T));
   }
-  HIPCHK_S(hipStreamSynchronize(s));
-  HIPCHK_S(hipGetLastError());
+  HIPCHK_S(fc.sync());
   if (counts_out) for (size_t t = 0; t < T; ++t) if (status_out[t] >= 0 && status_out[t] < n_status) ++counts_out[status_out[t]];
-  if (kernel_ms) { float ms = 0; (void)hipEventElapsedTime(&ms, Gd.ev[0], Gd.ev[1]); *kernel_ms = ms; }
+  if (kernel_ms) *kernel_ms = fc.kernel_ms();
   return GSFM_OK;
 }
 

@@ -21,6 +21,12 @@ class SolverError(RuntimeError):
     pass
 
 
+def _raise_if_failed(lib, name, st):
+    """The one error path of the calls that take no problem object: `name` is the C entry point, `st` its status."""
+    if st != 0:
+        raise SolverError("%s failed with status %d: %s" % (name, st, lib.gsfm_last_error().decode("utf-8", "replace")))
+
+
 class ProblemBase(object):
     """Shared call sequence for anything exporting the gsfm_rot_* argument lists.
     (The CPU oracle under oracle/ mirrors them with an orc_ prefix for the parity tests.)"""
@@ -216,9 +222,7 @@ class RotationProblem(ProblemBase):
         h = C.c_void_p()
         st = lib.gsfm_rot_problem_create(int(n_cams), int(n_edges), _u32p(ei), _u32p(ej), _dp(rel), int(error_type),
                                          _dp(c6), _dp(iw), C.byref(shard) if shard is not None else None, C.byref(h))
-        if st != 0:
-            raise SolverError("gsfm_rot_problem_create failed with status %d: %s"
-                              % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+        _raise_if_failed(lib, "gsfm_rot_problem_create", st)
         ProblemBase.__init__(self, lib, h, n_cams, n_edges, error_type, lib.gsfm_rot_residual_dim(int(error_type)))
         self._shard = shard
         if stream is not None:
@@ -324,8 +328,7 @@ def edge_sq_norms(n_cams, edge_i, edge_j, rel_aa, rot_aa, cov6=None, max_sq_norm
     st = lib.gsfm_rot_edge_sq_norms(int(n_cams), int(n_edges), _u32p(ei), _u32p(ej), _dp(rel), _dp(c6), _dp(rot),
                                     float(max_sq_norm if max_sq_norm is not None else -1.0), _dp(s),
                                     keep.ctypes.data_as(C.POINTER(C.c_uint8)) if keep is not None else None, C.byref(kept), C.byref(ms))
-    if st != 0:
-        raise SolverError("gsfm_rot_edge_sq_norms failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+    _raise_if_failed(lib, "gsfm_rot_edge_sq_norms", st)
     return {"s": s, "keep": None if keep is None else keep.astype(bool), "n_kept": int(kept.value), "kernel_ms": ms.value}
 
 
@@ -349,8 +352,7 @@ def orientations_from_maximum_spanning_tree(n_cams, edge_i, edge_j, rel_aa, weig
     st = lib.gsfm_rot_init_spanning_tree(n, int(n_edges), _u32p(ei), _u32p(ej), _dp(rel),
                                          None if wt is None else wt.ctypes.data_as(C.POINTER(C.c_int32)), _dp(rot),
                                          parent.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(root), C.byref(n_tree), C.byref(depth), C.byref(ms))
-    if st != 0:
-        raise SolverError("gsfm_rot_init_spanning_tree failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+    _raise_if_failed(lib, "gsfm_rot_init_spanning_tree", st)
     return {"rot_aa": rot, "parent_edge": parent, "root": int(root.value), "n_tree_cams": int(n_tree.value), "depth": int(depth.value),
             "kernel_ms": ms.value}
 
@@ -385,8 +387,7 @@ def filter_relative_translations(n_cams, edge_i, edge_j, rel_t, rot_aa, num_iter
     st = lib.gsfm_pos_filter_relative_translations(n, E, _u32p(ei), _u32p(ej), _dp(rel), _dp(rot), K, _dp(ax), int(seed), float(tolerance),
                                                    _dp(bad), keep.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(kept), _dp(stats), _dp(axes_out),
                                                    _dp(proj), _u32p(passes), _u32p(picks), C.byref(ms))
-    if st != 0:
-        raise SolverError("gsfm_pos_filter_relative_translations failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+    _raise_if_failed(lib, "gsfm_pos_filter_relative_translations", st)
     return keep.astype(bool), {"bad_weight": bad, "n_kept": int(kept.value), "mean": stats[:3].copy(), "variance": stats[3:].copy(), "axes": axes_out,
                                "projections": proj, "num_passes": passes, "num_picks": picks, "kernel_ms": ms.value}
 
@@ -419,8 +420,7 @@ def refine_relative_translations(n_cams, edge_i, edge_j, match_ptr, matches, int
     st = lib.gsfm_pos_refine_relative_translations(n, E, _u32p(ei), _u32p(ej), mp.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(m), _dp(K), _dp(rot),
                                                    _dp(rel), _dp(out), status.ctypes.data_as(i32p), iters.ctypes.data_as(i32p), _dp(cost),
                                                    C.byref(ms))
-    if st != 0:
-        raise SolverError("gsfm_pos_refine_relative_translations failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+    _raise_if_failed(lib, "gsfm_pos_refine_relative_translations", st)
     return out, {"status": status, "iterations": iters, "cost": cost, "kernel_ms": ms.value}
 
 
@@ -480,8 +480,7 @@ def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, 
                                                 float(max_reprojection_error_pixels), C.byref(opt), prog, n_nodes, _dp(points),
                                                 status.ctypes.data_as(i32p), n_views.ctypes.data_as(i32p), _dp(err), iters.ctypes.data_as(i32p),
                                                 _dp(cost0), _dp(cost1), term.ctypes.data_as(i32p), counts.ctypes.data_as(u64p), C.byref(ms))
-        if st != 0:
-            raise SolverError("gsfm_tracks_triangulate_refine failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+        _raise_if_failed(lib, "gsfm_tracks_triangulate_refine", st)
         return {"points": points, "status": status, "n_views": n_views, "mean_sq_err": err, "counts": counts, "kernel_ms": ms.value,
                 "iterations": iters, "initial_cost": cost0, "final_cost": cost1, "termination": term}
     err, counts = np.zeros(T), np.zeros(6, dtype=np.uint64)
@@ -489,8 +488,7 @@ def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, 
                                      tp.ctypes.data_as(u64p), _u32p(oc), _dp(xy), float(min_triangulation_angle_degrees),
                                      float(max_reprojection_error_pixels), _dp(points), status.ctypes.data_as(i32p), n_views.ctypes.data_as(i32p),
                                      _dp(err), counts.ctypes.data_as(u64p), C.byref(ms))
-    if st != 0:
-        raise SolverError("gsfm_tracks_triangulate failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+    _raise_if_failed(lib, "gsfm_tracks_triangulate", st)
     return {"points": points, "status": status, "n_views": n_views, "mean_sq_err": err, "counts": counts, "kernel_ms": ms.value}
 
 
@@ -502,8 +500,7 @@ def track_launch_order(track_ptr):
     order, begin = np.zeros(T, dtype=np.uint32), np.zeros(4, dtype=np.uint64)
     u64p = C.POINTER(C.c_uint64)
     st = lib.gsfm_tracks_launch_order(T, tp.ctypes.data_as(u64p), _u32p(order), begin.ctypes.data_as(u64p))
-    if st != 0:
-        raise SolverError("gsfm_tracks_launch_order failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+    _raise_if_failed(lib, "gsfm_tracks_launch_order", st)
     return order, begin
 
 
@@ -524,8 +521,7 @@ class PositionProblem(ProblemBase):
             raise ValueError("edge_i, edge_j and rel_t must describe the same edges")
         h = C.c_void_p()
         st = lib.gsfm_pos_problem_create(int(n_cams), ei.size, _u32p(ei), _u32p(ej), _dp(rel), _dp(rot), C.byref(h))
-        if st != 0:
-            raise SolverError("gsfm_pos_problem_create failed with status %d: %s" % (st, lib.gsfm_last_error().decode("utf-8", "replace")))
+        _raise_if_failed(lib, "gsfm_pos_problem_create", st)
         ProblemBase.__init__(self, lib, h, n_cams, ei.size, -1, 3)
 
     def _last_error(self):
