@@ -158,6 +158,15 @@ struct DeviceGuard {
   ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
+// wait for a stream; 0, or the status of what failed on it (the message is set)
+int sync_stream(hipStream_t s, const char* what) {
+  hipError_t e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return fail(GSFM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(GSFM_ERR_HIP, std::string(what) + " (launch): " + hipGetErrorString(e));
+  return 0;
+}
+
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- MAGSAC constants / tables (include/gamma_values.cpp; regenerated, see oracle/ref_loss.hpp) ----
@@ -209,13 +218,15 @@ template <typename T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
-  hipError_t alloc(size_t count, bool zero = false) {
+  // zero: cleared on the default stream and waited for with the whole device; with zero_on, cleared in that stream's order and not waited for
+  hipError_t alloc(size_t count, bool zero = false, hipStream_t zero_on = nullptr) {
     release();
     n = count;
     if (count == 0) return hipSuccess;
     hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
     if (e != hipSuccess) { p = nullptr; return e; }
-    if (zero) { e = hipMemset(p, 0, count * sizeof(T)); if (e == hipSuccess) e = hipDeviceSynchronize(); }
+    if (zero && zero_on) e = hipMemsetAsync(p, 0, count * sizeof(T), zero_on);
+    else if (zero) { e = hipMemset(p, 0, count * sizeof(T)); if (e == hipSuccess) e = hipDeviceSynchronize(); }
     return e;
   }
   template <typename A> hipError_t upload(const std::vector<T, A>& h) {

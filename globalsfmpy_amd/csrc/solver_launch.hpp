@@ -87,10 +87,7 @@ template <int F, int W, int L> struct ColLinLauncher {   // K2c (column-sorted l
 };
 
 int sync_check(gsfm_rot_problem* P, const char* what) {
-  hipError_t e = hipStreamSynchronize(P->stream);
-  if (e != hipSuccess) return fail(GSFM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(GSFM_ERR_HIP, std::string(what) + " (launch): " + hipGetErrorString(e));
+  if (int st = sync_stream(P->stream, what)) return st;
   P->timer.resolve();
   return 0;
 }

@@ -2,6 +2,7 @@
 // (the reference's ceres::Solve calls, src/GSfM_nonlinear_rotation_estimator.cpp:77,182,305,446) and the state transfers around it.
 #pragma once
 #include "host_common.hpp"
+#include "trust_region.hpp"
 
 namespace gsfm {
 // Per-camera 3-vectors between the caller's numbering and the internal one (the locality relabelling adopted at create), on the device:
@@ -172,8 +173,9 @@ enum { LM_GO_ON = -1, LM_NEXT = -2 };
 struct LmSolve {
   gsfm_rot_problem* const P; const gsfm_rot_options& o_in; gsfm_rot_options o; gsfm_rot_summary* const sum;   // (o: o_in as start() adjusts it)
   double t0 = 0.0, h[SC_N];
-  double radius = 0.0, decrease_factor = 2.0, x_cost = 0, x_norm = 0, gmax = 0;
-  int num_invalid = 0, iteration = 0;
+  TrustRegion tr;   // radius, decrease factor, consecutive invalid steps (trust_region.hpp)
+  double x_cost = 0, x_norm = 0, gmax = 0;
+  int iteration = 0;
   bool prep_valid = true, trial_lin = false, last_successful = false, pcg_struggles = false, pcg_dearer_than_cholesky = false;
   // LM control on the device for exact steps (the lm_device_control option; 0: the host loop, for A/B and for the bit-identity test) runs on
   // unsharded problems with a native loss on the row-major layout: its accept path, linearisation included, is enqueued before the host has
@@ -244,10 +246,10 @@ struct LmSolve {
     int cg = 0, cg_spent = 0; double cg_rel = 0, tau = 0;
   };
   void record(const Row& r) {
-    const double row[GSFM_ROT_TRACE_COLS] = {(double)iteration, x_cost, r.cc, gmax, r.sn, r.rd, radius, (double)r.cg};
+    const double row[GSFM_ROT_TRACE_COLS] = {(double)iteration, x_cost, r.cc, gmax, r.sn, r.rd, tr.radius, (double)r.cg};
     P->trace.insert(P->trace.end(), row, row + GSFM_ROT_TRACE_COLS);
     if (o.verbose) fprintf(stderr, "[gsfm] it %3d cost %.12e dcost %.3e |g| %.3e |dx| %.3e rho %.3e radius %.3e cg %d\n",
-                           iteration, x_cost, r.cc, gmax, r.sn, r.rd, radius, r.cg);
+                           iteration, x_cost, r.cc, gmax, r.sn, r.rd, tr.radius, r.cg);
   }
   void take_gmax() {   // (call behind a synchronisation of the stream)
     gmax = *gmax_pin; gmax_deferred = false;
@@ -257,7 +259,7 @@ struct LmSolve {
     if (gmax_deferred || P->timer.used) { (void)hipStreamSynchronize(P->stream); P->timer.resolve(); if (gmax_deferred) take_gmax(); }   // (the mailbox reads leave the phase timers' events unresolved)
     if (spec_enqueued || exact_pipeline_used) { (void)hipStreamSynchronize(P->stream); P->timer.resolve(); spec_enqueued = false; }   // (whatever was enqueued ahead skips itself; the phase timers need the sync)
     sum->termination = term; sum->num_iterations = iteration; sum->final_cost = x_cost; sum->final_gradient_max_norm = gmax;
-    sum->final_radius = radius; sum->t_total_ms = now_ms() - t0;
+    sum->final_radius = tr.radius; sum->t_total_ms = now_ms() - t0;
     sum->num_graph_launches = P->graph_launches;
     sum->num_collectives = P->n_collectives; sum->num_pcg_collectives = P->n_pcg_collectives; sum->num_pcg_launched = P->n_pcg_launched;
     sum->t_linearize_ms = P->timer.acc[T_LIN]; sum->t_sweep_ms = P->timer.acc[T_SWEEP]; sum->t_cg_ms = P->timer.acc[T_CG];
@@ -297,7 +299,7 @@ struct LmSolve {
     P->lap = P->lap_capable;
     P->comps.fresh_solve = true;
     P->component_rest = o.component_rest != 0;
-    radius = o.initial_trust_region_radius;
+    tr.radius = o.initial_trust_region_radius;
     defer_gmax = P->pin && !o.verbose;
     gmax_pin = P->pin ? (volatile double*)((char*)P->pin + 256) : nullptr;
     hipLaunchKernelGGL(k_cam_norm, dim3(P->nb_cam), dim3(GSFM_BLOCK), 0, P->stream, P->x.p, P->active.p, P->n_cams, P->param_dim, P->part_cam.p);
@@ -314,7 +316,7 @@ struct LmSolve {
       if (int st = launch_lin(P, P->q.p)) return st;
     }
     sum->num_residual_sweeps++; sum->num_linearizations++;
-    launch_prep(P, o, radius, true);
+    launch_prep(P, o, tr.radius, true);
     if (int st = read_scalars(P, h)) return st;
     x_cost = h[SC_COST]; gmax = h[SC_GMAX]; x_norm = std::sqrt(h[SC_XNORM2]);
     sum->initial_cost = x_cost;
@@ -333,13 +335,13 @@ struct LmSolve {
   int begin_iteration(Step& s) {
     if (iteration >= o.max_num_iterations) return finish(GSFM_TERM_NO_CONVERGENCE);
     if (last_successful && !gmax_deferred && gmax <= o.gradient_tolerance) return finish(GSFM_TERM_GRADIENT_TOLERANCE);
-    if (radius <= o.min_trust_region_radius) {
+    if (tr.radius <= o.min_trust_region_radius) {
       if (int r = check_deferred_gmax(true, false); r != LM_GO_ON) return r;
       return finish(GSFM_TERM_FAILURE);
     }
     ++iteration;
     last_successful = false;
-    if (!prep_valid) launch_prep(P, o, radius, false);
+    if (!prep_valid) launch_prep(P, o, tr.radius, false);
     prep_valid = false;
     // Forcing schedule: the step is solved loosely -- to a relative (energy-norm) error tau chosen so that tau * |step|_rms <= eps_rad, with the
     // step size predicted from the previous accepted step (first step: tau_max, corrected below) -- unless it is the last one the iteration
@@ -387,7 +389,7 @@ struct LmSolve {
                        (const double*)P->part_cam.p, P->nb_cam, (const double*)P->part_cost.p, P->nb_cost,
                        P->n_cams, P->param_dim, P->x.p, (const double*)P->x_trial.p, P->q.p, (const double2*)P->q_trial.p);
     if (int st = launch_lin(P, P->q.p, ctl + CT_ACCEPT)) return -st;
-    launch_prep(P, o, radius, false, ctl + CT_RADIUS, false);
+    launch_prep(P, o, tr.radius, false, ctl + CT_RADIUS, false);
     hipLaunchKernelGGL(k_lm_after, dim3(1), dim3(GSFM_BLOCK), 0, P->stream, lo, P->scal.p, (int)SC_GMAX, ctl, P->rec_dev, (int)REC, P->scal.p + SC_REC, (const double*)P->part_cam.p, P->nb_cam);
     return 0;
   }
@@ -397,7 +399,7 @@ struct LmSolve {
                          hipHostGetDevicePointer((void**)&P->rec_dev, P->rec_host, 0) != hipSuccess)) { (void)hipGetLastError(); return fail(GSFM_ERR_HIP, "mapped record of the LM control"); }
     exact_pipeline_used = true;
     if (!spec_enqueued) {
-      hipLaunchKernelGGL(k_lm_set, dim3(1), dim3(1), 0, P->stream, P->scal.p + SC_CTL, radius, decrease_factor, x_cost, x_norm, gmax, (double)num_invalid,
+      hipLaunchKernelGGL(k_lm_set, dim3(1), dim3(1), 0, P->stream, P->scal.p + SC_CTL, tr.radius, tr.decrease_factor, x_cost, x_norm, gmax, (double)tr.num_invalid,
                          P->scal.p + SC_REC, (double)iteration);   // (SC_REC: the device-resident iteration number, k_lm_set / k_lm_after)
       const int eq = enqueue_exact(iteration);
       if (eq < 0) return -eq;
@@ -435,10 +437,10 @@ struct LmSolve {
     }
     sum->num_dense_solves++;
     sum->num_residual_sweeps++;
-    num_invalid = (int)c[CT_NINVALID];
+    tr.num_invalid = (int)c[CT_NINVALID];
     if (c[CT_VALID] == 0.0) {                          // HandleInvalidStep
       if (c[CT_TERM] == 4.0) return finish(GSFM_TERM_FAILURE);
-      radius = c[CT_RADIUS]; decrease_factor = c[CT_DF];
+      tr.radius = c[CT_RADIUS]; tr.decrease_factor = c[CT_DF];
       sum->num_unsuccessful_steps++;
       record(Row{});
       return LM_NEXT;
@@ -448,7 +450,7 @@ struct LmSolve {
     if (sum->iters_to_1e6 < 0 && std::fabs(row.cc) <= 1e-6 * x_cost) sum->iters_to_1e6 = iteration;
     if (c[CT_TERM] == 2.0) { record(row); return finish(GSFM_TERM_PARAMETER_TOLERANCE); }
     if (c[CT_TERM] == 0.0) { record(row); return finish(GSFM_TERM_FUNCTION_TOLERANCE); }
-    radius = c[CT_RADIUS]; decrease_factor = c[CT_DF];
+    tr.radius = c[CT_RADIUS]; tr.decrease_factor = c[CT_DF];
     if (c[CT_ACCEPT] != 0.0) {
       x_norm = c[CT_XNORM]; x_cost = c[CT_XCOST]; gmax = c[CT_GMAX];
       sum->num_residual_sweeps++; sum->num_linearizations++;
@@ -475,7 +477,7 @@ struct LmSolve {
   int component_step(Step& s) {
     if (P->packed) (void)hipMemsetAsync(P->scal.p + SC_COMPBAD, 0, sizeof(double), P->stream);
     if (s.dense_used || P->n_components <= 1 || (P->sharded && !P->packed)) return LM_GO_ON;
-    if (int st = run_component_step(P, o, o_in.cg_relative_tolerance, pcg_struggles, radius, &s.comp_used, &s.cg, &s.cg_rel)) return st;
+    if (int st = run_component_step(P, o, o_in.cg_relative_tolerance, pcg_struggles, tr.radius, &s.comp_used, &s.cg, &s.cg_rel)) return st;
     if (!s.comp_used) return LM_GO_ON;
     s.loose = false;
     if (int r = check_deferred_gmax(P->comps.all_dense, true); r != LM_GO_ON) return r;
@@ -613,12 +615,12 @@ struct LmSolve {
     const double model_cost_change = -0.5 * eta_g + 0.5 * eta_r + 0.5 * eta_L;
     const bool valid = std::isfinite(model_cost_change) && model_cost_change > 0.0;
     if (!valid) {  // HandleInvalidStep
-      if (++num_invalid >= 5) return finish(GSFM_TERM_FAILURE);
-      reject();
+      if (tr.invalid_step()) return finish(GSFM_TERM_FAILURE);
+      sum->num_unsuccessful_steps++; prev_accepted = false;
       record(Row{0, 0, 0, s.cg});
       return LM_NEXT;
     }
-    num_invalid = 0;
+    tr.num_invalid = 0;
     double cand_cost = h[SC_TRIAL];
     if (!std::isfinite(cand_cost)) { cand_cost = std::numeric_limits<double>::max(); sum->nonfinite = 1; }
     const double step_norm = std::sqrt(h[SC_STEP + 3]);
@@ -652,7 +654,7 @@ struct LmSolve {
     const double w = P->loss_staircase ? std::fmin(1.0, 100.0 / std::sqrt(n_e)) : 1e-3, lo = 1.0 / (1.0 + w), hi = 1.0 + w;
     return r.cc > 0.0 && ((r.sn > lo * pt && r.sn <= hi * pt) || (acc > lo * ft && acc <= hi * ft) || (r.rd > lo * o.min_relative_decrease && r.rd <= hi * o.min_relative_decrease));
   }
-  void reject() { radius /= decrease_factor; decrease_factor *= 2.0; sum->num_unsuccessful_steps++; prev_accepted = false; }   // HandleUnsuccessfulStep
+  void reject() { tr.rejected(); sum->num_unsuccessful_steps++; prev_accepted = false; }   // HandleUnsuccessfulStep
   int accept(const Step& s, const Row& row, double cand_cost) {  // HandleSuccessfulStep
     std::swap(P->x.p, P->x_trial.p);
     // (a copy, not a pointer swap: the captured PCG / Cholesky graphs hold the address of the quaternions they rotate with)
@@ -663,10 +665,8 @@ struct LmSolve {
     else if (int st = launch_lin(P, P->q.p)) return st;
     sum->num_residual_sweeps++; sum->num_linearizations++;
     prev_accepted = true;
-    radius = radius / std::fmax(1.0 / 3.0, 1.0 - std::pow(2.0 * row.rd - 1.0, 3));   // (std::pow as Ceres' LevenbergMarquardtStrategy::StepAccepted and the oracle; k_lm_decide: the same value through lm_cube)
-    radius = std::fmin(o.max_trust_region_radius, radius);
-    decrease_factor = 2.0;
-    launch_prep(P, o, radius, false);
+    tr.accepted(row.rd, o.max_trust_region_radius);   // (std::pow as Ceres' LevenbergMarquardtStrategy::StepAccepted and the oracle; k_lm_decide: the same value through lm_cube)
+    launch_prep(P, o, tr.radius, false);
     prep_valid = true;
     if (defer_gmax) {
       HIPCHK(hipMemcpyAsync((void*)gmax_pin, P->scal.p + SC_GMAX, sizeof(double), hipMemcpyDeviceToHost, P->stream));

@@ -126,7 +126,6 @@ class ProblemBase(object):
         r = np.empty((self.n_edges, self.residual_dim)) if want_residuals else None
         cost = C.c_double(0)
         st = self._fn("residuals")(self._h, _dp(rot), _dp(s), _dp(rho), _dp(r), C.byref(cost))
-        self._reraise_callback_error()
         self._check(st, "residuals")
         return {"s": s, "rho": rho, "residuals": r, "cost": cost.value}
 
@@ -163,7 +162,6 @@ class ProblemBase(object):
         o = self._options(options)
         s = _abi.Summary()
         st = self._fn("solve")(self._h, _dp(rot), C.byref(o), C.byref(s))
-        self._reraise_callback_error()
         self._check(st, "solve")
         return rot, s.as_dict()
 
@@ -172,7 +170,6 @@ class ProblemBase(object):
         o = self._options(options)
         s = _abi.Summary()
         st = self._fn("solve_sigma_consensus")(self._h, _dp(rot), int(iters_num), float(sigma_max), C.byref(o), C.byref(s))
-        self._reraise_callback_error()
         self._check(st, "solve_sigma_consensus")
         return rot, s.as_dict()
 
@@ -242,7 +239,6 @@ class RotationProblem(ProblemBase):
         o = self._options(options)
         s = _abi.Summary()
         st = self._lib.gsfm_rot_solve_resident(self._h, C.c_void_p(ptr), C.byref(o), C.byref(s))
-        self._reraise_callback_error()
         self._check(st, "solve_resident")
         return s.as_dict()
 
@@ -539,7 +535,6 @@ class PositionProblem(ProblemBase):
         o = self._options(options)
         s = _abi.PosSummary()
         st = self._lib.gsfm_pos_solve(self._h, _dp(pos), int(fixed_cam), C.byref(o), C.byref(s))
-        self._reraise_callback_error()
         self._check(st, "solve")
         return pos, s.as_dict()
 
@@ -549,7 +544,6 @@ class PositionProblem(ProblemBase):
         r = np.empty((self.n_edges, 3))
         rho = np.empty(self.n_edges)
         st = self._lib.gsfm_pos_residuals(self._h, _dp(pos), _dp(r), _dp(rho))
-        self._reraise_callback_error()
         self._check(st, "residuals")
         return r, rho
 
@@ -568,7 +562,6 @@ class PositionProblem(ProblemBase):
         info = np.zeros(3, dtype=np.int32)
         st = self._lib.gsfm_pos_step_check(self._h, _dp(pos), int(fixed_cam), float(radius), C.byref(o), None if K is None else _dp(K),
                                            _dp(b), _dp(y), _dp(delta), _dp(scal), info.ctypes.data_as(C.POINTER(C.c_int32)))
-        self._reraise_callback_error()
         self._check(st, "step_check")
         return {"K": K if info[1] >= 0 else None, "b": b, "y": y, "delta": delta,
                 "model_cost_change": scal[0], "dg": scal[1], "dld": scal[2], "cg_rel": scal[3], "path": int(info[0]),

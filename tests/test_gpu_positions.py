@@ -95,6 +95,22 @@ def test_deterministic(dense_max_cams):
     assert s1["final_cost"] == s2["final_cost"] and s1["num_iterations"] == s2["num_iterations"]
 
 
+def test_one_problem_object_across_solver_paths():
+    """PCG, then the dense step (its tiles allocated and cleared at first use, in the stream's order), then a host-callback loss (its
+    buffers allocated at first use) on ONE problem object: each solve equals, bit for bit, the same solve on a fresh problem -- nothing a
+    solve finds in the problem's memory depends on what ran there before."""
+    g = synth.make_position_graph(50, 400, seed=3, outlier_frac=0.2)
+    p = _problem(g, lf.HuberLoss(0.1))
+    for loss, kw in ((None, {"dense_max_cams": 0}), (None, {"dense_max_cams": 1000}), (PyHuber(0.1), {})):
+        if loss is not None:
+            p.set_loss(loss)
+        x1, s1 = p.solve(None, fixed_cam=0, **kw)
+        x2, s2 = _problem(g, loss if loss is not None else lf.HuberLoss(0.1)).solve(None, fixed_cam=0, **kw)
+        assert np.array_equal(x1, x2), kw
+        assert s1["num_iterations"] == s2["num_iterations"] and s1["termination"] == s2["termination"], (s1, s2)
+        assert (s1["num_dense_solves"] > 0) == (kw.get("dense_max_cams") != 0), s1
+
+
 @pytest.mark.parametrize("dense_max_cams", [1000, 0])
 def test_large_radius_scale_gauge(dense_max_cams):
     """The radius grows to >= 1e12, where the damped step system's condition number along the scale direction v = c - c_0 is of the
