@@ -70,7 +70,8 @@ void gsfm_rot_problem_destroy(gsfm_rot_problem* P) {
 gsfm_status gsfm_rot_set_stream(gsfm_rot_problem* P, void* s) {
   if (!P) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL problem");
   DeviceGuard g(P->device);
-  if (P->own_stream && P->stream) { (void)hipStreamSynchronize(P->stream); (void)hipStreamDestroy(P->stream); }
+  if (P->stream) (void)hipStreamSynchronize(P->stream);   // (whatever the problem enqueued on the stream it leaves, a loss upload say, has arrived)
+  if (P->own_stream && P->stream) (void)hipStreamDestroy(P->stream);
   P->reset_pcg_graphs(); P->pcg_graph.unusable = false; P->pcg2_graph.unusable = false;
   if (P->dense_graph) { (void)hipGraphExecDestroy(P->dense_graph); P->dense_graph = nullptr; }
   P->comps.drop_graph(); P->comps.drop_side();
@@ -102,10 +103,7 @@ gsfm_status gsfm_rot_set_edge_weights(gsfm_rot_problem* P, const double* w) {
   if (!P || !w) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
   if (P->functor != F_AA || P->wmode == W_MATRIX) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "edge weights only apply to the scalar-weight angle-axis types");
   DeviceGuard g(P->device);
-  if (P->wmode == W_NONE) {  // ANGLE_AXIS: promote to a scalar-weight problem
-    if (P->cost.ws.alloc(P->cost.n) != hipSuccess || P->dir.ws.alloc(P->dir.n) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc weight planes");
-    P->wmode = W_SCALAR;
-  }
+  if (int st = promote_to_scalar_weights(P)) return (gsfm_status)st;
   if (!P->w_orig.p && P->w_orig.alloc(P->n_edges_in) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc weights");
   if (hipMemcpyAsync(P->w_orig.p, w, 8 * P->n_edges_in, hipMemcpyHostToDevice, P->stream) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "upload weights");
   if (P->cost.n) hipLaunchKernelGGL(k_gather_weights, dim3(grid_for(P->cost.n)), dim3(GSFM_BLOCK), 0, P->stream, P->w_orig.p, P->cost.eid.p, P->cost.n, P->cost.ws.p);
@@ -133,7 +131,7 @@ static gsfm_status solve_impl(gsfm_rot_problem* P, double* rot, const gsfm_rot_o
   const gsfm_rot_options o = opt ? *opt : default_options();
   gsfm_rot_summary local; if (!summary) summary = &local;
   const double t0 = now_ms();
-  if (int st = resident ? upload_state_resident(P, rot) : upload_state(P, rot)) return (gsfm_status)st;
+  if (int st = upload_state(P, rot, resident)) return (gsfm_status)st;
   int st = lm_solve(P, o, summary);
   if (st == GSFM_INTERNAL_RESTART) {
     // The forcing schedule gave up on this trajectory after inexact steps had been applied (solver_lm.hpp, the contraction gate): the solve is
@@ -142,12 +140,10 @@ static gsfm_status solve_impl(gsfm_rot_problem* P, double* rot, const gsfm_rot_o
     gsfm_rot_options o2 = o;
     o2.pcg_forcing = 0;
     if (o.verbose) fprintf(stderr, "[gsfm] forcing schedule abandoned after %d LM iterations (steps stopped contracting): restarting with exact steps\n", spent.num_iterations);
-    if (int st2 = resident ? upload_state_resident(P, rot) : upload_state(P, rot)) return (gsfm_status)st2;
+    if (int st2 = upload_state(P, rot, resident)) return (gsfm_status)st2;
     st = lm_solve(P, o2, summary);
     summary->num_forcing_restarts = 1;
-    summary->num_cg_iterations += spent.num_cg_iterations; summary->num_residual_sweeps += spent.num_residual_sweeps; summary->num_linearizations += spent.num_linearizations;
-    summary->num_graph_launches += spent.num_graph_launches; summary->num_collectives += spent.num_collectives; summary->num_pcg_collectives += spent.num_pcg_collectives;
-    summary->num_pcg_launched += spent.num_pcg_launched; summary->t_linearize_ms += spent.t_linearize_ms; summary->t_sweep_ms += spent.t_sweep_ms; summary->t_cg_ms += spent.t_cg_ms;
+    add_work(summary, spent);
   }
   if (st) return (gsfm_status)st;
   if (int st2 = resident ? download_state_resident(P, rot) : download_state(P, rot)) return (gsfm_status)st2;
@@ -165,24 +161,13 @@ gsfm_status gsfm_rot_solve_sigma_consensus(gsfm_rot_problem* P, double* rot, int
   gsfm_rot_summary local, total; if (!summary) summary = &local;
   std::memset(&total, 0, sizeof(total));
   const double t0 = now_ms();
-  const MagsacConst c = magsac_const(3);
-  const double squared_sigma_max_2 = sigma_max * sigma_max * 2.0;
-  const double dof_minus_one_per_two = (c.nu - 1.0) / 2.0;
-  const double one_over_sigma = c.C * std::pow(2.0, dof_minus_one_per_two) / sigma_max;
-  const double weight_zero = one_over_sigma * (std::tgamma(dof_minus_one_per_two) - c.gk);
   // The scalar-weight planes live on the device for the whole loop, each in its kernel's own order.  There is no weight pass: the first
   // cost sweep and the first linearisation of every inner solve start from exactly the rotations the reference computes the weights at
   // (:378-416), so they compute, store and use them (setup_kernels.hpp, SigmaDev).  The first comparison is against zero weights, like the
   // reference's zero-initialised last_weights (:352-353).
-  if (P->wmode == W_NONE) {
-    if (P->cost.ws.alloc(P->cost.n) != hipSuccess || P->dir.ws.alloc(P->dir.n) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc weight planes");
-    P->wmode = W_SCALAR;
-  }
+  if (int st = promote_to_scalar_weights(P)) return (gsfm_status)st;
   if (P->cost.n) HIPCHK_S(hipMemsetAsync(P->cost.ws.p, 0, 8 * P->cost.n, P->stream));
-  if (!P->sigma_table.p && P->sigma_table.upload(magsac_table(3)) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc sigma consensus buffers");
-  if (!P->sigma_sum.p && P->sigma_sum.alloc(2, true) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc sigma consensus buffers");
-  P->sigma.table = P->sigma_table.p; P->sigma.table_len = c.n; P->sigma.on = 0; P->sigma.ssm2 = squared_sigma_max_2; P->sigma.inv_ssm2 = 1.0 / squared_sigma_max_2;
-  P->sigma.one_over_sigma = one_over_sigma; P->sigma.gk = c.gk; P->sigma.weight_zero = weight_zero;
+  if (int st = ensure_sigma(P, sigma_max, &P->sigma)) return (gsfm_status)st;
   double global_edges = (double)P->n_edges_in;
   if (P->sharded) {
     // every edge is counted in mean |w - w_old| by exactly one rank: its cost owner
@@ -208,14 +193,11 @@ gsfm_status gsfm_rot_solve_sigma_consensus(gsfm_rot_problem* P, double* rot, int
     avg /= global_edges;
     if (it == 0) total = *summary;
     else {
+      add_work(&total, *summary);
       total.num_iterations += summary->num_iterations; total.num_successful_steps += summary->num_successful_steps;
-      total.num_unsuccessful_steps += summary->num_unsuccessful_steps; total.num_residual_sweeps += summary->num_residual_sweeps;
-      total.num_linearizations += summary->num_linearizations; total.num_cg_iterations += summary->num_cg_iterations;
+      total.num_unsuccessful_steps += summary->num_unsuccessful_steps; total.num_dense_solves += summary->num_dense_solves;
       total.final_cost = summary->final_cost; total.termination = summary->termination;
       total.final_gradient_max_norm = summary->final_gradient_max_norm; total.final_radius = summary->final_radius;
-      total.num_dense_solves += summary->num_dense_solves; total.num_graph_launches += summary->num_graph_launches;
-      total.num_collectives += summary->num_collectives; total.num_pcg_collectives += summary->num_pcg_collectives; total.num_pcg_launched += summary->num_pcg_launched;
-      total.t_linearize_ms += summary->t_linearize_ms; total.t_sweep_ms += summary->t_sweep_ms; total.t_cg_ms += summary->t_cg_ms;
       total.num_forcing_refinements += summary->num_forcing_refinements; total.num_inexact_steps += summary->num_inexact_steps;
       total.num_pcg_capped_steps += summary->num_pcg_capped_steps; total.num_forcing_restarts += summary->num_forcing_restarts;
       total.worst_accepted_cg_residual = std::fmax(total.worst_accepted_cg_residual, summary->worst_accepted_cg_residual);
@@ -248,8 +230,8 @@ gsfm_status gsfm_rot_residuals(gsfm_rot_problem* P, const double* rot, double* s
   std::vector<double> stage;
   if (s_out || rho_out) {   // device planes: (s, rho) and (rho', rho'') per edge
     stage.resize(4 * Ec);
-    if (Ec && (hipMemcpy(stage.data(), dsr.p, 16 * Ec, hipMemcpyDeviceToHost) != hipSuccess || (rho_out && hipMemcpy(stage.data() + 2 * Ec, dr12.p, 16 * Ec, hipMemcpyDeviceToHost) != hipSuccess)))
-      return (gsfm_status)fail(GSFM_ERR_HIP, "copy s / rho");
+    if (Ec) if (int st = read_back(P, stage.data(), dsr.p, 16 * Ec, "copy s / rho")) return (gsfm_status)st;
+    if (Ec && rho_out) if (int st = read_back(P, stage.data() + 2 * Ec, dr12.p, 16 * Ec, "copy rho', rho''")) return (gsfm_status)st;
     if (s_out) { std::memset(s_out, 0, 8 * E); for (size_t u = 0; u < Ec; ++u) s_out[ord[u]] = stage[2 * u]; }
     if (rho_out) {
       std::memset(rho_out, 0, 24 * E);
@@ -258,7 +240,7 @@ gsfm_status gsfm_rot_residuals(gsfm_rot_problem* P, const double* rot, double* s
   }
   if (r_out) {
     stage.resize(R * Ec);
-    if (Ec && hipMemcpy(stage.data(), dr.p, 8 * R * Ec, hipMemcpyDeviceToHost) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "copy r");
+    if (Ec) if (int st = read_back(P, stage.data(), dr.p, 8 * R * Ec, "copy r")) return (gsfm_status)st;
     std::memset(r_out, 0, 8 * R * E);
     for (size_t u = 0; u < Ec; ++u) for (size_t k = 0; k < R; ++k) r_out[R * (size_t)ord[u] + k] = stage[k * Ec + u];
   }
@@ -288,11 +270,11 @@ gsfm_status gsfm_rot_linearize(gsfm_rot_problem* P, const double* rot, double* g
   std::vector<double> stage;
   if (!P->perm.empty()) stage.resize(9 * N);
   if (gradient) {
-    if (hipMemcpy(P->perm.empty() ? gradient : stage.data(), dg.p, 24 * N, hipMemcpyDeviceToHost) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "copy gradient");
+    if (int st = read_back(P, P->perm.empty() ? gradient : stage.data(), dg.p, 24 * N, "copy gradient")) return (gsfm_status)st;
     if (!P->perm.empty()) to_external(P, stage.data(), gradient, 3);
   }
   if (diag_blocks) {
-    if (hipMemcpy(P->perm.empty() ? diag_blocks : stage.data(), dblk.p, 72 * N, hipMemcpyDeviceToHost) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "copy blocks");
+    if (int st = read_back(P, P->perm.empty() ? diag_blocks : stage.data(), dblk.p, 72 * N, "copy blocks")) return (gsfm_status)st;
     if (!P->perm.empty()) to_external(P, stage.data(), diag_blocks, 9);
   }
   return GSFM_OK;
@@ -447,18 +429,8 @@ gsfm_status gsfm_rot_time_sweep(gsfm_rot_problem* P, const double* rot, int32_t 
   DeviceGuard g(P->device);
   if (int st = upload_state(P, rot)) return (gsfm_status)st;
   const CostArgs a = cost_args(P, P->q.p);
-  for (int k = 0; k < 3; ++k) if (dispatch<CostArgs, CostLauncher>(P, a, P->nb_cost)) return (gsfm_status)fail(GSFM_ERR_UNSUPPORTED, "dispatch");
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "event create");
-  (void)hipEventRecord(e0, P->stream);
-  for (int k = 0; k < reps; ++k) dispatch<CostArgs, CostLauncher>(P, a, P->nb_cost);
-  (void)hipEventRecord(e1, P->stream);
-  int st = sync_check(P, "time_sweep");
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  *mean_ms = ms / reps;
-  return (gsfm_status)st;
+  auto sweep = [&] { return dispatch<CostArgs, CostLauncher>(P, a, P->nb_cost) ? fail(GSFM_ERR_UNSUPPORTED, "dispatch") : 0; };
+  return (gsfm_status)timed(P, reps, 3, 1, "time_sweep", sweep, mean_ms);
 }
 
 gsfm_status gsfm_rot_time_sweep_variants(gsfm_rot_problem* P, const double* rot, int32_t reps, double* out_ms8) {
@@ -468,55 +440,38 @@ gsfm_status gsfm_rot_time_sweep_variants(gsfm_rot_problem* P, const double* rot,
   const size_t Ec = P->cost.n;
   if (int st = upload_state(P, rot)) return (gsfm_status)st;
   DevBuf<double> ds; DevBuf<double2> dsr, dr12;
-  if (ds.alloc(Ec, true) != hipSuccess || dsr.alloc(Ec, true) != hipSuccess || dr12.alloc(Ec, true) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc outputs");
+  if (ds.alloc_zeroed(Ec, P->stream) != hipSuccess || dsr.alloc_zeroed(Ec, P->stream) != hipSuccess || dr12.alloc_zeroed(Ec, P->stream) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc outputs");
   const CostArgs base = cost_args(P, P->q.p);
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "event create");
-  auto timed = [&](auto&& launch, double* out) -> int {   // two rounds, the faster one counts (a round now and then is hit by something else on the box)
-    double best = 0.0;
-    for (int round = 0; round < 2; ++round) {
-      for (int k = -2; k < reps; ++k) { if (k == 0) (void)hipEventRecord(e0, P->stream); launch(); }
-      (void)hipEventRecord(e1, P->stream);
-      if (int st = sync_check(P, "time_sweep_variants")) return st;
-      float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
-      if (round == 0 || ms / reps < best) best = ms / reps;
-    }
-    *out = best; return 0;
-  };
+  // two warm-ups, the faster of two rounds; a launch that cannot be dispatched times nothing, as before
+  auto time_it = [&](auto&& launch, double* out) { return timed(P, reps, 2, 2, "time_sweep_variants", [&] { launch(); return 0; }, out); };
   int st = 0;
   for (int k = 0; k < 8; ++k) out_ms8[k] = 0.0;
-  { CostArgs a = base; st = timed([&] { dispatch<CostArgs, CostLauncher>(P, a, P->nb_cost); }, &out_ms8[0]); }                                   // trial cost: rho value only
-  if (!st) { CostArgs a = base; a.srho_out = dsr.p; a.rho12_out = dr12.p; st = timed([&] { dispatch<CostArgs, CostLauncher>(P, a, P->nb_cost); }, &out_ms8[1]); }  // s + rho triple
-  if (!st) { CostArgs a = base; a.s_out = ds.p; a.s_only = 1; st = timed([&] { dispatch<CostArgs, CostLauncher>(P, a, P->nb_cost); }, &out_ms8[2]); }   // s only (callback pass 1)
-  if (!st) { CostArgs a = base; a.rho1_out = ds.p; st = timed([&] { dispatch<CostArgs, CostLauncher>(P, a, P->nb_cost); }, &out_ms8[3]); }             // the reweight sweep of SURVEY 8(d): rho' out
+  { CostArgs a = base; st = time_it([&] { dispatch<CostArgs, CostLauncher>(P, a, P->nb_cost); }, &out_ms8[0]); }                                   // trial cost: rho value only
+  if (!st) { CostArgs a = base; a.srho_out = dsr.p; a.rho12_out = dr12.p; st = time_it([&] { dispatch<CostArgs, CostLauncher>(P, a, P->nb_cost); }, &out_ms8[1]); }  // s + rho triple
+  if (!st) { CostArgs a = base; a.s_out = ds.p; a.s_only = 1; st = time_it([&] { dispatch<CostArgs, CostLauncher>(P, a, P->nb_cost); }, &out_ms8[2]); }   // s only (callback pass 1)
+  if (!st) { CostArgs a = base; a.rho1_out = ds.p; st = time_it([&] { dispatch<CostArgs, CostLauncher>(P, a, P->nb_cost); }, &out_ms8[3]); }             // the reweight sweep of SURVEY 8(d): rho' out
   if (!st && P->functor == F_AA && P->wmode == W_SCALAR && P->cost.ws.p && P->dir.ws.p) {
     // sigma consensus: the first cost sweep / linearisation of an inner solve with the weight computation fused in (estimator.cpp:400-416),
     // against the same kernels without it.  The sweeps overwrite the problem's own weight planes: save and restore them.
-    const MagsacConst c = magsac_const(3);
-    if (!P->sigma_table.p && P->sigma_table.upload(magsac_table(3)) != hipSuccess) st = fail(GSFM_ERR_HIP, "alloc");
-    if (!st && !P->sigma_sum.p && P->sigma_sum.alloc(2, true) != hipSuccess) st = fail(GSFM_ERR_HIP, "alloc");
+    SigmaDev sg{};
+    st = ensure_sigma(P, 0.02, &sg); sg.on = 1;
     DevBuf<double> keep_c, keep_d;
     if (!st && (keep_c.alloc(P->cost.n) != hipSuccess || keep_d.alloc(P->dir.n) != hipSuccess)) st = fail(GSFM_ERR_HIP, "alloc");
     if (!st) {
-      const double sigma_max = 0.02, one_over_sigma = c.C * std::pow(2.0, (c.nu - 1.0) / 2.0) / sigma_max;
-      SigmaDev sg{};
-      sg.table = P->sigma_table.p; sg.table_len = c.n; sg.on = 1; sg.ssm2 = 2.0 * sigma_max * sigma_max; sg.inv_ssm2 = 1.0 / sg.ssm2; sg.one_over_sigma = one_over_sigma;
-      sg.gk = c.gk; sg.weight_zero = one_over_sigma * (std::tgamma((c.nu - 1.0) / 2.0) - c.gk);
       (void)hipMemcpyAsync(keep_c.p, P->cost.ws.p, 8 * P->cost.n, hipMemcpyDeviceToDevice, P->stream);
       (void)hipMemcpyAsync(keep_d.p, P->dir.ws.p, 8 * P->dir.n, hipMemcpyDeviceToDevice, P->stream);
       const SigmaDev keep_sigma = P->sigma;
       P->sigma = sg;
-      st = timed([&] { P->sigma_pending_cost = true; (void)launch_cost(P, P->q.p, SC_COST); }, &out_ms8[4]);    // K1 with the weights fused in (+ the two scalar reductions)
-      if (!st) st = timed([&] { (void)launch_cost(P, P->q.p, SC_COST); }, &out_ms8[5]);                          // the same sweep without
-      if (!st) st = timed([&] { P->sigma_pending_lin = true; (void)launch_lin(P, P->q.p); }, &out_ms8[6]);       // K2 with the weights fused in
-      if (!st) st = timed([&] { (void)launch_lin(P, P->q.p); }, &out_ms8[7]);                                    // K2 without
+      st = time_it([&] { P->sigma_pending_cost = true; (void)launch_cost(P, P->q.p, SC_COST); }, &out_ms8[4]);    // K1 with the weights fused in (+ the two scalar reductions)
+      if (!st) st = time_it([&] { (void)launch_cost(P, P->q.p, SC_COST); }, &out_ms8[5]);                          // the same sweep without
+      if (!st) st = time_it([&] { P->sigma_pending_lin = true; (void)launch_lin(P, P->q.p); }, &out_ms8[6]);       // K2 with the weights fused in
+      if (!st) st = time_it([&] { (void)launch_lin(P, P->q.p); }, &out_ms8[7]);                                    // K2 without
       P->sigma = keep_sigma; P->sigma_pending_cost = P->sigma_pending_lin = false;
       (void)hipMemcpyAsync(P->cost.ws.p, keep_c.p, 8 * P->cost.n, hipMemcpyDeviceToDevice, P->stream);
       (void)hipMemcpyAsync(P->dir.ws.p, keep_d.p, 8 * P->dir.n, hipMemcpyDeviceToDevice, P->stream);
       if (int s2 = sync_check(P, "time_sweep_variants restore")) st = st ? st : s2;
     }
   }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return (gsfm_status)st;
 }
 
@@ -541,7 +496,7 @@ gsfm_status gsfm_rot_trial_lin_check(gsfm_rot_problem* P, const double* rot, con
   DevBuf<double> sgD;
   DevBuf<unsigned int> flag;
   if (s0.alloc(P->h0.n) != hipSuccess || s1.alloc(P->h1.n) != hipSuccess || s2.alloc(P->h2.n) != hipSuccess || sq.alloc(P->q.n) != hipSuccess ||
-      sgD.alloc(P->gD.n) != hipSuccess || flag.alloc(2, true) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc snapshot");
+      sgD.alloc(P->gD.n) != hipSuccess || flag.alloc_zeroed(2, P->stream) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "alloc snapshot");
   HIPCHK_S(hipMemcpyAsync(s0.p, P->h0.p, 16 * P->h0.n, hipMemcpyDeviceToDevice, P->stream));
   HIPCHK_S(hipMemcpyAsync(s1.p, P->h1.p, 16 * P->h1.n, hipMemcpyDeviceToDevice, P->stream));
   HIPCHK_S(hipMemcpyAsync(s2.p, P->h2.p, 16 * P->h2.n, hipMemcpyDeviceToDevice, P->stream));
@@ -567,7 +522,7 @@ gsfm_status gsfm_rot_trial_lin_check(gsfm_rot_problem* P, const double* rot, con
   double h[SC_N];
   if (int st = read_scalars(P, h)) return (gsfm_status)st;
   unsigned int f[2] = {1, 1};
-  HIPCHK_S(hipMemcpy(f, flag.p, sizeof(f), hipMemcpyDeviceToHost));
+  if (int st = read_back(P, f, flag.p, sizeof(f), "trial_lin_check flags")) return (gsfm_status)st;
   cost_out[0] = h[SC_COST]; cost_out[1] = h[SC_TRIAL];
   same_out[0] = f[0] == 0; same_out[1] = f[1] == 0;
   if (int st = launch_lin(P, P->q.p)) return (gsfm_status)st;
@@ -588,26 +543,11 @@ gsfm_status gsfm_rot_time_kernels(gsfm_rot_problem* P, const double* rot, int32_
   if (int st = launch_lin(P, P->q.p)) return (gsfm_status)st;
   launch_prep(P, o, o.initial_trust_region_radius, true);
   if (int st = sync_check(P, "time_kernels setup")) return (gsfm_status)st;
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return (gsfm_status)fail(GSFM_ERR_HIP, "event create");
-  for (int which = 0; which < 4; ++which) {
-    out_ms4[which] = 0.0;
-    if (which == 3) continue;   // (reserved)
-    for (int round = 0; round < 2; ++round) {   // two rounds of `reps` launches each, the faster round's mean counts
-      for (int k = -2; k < reps; ++k) {  // two warm-up launches
-        if (k == 0) (void)hipEventRecord(e0, P->stream);
-        if (which == 0) { if (int st = launch_cost(P, P->q.p, SC_COST)) return (gsfm_status)st; }
-        else if (which == 1) { if (int st = launch_lin(P, P->q.p)) return (gsfm_status)st; }
-        else if (which == 2) { if (int st = launch_matvec(P, P->Mblk.p, P->b.p, P->Ap.p, nullptr)) return (gsfm_status)st; }
-      }
-      (void)hipEventRecord(e1, P->stream);
-      if (int st = sync_check(P, "time_kernels")) return (gsfm_status)st;
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      if (round == 0 || ms / reps < out_ms4[which]) out_ms4[which] = ms / reps;
-    }
+  for (int which = 0; which < 4; ++which) out_ms4[which] = 0.0;   // ([3]: reserved)
+  for (int which = 0; which < 3; ++which) {   // two warm-ups, the faster of two rounds
+    auto launch = [&] { return which == 0 ? launch_cost(P, P->q.p, SC_COST) : which == 1 ? launch_lin(P, P->q.p) : launch_matvec(P, P->Mblk.p, P->b.p, P->Ap.p, nullptr); };
+    if (int st = timed(P, reps, 2, 2, "time_kernels", launch, &out_ms4[which])) return (gsfm_status)st;
   }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return GSFM_OK;
 }
 

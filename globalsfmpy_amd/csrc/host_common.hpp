@@ -214,25 +214,33 @@ struct NoInitAlloc {
 };
 template <typename T> using hvec = std::vector<T, NoInitAlloc<T>>;
 
+// One device array.  The TRANSFER RULE of everything that owns one: every fill and copy of problem memory is enqueued on a stream the caller
+// names -- the problem's; nothing uses the default stream or synchronises the device (tests/test_stream_rule.py reads the sources for it).
+// The LIFETIME RULE that goes with it: a host array handed to an asynchronous copy, pageable memory included, stays alive and unmodified
+// until that stream is next synchronised.  A function that uploads from a host array of its own ends with ONE sync_stream before the array
+// dies; arrays that persist with the problem (h_loss, perm, h_cam, the MAGSAC tables' statics) need none.  And nothing is allocated or cleared
+// on a stream that is being captured: a solve's first-use buffers are built in front of the captures (solver_dense / _pcg / _components.hpp).
+// (release: hipFree still synchronises inside the runtime; the create-time temporaries -- d_rel, d_cov, d_inl, d_labels, agree_buf -- pay that.)
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
-  // zero: cleared on the default stream and waited for with the whole device; with zero_on, cleared in that stream's order and not waited for
-  hipError_t alloc(size_t count, bool zero = false, hipStream_t zero_on = nullptr) {
+  hipError_t alloc(size_t count) {
     release();
     n = count;
     if (count == 0) return hipSuccess;
-    hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-    if (e != hipSuccess) { p = nullptr; return e; }
-    if (zero && zero_on) e = hipMemsetAsync(p, 0, count * sizeof(T), zero_on);
-    else if (zero) { e = hipMemset(p, 0, count * sizeof(T)); if (e == hipSuccess) e = hipDeviceSynchronize(); }
+    const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+    if (e != hipSuccess) p = nullptr;
     return e;
   }
-  template <typename A> hipError_t upload(const std::vector<T, A>& h) {
-    hipError_t e = alloc(h.size());
-    if (e != hipSuccess || h.empty()) return e;
-    return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+  // ... cleared in the stream's order, not waited for
+  hipError_t alloc_zeroed(size_t count, hipStream_t s) {
+    const hipError_t e = alloc(count);
+    return e != hipSuccess || count == 0 ? e : hipMemsetAsync(p, 0, count * sizeof(T), s);
+  }
+  template <typename A> hipError_t upload(const std::vector<T, A>& h, hipStream_t s) {
+    const hipError_t e = alloc(h.size());
+    return e != hipSuccess || h.empty() ? e : hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
   }
   void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
   ~DevBuf() { release(); }

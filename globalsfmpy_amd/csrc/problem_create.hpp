@@ -29,7 +29,7 @@ int upload_planes(gsfm_rot_problem* P, EdgePlanes& pl, const EidVec& eid, const 
   pl.n = eid.size();
   // (qr1: the third stored component, one double per position, on the W_MATRIX problems -- edge_math.hpp, qrel_three; the full quaternion's (z, w) pairs otherwise)
   const bool three = P->q3;
-  if (pl.eid.upload(eid) != hipSuccess || pl.qr0.alloc(pl.n) != hipSuccess || pl.qr1.alloc(three ? (pl.n + 1) / 2 : pl.n) != hipSuccess)
+  if (pl.eid.upload(eid, P->stream) != hipSuccess || pl.qr0.alloc(pl.n) != hipSuccess || pl.qr1.alloc(three ? (pl.n + 1) / 2 : pl.n) != hipSuccess)
     return fail(GSFM_ERR_HIP, "uploading edge planes failed (out of memory?)");
   if (pl.n) hipLaunchKernelGGL(k_build_qrel, dim3(grid_for(pl.n)), dim3(GSFM_BLOCK), 0, P->stream, d_rel_aa, pl.eid.p, pl.n, pl.qr0.p, pl.qr1.p, three ? 1 : 0);
   if (P->wmode == W_MATRIX) {
@@ -71,9 +71,9 @@ struct CreateCtx {
     agreed = true;
     if (!P->sharded) return 0;
     double h[3] = {my_flag, my_vote, (double)P->cost.n};
-    if (agree_buf.alloc(3) != hipSuccess || hipMemcpy(agree_buf.p, h, 24, hipMemcpyHostToDevice) != hipSuccess) return -1;
-    if (all_reduce(P, agree_buf.p, 3) != 0) return -1;
-    if (hipStreamSynchronize(P->stream) != hipSuccess || hipMemcpy(h, agree_buf.p, 24, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (agree_buf.alloc(3) != hipSuccess || hipMemcpyAsync(agree_buf.p, h, 24, hipMemcpyHostToDevice, P->stream) != hipSuccess) return -1;
+    const bool reduced = all_reduce(P, agree_buf.p, 3) == 0;
+    if (read_back(P, h, agree_buf.p, 24, "the create-time agreement") != 0 || !reduced) return -1;   // (waited for either way: h is in flight)
     coarse_votes_against = h[1];
     P->cost_n_global = h[2];
     return (int)(h[0] + 0.5);
@@ -169,8 +169,9 @@ void choose_coarse_space(gsfm_rot_problem* P, const HostStructure& H) {
   P->coarse_chunk = (n_cams + want - 1) / want;
   P->coarse_want = (n_cams + P->coarse_chunk - 1) / P->coarse_chunk;   // no empty aggregate
   const size_t nc = 3 * (size_t)P->coarse_want;
-  if (P->coarseA.alloc(nc * nc) != hipSuccess || P->coarseAinv.alloc(nc * nc) != hipSuccess || P->coarse_rc.alloc(nc, true) != hipSuccess ||
-      P->coarse_xc.alloc(nc + 1, true) != hipSuccess || P->coarse_scale.alloc(2, true) != hipSuccess || P->coarse_part.alloc(6 * (size_t)grid_for(n_cams), true) != hipSuccess) {
+  const hipStream_t s = P->stream;
+  if (P->coarseA.alloc(nc * nc) != hipSuccess || P->coarseAinv.alloc(nc * nc) != hipSuccess || P->coarse_rc.alloc_zeroed(nc, s) != hipSuccess ||
+      P->coarse_xc.alloc_zeroed(nc + 1, s) != hipSuccess || P->coarse_scale.alloc_zeroed(2, s) != hipSuccess || P->coarse_part.alloc_zeroed(6 * (size_t)grid_for(n_cams), s) != hipSuccess) {
     P->coarseA.release(); P->coarse_want = 0; (void)hipGetLastError();   // (a sharded rank then votes against in the agreement: all ranks stay on block-Jacobi)
   }
 }
@@ -201,18 +202,20 @@ bool three_component_planes(int wmode, uint64_t n_edges) {
 }
 
 // Device half of the column-sorted layout: the layout arrays go up, col / deid are REPLACED by their position-ordered forms.  Out of memory
-// leaves the problem on the row-major form, which needs none of this.
+// leaves the problem on the row-major form, which needs none of this.  Ends with the stream waited for: L dies with the caller's scope.
 void upload_colsort(gsfm_rot_problem* P, ColsortHost& L, hvec<uint32_t>& col, hvec<uint32_t>& deid) {
   auto& C = P->cs;
+  const hipStream_t s = P->stream;
   C.nch = L.nch; C.n_wg = (uint32_t)L.wg.size(); C.n_pos = L.n_pos; C.cbits = L.cbits; C.cmax = L.cmax;
   // The 2-byte record pays where an escape (a step of 15 cameras or more, a row with 7 or more entries in one sub-chunk: each its own 32-byte
   // sector) is rare: below one position in a hundred -- the benchmark graph has 1e-4 --; an allocation that fails leaves the 4-byte record in use.
   if (L.k16_mode != 0 && (L.k16_mode > 0 || (double)L.k16_escapes <= 0.01 * (double)L.n_pos)) {
-    if (C.k16.upload(L.k16) == hipSuccess && C.kbase.upload(L.kbase) == hipSuccess && C.kdel.upload(L.kdel) == hipSuccess) C.k16_active = true;
+    if (C.k16.upload(L.k16, s) == hipSuccess && C.kbase.upload(L.kbase, s) == hipSuccess && C.kdel.upload(L.kdel, s) == hipSuccess) C.k16_active = true;
     else { (void)hipGetLastError(); C.k16.release(); C.kbase.release(); C.kdel.release(); }
   }
-  if (C.wg.upload(L.wg) != hipSuccess || C.meta.upload(L.meta) != hipSuccess || (!C.k16_active && C.kcol.upload(L.kcol) != hipSuccess) || C.kcnt.upload(L.kcnt) != hipSuccess ||
-      C.part.alloc((size_t)9 * C.n_wg * GSFM_COL_RB) != hipSuccess) {
+  const bool up = C.wg.upload(L.wg, s) == hipSuccess && C.meta.upload(L.meta, s) == hipSuccess && (C.k16_active || C.kcol.upload(L.kcol, s) == hipSuccess) &&
+                  C.kcnt.upload(L.kcnt, s) == hipSuccess && C.part.alloc((size_t)9 * C.n_wg * GSFM_COL_RB) == hipSuccess;
+  if (sync_stream(s, "uploading the column-sorted layout") != 0 || !up) {
     (void)hipGetLastError();
     C = gsfm_rot_problem::ColSort();
     return;
@@ -248,15 +251,16 @@ void choose_colsort(gsfm_rot_problem* P, HostStructure& H, int n_threads) {
 int upload_structure(gsfm_rot_problem* P, const HostStructure& H, const double* rel_aa, size_t nd_planes) {
   {
     DevBuf<double> d_rel;   // the measurements go up once; both sets of planes are gathered from them on the device
-    if (d_rel.alloc(3 * H.n_edges) != hipSuccess || (H.n_edges > 0 && hipMemcpy(d_rel.p, rel_aa, 24 * H.n_edges, hipMemcpyHostToDevice) != hipSuccess))
+    if (d_rel.alloc(3 * H.n_edges) != hipSuccess || (H.n_edges > 0 && hipMemcpyAsync(d_rel.p, rel_aa, 24 * H.n_edges, hipMemcpyHostToDevice, P->stream) != hipSuccess))
       return fail(GSFM_ERR_HIP, "uploading the relative rotations failed");
     if (int st = upload_planes(P, P->cost, H.cost_eid, d_rel.p)) return st;
     if (int st = upload_planes(P, P->dir, H.deid, d_rel.p)) return st;
-    if (hipStreamSynchronize(P->stream) != hipSuccess) return fail(GSFM_ERR_HIP, "building the measurement planes failed");
+    if (int st = sync_stream(P->stream, "building the measurement planes")) return st;   // (this phase's one wait, here because d_rel is freed here)
   }
-  if (P->cost_tiles.upload(H.tiles) != hipSuccess) return fail(GSFM_ERR_HIP, "uploading cost tiles failed");
+  // (H and the caller's arrays outlive every phase: their copies are waited for at the next phase's sync, the last ones at the end of the creation)
+  if (P->cost_tiles.upload(H.tiles, P->stream) != hipSuccess) return fail(GSFM_ERR_HIP, "uploading cost tiles failed");
   P->nb_cost = (int)H.tiles.size();
-  if (P->cost_idx.upload(H.cidx) != hipSuccess || P->row_ptr.upload(H.rp) != hipSuccess || P->col.upload(H.col) != hipSuccess)
+  if (P->cost_idx.upload(H.cidx, P->stream) != hipSuccess || P->row_ptr.upload(H.rp, P->stream) != hipSuccess || P->col.upload(H.col, P->stream) != hipSuccess)
     return fail(GSFM_ERR_HIP, "uploading graph structure failed");
   // planes h3, h4 (the last three of the nine values of a general block) are allocated on first use: the Laplacian form needs six
   if (P->h0.alloc(nd_planes) != hipSuccess || P->h1.alloc(nd_planes) != hipSuccess || P->h2.alloc(nd_planes) != hipSuccess)
@@ -269,14 +273,13 @@ int whiten_planes(gsfm_rot_problem* P, uint64_t n_edges, const double* cov6, con
   if (P->wmode == W_NONE) return 0;
   const ErrorTypeInfo et = classify_error_type(P->error_type);
   DevBuf<double> d_cov, d_inl;
-  if (cov6 && et.need_cov && (d_cov.alloc(6 * n_edges) != hipSuccess || (n_edges && hipMemcpy(d_cov.p, cov6, 48 * n_edges, hipMemcpyHostToDevice) != hipSuccess)))
+  if (cov6 && et.need_cov && (d_cov.alloc(6 * n_edges) != hipSuccess || (n_edges && hipMemcpyAsync(d_cov.p, cov6, 48 * n_edges, hipMemcpyHostToDevice, P->stream) != hipSuccess)))
     return fail(GSFM_ERR_HIP, "upload cov6");
-  if (inlier_weight && et.need_inl && (d_inl.alloc(n_edges) != hipSuccess || (n_edges && hipMemcpy(d_inl.p, inlier_weight, 8 * n_edges, hipMemcpyHostToDevice) != hipSuccess)))
+  if (inlier_weight && et.need_inl && (d_inl.alloc(n_edges) != hipSuccess || (n_edges && hipMemcpyAsync(d_inl.p, inlier_weight, 8 * n_edges, hipMemcpyHostToDevice, P->stream) != hipSuccess)))
     return fail(GSFM_ERR_HIP, "upload inlier weights");
   run_whiten(P, P->cost, d_cov.p, d_inl.p);
   run_whiten(P, P->dir, d_cov.p, d_inl.p);
-  if (hipStreamSynchronize(P->stream) != hipSuccess) return fail(GSFM_ERR_HIP, "whitening kernel failed");
-  return 0;
+  return sync_stream(P->stream, "whitening");   // (d_cov, d_inl are freed here)
 }
 
 // ---- camera buffers, and the launch geometry that sizes some of them ----
@@ -284,17 +287,6 @@ int alloc_camera_buffers(gsfm_rot_problem* P) {
   const size_t N = P->n_cams, NP = P->n_pad;
   P->nb_cam = grid_for(N);
   if (P->nb_cam > GSFM_MAX_PARTIALS * 64) return fail(GSFM_ERR_INVALID_ARG, "too many cameras");
-  bool ok = true;
-  ok &= P->x.alloc(4 * N, true) == hipSuccess; ok &= P->x_trial.alloc(4 * N, true) == hipSuccess; ok &= P->aa_io.alloc(3 * N, true) == hipSuccess;
-  ok &= P->active.alloc(NP, true) == hipSuccess; ok &= P->scale.alloc(3 * N, true) == hipSuccess; ok &= P->gD.alloc(9 * NP, true) == hipSuccess;
-  ok &= P->Mblk.alloc(6 * N) == hipSuccess; ok &= P->Minv.alloc(6 * N) == hipSuccess; ok &= P->Lam.alloc(6 * N) == hipSuccess;
-  ok &= P->Tinv.alloc(9 * N) == hipSuccess; ok &= P->b.alloc(3 * N) == hipSuccess; ok &= P->D6.alloc(6 * N) == hipSuccess;
-  ok &= P->q.alloc(2 * N) == hipSuccess; ok &= P->q_trial.alloc(2 * N) == hipSuccess;
-  ok &= P->xcg.alloc(3 * NP, true) == hipSuccess; ok &= P->r.alloc(3 * NP, true) == hipSuccess; ok &= P->z.alloc(3 * N) == hipSuccess;   // (xcg, r: padded like p / Ap -- a packed sharded problem all-gathers them)
-  ok &= P->p.alloc(3 * NP, true) == hipSuccess; ok &= P->Ap.alloc(3 * NP, true) == hipSuccess; ok &= P->u_rot.alloc(3 * NP, true) == hipSuccess;
-  ok &= P->part_a.alloc(P->nb_cam) == hipSuccess; ok &= P->part_b.alloc(P->nb_cam) == hipSuccess;
-  ok &= P->part_cam.alloc((size_t)6 * P->nb_cam) == hipSuccess; ok &= P->part_gauge.alloc((size_t)9 * P->nb_cam) == hipSuccess; ok &= P->part_cost.alloc((size_t)2 * P->nb_cost) == hipSuccess;
-  ok &= P->scal.alloc(SC_ALL, true) == hipSuccess; ok &= P->cgsc.alloc(1, true) == hipSuccess;
   {  // fused mat-vec of the single-reduction PCG: one row group (256 / G rows) per workgroup unless that leaves too many partials
     const size_t rows_per_group = GSFM_BLOCK / P->G, groups = (P->n_rows + rows_per_group - 1) / rows_per_group;
     size_t max_partials = GSFM_MV_MAX_PARTIALS;
@@ -305,10 +297,20 @@ int alloc_camera_buffers(gsfm_rot_problem* P) {
     P->mv_reps = (int)std::max<size_t>(1, (groups + max_partials - 1) / max_partials);
     P->nb_mv = (int)std::max<size_t>(1, (groups + P->mv_reps - 1) / P->mv_reps);
   }
-  ok &= P->s_dir.alloc(3 * N, true) == hipSuccess; ok &= P->part_g2.alloc((size_t)2 * P->nb_cam, true) == hipSuccess;
-  ok &= P->part_d2.alloc(std::max(P->nb_mv, P->nb_cam), true) == hipSuccess; ok &= P->cg2sc.alloc(1, true) == hipSuccess;
+  bool ok = true;
+  auto plain = [&](auto& buf, size_t count) { ok = ok && buf.alloc(count) == hipSuccess; };
+  auto zeroed = [&](auto& buf, size_t count) { ok = ok && buf.alloc_zeroed(count, P->stream) == hipSuccess; };
+  const size_t nb = (size_t)P->nb_cam;
+  zeroed(P->x, 4 * N); zeroed(P->x_trial, 4 * N); zeroed(P->aa_io, 3 * N); zeroed(P->active, NP); zeroed(P->scale, 3 * N); zeroed(P->gD, 9 * NP);
+  plain(P->Mblk, 6 * N); plain(P->Minv, 6 * N); plain(P->Lam, 6 * N); plain(P->Tinv, 9 * N); plain(P->b, 3 * N); plain(P->D6, 6 * N);
+  plain(P->q, 2 * N); plain(P->q_trial, 2 * N);
+  zeroed(P->xcg, 3 * NP); zeroed(P->r, 3 * NP); plain(P->z, 3 * N);   // (xcg, r: padded like p / Ap -- a packed sharded problem all-gathers them)
+  zeroed(P->p, 3 * NP); zeroed(P->Ap, 3 * NP); zeroed(P->u_rot, 3 * NP);
+  plain(P->part_a, nb); plain(P->part_b, nb); plain(P->part_cam, 6 * nb); plain(P->part_gauge, 9 * nb); plain(P->part_cost, (size_t)2 * P->nb_cost);
+  zeroed(P->scal, SC_ALL); zeroed(P->cgsc, 1);
+  zeroed(P->s_dir, 3 * N); zeroed(P->part_g2, 2 * nb); zeroed(P->part_d2, std::max(P->nb_mv, P->nb_cam)); zeroed(P->cg2sc, 1);
   // (here, not at the first solve: an allocation that fails on one rank only must be part of the create-time agreement)
-  if (P->sharded) ok &= P->w_gather.alloc(((size_t)3 * P->shard.slice_width + P->w_tail) * P->shard.world_size, true) == hipSuccess;
+  if (P->sharded) zeroed(P->w_gather, ((size_t)3 * P->shard.slice_width + P->w_tail) * P->shard.world_size);
   return ok ? 0 : fail(GSFM_ERR_HIP, "allocating camera buffers failed");
 }
 
@@ -316,8 +318,8 @@ int alloc_camera_buffers(gsfm_rot_problem* P) {
 int upload_active_mask(gsfm_rot_problem* P, const std::vector<uint32_t>& rp) {
   std::vector<double> act(P->n_pad, 0.0);
   for (uint32_t r = 0; r < P->n_rows; ++r) act[P->own_begin + r] = (rp[r + 1] > rp[r]) ? 1.0 : 0.0;
-  if (hipMemcpy(P->active.p, act.data(), 8 * (size_t)P->n_pad, hipMemcpyHostToDevice) != hipSuccess) return fail(GSFM_ERR_HIP, "upload active mask");
-  return 0;
+  if (hipMemcpyAsync(P->active.p, act.data(), 8 * (size_t)P->n_pad, hipMemcpyHostToDevice, P->stream) != hipSuccess) return fail(GSFM_ERR_HIP, "upload active mask");
+  return sync_stream(P->stream, "upload active mask");
 }
 
 // ---- sharded: the component labels, the agreement, the collectives after it ----
@@ -332,8 +334,8 @@ int local_component_labels(gsfm_rot_problem* P, const HostStructure& H, std::vec
   if (d_labels->alloc((size_t)P->shard.world_size * NP) != hipSuccess) return fail(GSFM_ERR_HIP, "allocating the component labels failed");
   std::vector<double> lab(NP);
   for (uint32_t c = 0; c < NP; ++c) lab[c] = (double)(*comp_label)[c];
-  if (hipMemcpy(d_labels->p + (size_t)P->shard.rank * NP, lab.data(), 8 * (size_t)NP, hipMemcpyHostToDevice) != hipSuccess) return fail(GSFM_ERR_HIP, "upload component labels");
-  return 0;
+  if (hipMemcpyAsync(d_labels->p + (size_t)P->shard.rank * NP, lab.data(), 8 * (size_t)NP, hipMemcpyHostToDevice, P->stream) != hipSuccess) return fail(GSFM_ERR_HIP, "upload component labels");
+  return sync_stream(P->stream, "upload component labels");
 }
 
 // A rank of a sharded problem sees only its own edges, so whether the GLOBAL view graph is connected -- which decides the PCG tolerance,
@@ -392,11 +394,9 @@ int sharded_agreement(CreateCtx& ctx, const std::vector<uint32_t>& comp_label, D
   if (ctx.coarse_votes_against > 0.5) P->coarse_want = 0;
   if (int st = all_gather(P, P->active.p, P->shard.slice_width)) return st;
   if (int st = all_gather(P, d_labels.p, NP)) return st;
-  std::vector<double> all((size_t)P->shard.world_size * NP);
-  if (hipStreamSynchronize(P->stream) != hipSuccess || hipMemcpy(all.data(), d_labels.p, 8 * all.size(), hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(GSFM_ERR_HIP, "active mask / component labels all-gather failed");
-  std::vector<double> act(NP);
-  if (hipMemcpy(act.data(), P->active.p, 8 * (size_t)NP, hipMemcpyDeviceToHost) != hipSuccess) return fail(GSFM_ERR_HIP, "download active mask");
+  std::vector<double> all((size_t)P->shard.world_size * NP), act(NP);
+  if (int st = read_back(P, all.data(), d_labels.p, 8 * all.size(), "active mask / component labels all-gather")) return st;
+  if (int st = read_back(P, act.data(), P->active.p, 8 * (size_t)NP, "download active mask")) return st;
   const uint32_t comps = global_component_count(all, act, NP, P->shard.world_size);
   P->n_components = std::max<uint32_t>(std::max<uint32_t>(1, comps), (P->shard.flags & GSFM_SHARD_DISCONNECTED) ? 2u : 1u);
   P->packed = P->n_components > 1 && packed_verdict(all, NP, P->shard);
@@ -419,7 +419,7 @@ void alloc_trial_spare_set(gsfm_rot_problem* P, size_t nd_planes) {
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (double)free_b >= (double)need + reserve) {
     if (P->h0_b.alloc(nd_planes) != hipSuccess || P->h1_b.alloc(nd_planes) != hipSuccess || P->h2_b.alloc(nd_planes) != hipSuccess ||
-        P->gD_b.alloc(9 * NP, true) != hipSuccess || P->cs.cost_part.alloc(P->cs.n_wg) != hipSuccess) {
+        P->gD_b.alloc_zeroed(9 * NP, P->stream) != hipSuccess || P->cs.cost_part.alloc(P->cs.n_wg) != hipSuccess) {
       P->h0_b.release(); P->h1_b.release(); P->h2_b.release(); P->gD_b.release(); P->cs.cost_part.release();
     }
   }
@@ -479,6 +479,7 @@ static gsfm_status problem_create_impl(uint32_t n_cams, uint64_t n_edges, const 
   ctx.lap("camera buffers");
   if (P->sharded) if (int st = sharded_agreement(ctx, comp_label, d_labels)) return ctx.bail(st);
   alloc_trial_spare_set(P, nd_planes);
+  if (int st = sync_stream(P->stream, "problem creation")) return ctx.bail(st);   // (the clears and the last copies: gsfm_rot_set_stream may follow at once)
   *live = nullptr;
   *out = P;
   return GSFM_OK;

@@ -75,14 +75,18 @@ bool comps_build(gsfm_rot_problem* P, int cap) {
   for (size_t i = 0; i < items.size(); ++i) item_ptr[i + 1] += item_ptr[i];
   item_cams.resize(item_ptr.back());
   { std::vector<uint32_t> fill(item_ptr.begin(), item_ptr.end() - 1); for (uint32_t k = 0; k < P->n_cams; ++k) if (cam_item[k] >= 0) item_cams[fill[cam_item[k]]++] = k; }
-  if (C.slab.alloc(words, true) != hipSuccess || C.info.alloc(items.size(), true) != hipSuccess || C.active.alloc(items.size(), true) != hipSuccess ||
-      C.stepmax.alloc(items.size(), true) != hipSuccess || C.stepprev.alloc(items.size(), true) != hipSuccess || C.frozen.alloc(items.size(), true) != hipSuccess || C.steprad.alloc(2 * items.size(), true) != hipSuccess ||
-      C.item_ptr.upload(item_ptr) != hipSuccess || C.item_cams.upload(item_cams) != hipSuccess || C.b_pcg.alloc(3 * (size_t)P->n_cams, true) != hipSuccess) {
-    (void)hipGetLastError(); C.slab.release(); return false;
-  }
-  for (size_t i = 0; i < items.size(); ++i) { items[i].A = C.slab.p + offA[i]; items[i].L = C.slab.p + offL[i]; items[i].x = C.slab.p + offX[i]; items[i].info = C.info.p + i; items[i].active = C.active.p + i; }
-  if (C.items.upload(items) != hipSuccess || C.cam_item.upload(cam_item) != hipSuccess || C.cam_loc.upload(cam_loc) != hipSuccess) { (void)hipGetLastError(); return false; }
-  { std::vector<unsigned long long> inf(items.size(), 0x7ff0000000000000ull); if (hipMemcpy(C.stepmax.p, inf.data(), 8 * items.size(), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(C.stepprev.p, inf.data(), 8 * items.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return false; } }   // nothing measured yet
+  // On the problem's stream, never on C.side: run_component_step builds in front of its fork record, so the side stream's first use of the
+  // slab comes after the clears.  One wait at the end, before the staging vectors die.
+  const hipStream_t s = P->stream;
+  const size_t ni = items.size();
+  const std::vector<unsigned long long> inf(ni, 0x7ff0000000000000ull);   // nothing measured yet
+  bool ok = C.slab.alloc_zeroed(words, s) == hipSuccess && C.info.alloc_zeroed(ni, s) == hipSuccess && C.active.alloc_zeroed(ni, s) == hipSuccess &&
+            C.stepmax.upload(inf, s) == hipSuccess && C.stepprev.upload(inf, s) == hipSuccess && C.frozen.alloc_zeroed(ni, s) == hipSuccess &&
+            C.steprad.alloc_zeroed(2 * ni, s) == hipSuccess && C.item_ptr.upload(item_ptr, s) == hipSuccess && C.item_cams.upload(item_cams, s) == hipSuccess &&
+            C.b_pcg.alloc_zeroed(3 * (size_t)P->n_cams, s) == hipSuccess;
+  for (size_t i = 0; ok && i < ni; ++i) { items[i].A = C.slab.p + offA[i]; items[i].L = C.slab.p + offL[i]; items[i].x = C.slab.p + offX[i]; items[i].info = C.info.p + i; items[i].active = C.active.p + i; }
+  ok = ok && C.items.upload(items, s) == hipSuccess && C.cam_item.upload(cam_item, s) == hipSuccess && C.cam_loc.upload(cam_loc, s) == hipSuccess;
+  if (sync_stream(s, "building the component batch") != 0 || !ok) { (void)hipGetLastError(); C.slab.release(); return false; }
   C.n_items = (uint32_t)items.size(); C.Tmax = Tmax; C.n_dense_cams = n_dense; C.all_dense = pcg_comps == 0;
   C.a_words = a_words; C.n_pcg_comps = pcg_comps;
   return true;

@@ -47,9 +47,6 @@ int run_dense(gsfm_rot_problem* P, bool* used, bool plain = false) {
   const uint32_t n = 3 * P->n_cams, T = (n + GSFM_CB - 1) / GSFM_CB;
   if (T > GSFM_DENSE_MAX_T) return 0;
   const size_t elems = chol_num_tiles(T) * GSFM_TILE_ELEMS;
-  if (!P->denseA.p) {
-    if (P->denseA.alloc(elems) != hipSuccess || P->denseL.alloc(elems, true) != hipSuccess || P->dense_x.alloc((size_t)T * GSFM_CB, true) != hipSuccess) { P->denseA.release(); return 0; }
-  }
   auto enqueue = [&]() {
     (void)hipMemsetAsync(P->denseA.p, 0, 8 * elems, P->stream);
     int* const info = (int*)(P->scal.p + SC_DENSE_INFO);
@@ -61,10 +58,13 @@ int run_dense(gsfm_rot_problem* P, bool* used, bool plain = false) {
     // (exact solve: the PCG residual term of the model decrease is zero -- k_dense_assemble cleared it)
   };
   if (plain) {
-    if (!P->denseA.p) return 0;   // (nothing may be allocated under a capture)
+    if (!P->denseA.p) return 0;   // (nothing may be allocated, or cleared on the stream, under a capture: the tiles of an earlier step or none)
     enqueue();
     *used = true;
     return 0;
+  }
+  if (!P->denseA.p) {   // first use; the clears are ordered in front of the capture below
+    if (P->denseA.alloc(elems) != hipSuccess || P->denseL.alloc_zeroed(elems, P->stream) != hipSuccess || P->dense_x.alloc_zeroed((size_t)T * GSFM_CB, P->stream) != hipSuccess) { P->denseA.release(); return 0; }
   }
   const int tk = P->timer.begin(T_CG);
   if (P->dense_graph && (P->dense_graph_lap != P->lin_is_lap || P->dense_graph_planes != P->h0.p)) { (void)hipGraphExecDestroy(P->dense_graph); P->dense_graph = nullptr; }

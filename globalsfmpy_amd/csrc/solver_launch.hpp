@@ -1,4 +1,5 @@
-// Host side, part 2: kernel dispatch on (functor, whitening mode, loss shape), loss preparation, the collective callbacks of a sharded
+// Host side, part 2: kernel dispatch on (functor, whitening mode, loss shape), read-backs and the event-timed launch loop of the timing
+// entries, loss preparation (with the weight planes and the sigma consensus' set-up), the collective callbacks of a sharded
 // problem and the launchers of the per-edge / per-camera kernels (K1 cost sweep, K2 / K2c linearisation, K3 / K3c mat-vec, K5 camera kernels).
 #pragma once
 #include "host_common.hpp"
@@ -102,10 +103,31 @@ int read_back(gsfm_rot_problem* P, void* dst, const void* src_dev, size_t bytes,
   return 0;
 }
 
+// Mean device time (ms) of one launch(): `warmups` untimed launches, then `reps` between two events; the fastest of `rounds` such rounds
+// counts (a round now and then is hit by something else on the box).  launch() returns 0 or a status, which ends the measurement.
+struct EventPair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  bool create() { return hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess; }
+  ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+template <typename F> int timed(gsfm_rot_problem* P, int reps, int warmups, int rounds, const char* what, F&& launch, double* mean_ms) {
+  EventPair ev;
+  if (!ev.create()) return fail(GSFM_ERR_HIP, "event create");
+  for (int round = 0; round < rounds; ++round) {
+    for (int k = -warmups; k < reps; ++k) { if (k == 0) (void)hipEventRecord(ev.e0, P->stream); if (int st = launch()) return st; }
+    (void)hipEventRecord(ev.e1, P->stream);
+    const int st = sync_check(P, what);
+    float ms = 0; (void)hipEventElapsedTime(&ms, ev.e0, ev.e1);
+    if (round == 0 || ms / reps < *mean_ms) *mean_ms = ms / reps;
+    if (st) return st;
+  }
+  return 0;
+}
+
 // ---- loss preparation ---------------------------------------------------------------------
 // The device form of a loss program (node checks, MAGSAC constants, the tables uploaded once into tables[0..2]): shared by the rotation
 // problem (prepare_loss) and the position problem (solver_pos.hpp).
-int build_dev_loss(const gsfm_loss_node* prog, int n, DevBuf<double>* tables, DevLoss& L) {
+int build_dev_loss(const gsfm_loss_node* prog, int n, DevBuf<double>* tables, hipStream_t stream, DevLoss& L) {
   if (n < 0 || n > GSFM_LOSS_MAX_NODES) return fail(GSFM_ERR_INVALID_ARG, "loss program length out of range");
   std::memset(&L, 0, sizeof(L));
   L.n = n;
@@ -154,7 +176,7 @@ int build_dev_loss(const gsfm_loss_node* prog, int n, DevBuf<double>* tables, De
         while (d.x_clamp < c.n && (double)d.x_clamp * (2.0 * squared_sigma) / 1000.0 < 1e-7) d.x_clamp++;   // cells whose s = x 2 sigma^2 / 1000 the reference lifts to 1e-7 (:317)
         const int ti = nu == 3 ? 0 : nu == 4 ? 1 : 2;
         if (!tables[ti].p) {
-          if (tables[ti].upload(magsac_table(nu)) != hipSuccess) return fail(GSFM_ERR_HIP, "uploading MAGSAC table failed");
+          if (tables[ti].upload(magsac_table(nu), stream) != hipSuccess) return fail(GSFM_ERR_HIP, "uploading MAGSAC table failed");
         }
         d.table = tables[ti].p; d.table_len = c.n;
         ++nr; break; }
@@ -169,7 +191,7 @@ int prepare_loss(gsfm_rot_problem* P, const gsfm_loss_node* prog, int n) {
   if (n < 0 || n > GSFM_LOSS_MAX_NODES) return fail(GSFM_ERR_INVALID_ARG, "loss program length out of range");
   P->loss_epoch++;   // (captured LM iterations froze the kernels the old loss selected)
   DevLoss L;
-  if (int st = build_dev_loss(prog, n, P->tables, L)) return st;
+  if (int st = build_dev_loss(prog, n, P->tables, P->stream, L)) return st;
   // K2's fast path assumes rho'' <= 0 for every s (Ceres' Corrector then always takes its alpha = 0 branch).  That is a property of the leaf
   // kind AND of its parameters: Geman-McClure, rho'' = -g2^2 / (a^2 t^3) with t = s / a^2 + g2, turns positive for a negative sigma^2 (g2);
   // a MAGSAC weight loss with a negative sigma flips the sign of rho' and rho''.  Anything doubtful takes the general path (full Corrector).
@@ -188,7 +210,30 @@ int prepare_loss(gsfm_rot_problem* P, const gsfm_loss_node* prog, int n) {
   }
   P->h_loss = L;
   if (!P->d_loss.p && P->d_loss.alloc(1) != hipSuccess) return fail(GSFM_ERR_HIP, "alloc loss");
-  HIPCHK(hipMemcpy(P->d_loss.p, &P->h_loss, sizeof(DevLoss), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpyAsync(P->d_loss.p, &P->h_loss, sizeof(DevLoss), hipMemcpyHostToDevice, P->stream));   // (h_loss persists: DevBuf's lifetime rule)
+  return 0;
+}
+
+// An ANGLE_AXIS problem that is given weights (gsfm_rot_set_edge_weights, the sigma consensus) becomes a scalar-weight problem.
+int promote_to_scalar_weights(gsfm_rot_problem* P) {
+  if (P->wmode != W_NONE) return 0;
+  if (P->cost.ws.alloc(P->cost.n) != hipSuccess || P->dir.ws.alloc(P->dir.n) != hipSuccess) return fail(GSFM_ERR_HIP, "alloc weight planes");
+  P->wmode = W_SCALAR;
+  return 0;
+}
+
+// The sigma consensus' device side: the nu = 3 table and the weight-change sum (both at first use), and the constants of sigma_max
+// (estimator.cpp:352-372) with the weight computation switched off -- the caller switches it on per launch.
+int ensure_sigma(gsfm_rot_problem* P, double sigma_max, SigmaDev* sg) {
+  const MagsacConst c = magsac_const(3);
+  if (!P->sigma_table.p && P->sigma_table.upload(magsac_table(3), P->stream) != hipSuccess) return fail(GSFM_ERR_HIP, "alloc sigma consensus buffers");
+  if (!P->sigma_sum.p && P->sigma_sum.alloc_zeroed(2, P->stream) != hipSuccess) return fail(GSFM_ERR_HIP, "alloc sigma consensus buffers");
+  const double dof_minus_one_per_two = (c.nu - 1.0) / 2.0;
+  *sg = SigmaDev{};
+  sg->table = P->sigma_table.p; sg->table_len = c.n; sg->on = 0;
+  sg->ssm2 = sigma_max * sigma_max * 2.0; sg->inv_ssm2 = 1.0 / sg->ssm2;
+  sg->one_over_sigma = c.C * std::pow(2.0, dof_minus_one_per_two) / sigma_max; sg->gk = c.gk;
+  sg->weight_zero = sg->one_over_sigma * (std::tgamma(dof_minus_one_per_two) - c.gk);
   return 0;
 }
 

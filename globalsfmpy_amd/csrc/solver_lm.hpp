@@ -106,9 +106,15 @@ void to_external(gsfm_rot_problem* P, const double* internal, double* ext, int w
   for (size_t k = 0; k < P->n_cams; ++k) std::memcpy(ext + k * width, internal + (size_t)P->perm[k] * width, 8 * (size_t)width);
 }
 
-int upload_state(gsfm_rot_problem* P, const double* rot_aa) {
+// rot_aa: the caller's rotations, on the host or -- resident (gsfm_rot_solve_resident) -- in device memory: nothing crosses PCIe then.
+int upload_state(gsfm_rot_problem* P, const double* rot_aa, bool resident = false) {
   const size_t N = P->n_cams;
-  HIPCHK(hipMemcpyAsync(P->aa_io.p, to_internal(P, rot_aa, 3), 24 * N, hipMemcpyHostToDevice, P->stream));
+  if (!resident) { HIPCHK(hipMemcpyAsync(P->aa_io.p, to_internal(P, rot_aa, 3), 24 * N, hipMemcpyHostToDevice, P->stream)); }
+  else if (P->perm.empty()) { HIPCHK(hipMemcpyAsync(P->aa_io.p, rot_aa, 24 * N, hipMemcpyDeviceToDevice, P->stream)); }
+  else {
+    if (!P->d_perm.p && P->d_perm.upload(P->perm, P->stream) != hipSuccess) { (void)hipGetLastError(); return fail(GSFM_ERR_HIP, "uploading the camera relabelling failed"); }
+    hipLaunchKernelGGL(k_cam_permute3, dim3(grid_for(N)), dim3(GSFM_BLOCK), 0, P->stream, rot_aa, (const uint32_t*)P->d_perm.p, P->n_cams, 1, P->aa_io.p);
+  }
   if (P->param_dim == 3) { HIPCHK(hipMemcpyAsync(P->x.p, P->aa_io.p, 24 * N, hipMemcpyDeviceToDevice, P->stream)); }
   else {  // estimator.cpp:130-136: angle-axis -> quaternion state
     hipLaunchKernelGGL(k_cam_cache, dim3(grid_for(N)), dim3(GSFM_BLOCK), 0, P->stream, P->aa_io.p, P->n_cams, 3, (double2*)P->x.p);
@@ -116,18 +122,12 @@ int upload_state(gsfm_rot_problem* P, const double* rot_aa) {
   launch_cache(P, P->x.p, P->q.p);
   return 0;
 }
-// The same two transfers for a caller whose rotations live in device memory (gsfm_rot_solve_resident): nothing crosses PCIe.
-int upload_state_resident(gsfm_rot_problem* P, const double* d_rot_aa) {
-  const size_t N = P->n_cams;
-  if (P->perm.empty()) { HIPCHK(hipMemcpyAsync(P->aa_io.p, d_rot_aa, 24 * N, hipMemcpyDeviceToDevice, P->stream)); }
-  else {
-    if (!P->d_perm.p && P->d_perm.upload(P->perm) != hipSuccess) { (void)hipGetLastError(); return fail(GSFM_ERR_HIP, "uploading the camera relabelling failed"); }
-    hipLaunchKernelGGL(k_cam_permute3, dim3(grid_for(N)), dim3(GSFM_BLOCK), 0, P->stream, d_rot_aa, (const uint32_t*)P->d_perm.p, P->n_cams, 1, P->aa_io.p);
-  }
-  if (P->param_dim == 3) { HIPCHK(hipMemcpyAsync(P->x.p, P->aa_io.p, 24 * N, hipMemcpyDeviceToDevice, P->stream)); }
-  else hipLaunchKernelGGL(k_cam_cache, dim3(grid_for(N)), dim3(GSFM_BLOCK), 0, P->stream, P->aa_io.p, P->n_cams, 3, (double2*)P->x.p);
-  launch_cache(P, P->x.p, P->q.p);
-  return 0;
+// What another solve spent is added to a summary's bill: the counters and phase times that the forcing restart (solve_impl) and the sigma
+// consensus' outer loop both accumulate.  Each adds the fields only it reports itself.
+void add_work(gsfm_rot_summary* total, const gsfm_rot_summary& spent) {
+  total->num_cg_iterations += spent.num_cg_iterations; total->num_residual_sweeps += spent.num_residual_sweeps; total->num_linearizations += spent.num_linearizations;
+  total->num_graph_launches += spent.num_graph_launches; total->num_collectives += spent.num_collectives; total->num_pcg_collectives += spent.num_pcg_collectives;
+  total->num_pcg_launched += spent.num_pcg_launched; total->t_linearize_ms += spent.t_linearize_ms; total->t_sweep_ms += spent.t_sweep_ms; total->t_cg_ms += spent.t_cg_ms;
 }
 int download_state_resident(gsfm_rot_problem* P, double* d_rot_aa) {
   const size_t N = P->n_cams;

@@ -92,13 +92,14 @@ bool graph_collectives_ok(const gsfm_rot_problem* P, const gsfm_rot_options& o) 
 }
 
 // ---- the PCG's status without a stream synchronisation (pcg_kernels.hpp, k_pcg_mail) -----------------------------------------------------------
-// mail_usable: allocates on first use (mapped, coherent host memory + the device counter); the read-backs remain the fallback when that fails.
+// mail_usable: allocates on first use (mapped, coherent host memory + the device counter, cleared on the stream: callers ask in front of a
+// capture, never under one); the read-backs remain the fallback when that fails.
 bool mail_usable(gsfm_rot_problem* P) {
   if (P->mail_state == 0) {
     P->mail_state = -1;
     if (hipHostMalloc((void**)&P->mail_host, (GSFM_MAIL_WORDS + 1) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
       std::memset(P->mail_host, 0, (GSFM_MAIL_WORDS + 1) * sizeof(double));
-      if (hipHostGetDevicePointer((void**)&P->mail_dev, P->mail_host, 0) == hipSuccess && P->mail_count.alloc(1, true) == hipSuccess) { P->mail_expected = 0.0; P->mail_state = 1; }
+      if (hipHostGetDevicePointer((void**)&P->mail_dev, P->mail_host, 0) == hipSuccess && P->mail_count.alloc_zeroed(1, P->stream) == hipSuccess) { P->mail_expected = 0.0; P->mail_state = 1; }
     }
     if (P->mail_state < 0) { (void)hipGetLastError(); if (P->mail_host) { (void)hipHostFree(P->mail_host); P->mail_host = nullptr; } }
   }
@@ -223,7 +224,7 @@ int run_pcg(gsfm_rot_problem* P, const gsfm_rot_options& o, double tol, double e
   // once per evaluated step by the caller (solver_components.hpp, packed_exchange).  The ranks' solves end after different iteration counts: nothing in the LM loop is decided from them.
   struct LocalScope { gsfm_rot_problem* P; bool on; ~LocalScope() { if (on) { P->pcg_local = false; P->b_rhs = nullptr; } } } local{P, P->sharded && P->packed};
   if (local.on) {
-    if (!P->b_own.p && P->b_own.alloc(3 * (size_t)P->n_cams, true) != hipSuccess) return fail(GSFM_ERR_HIP, "allocating the rank-local right-hand side failed");
+    if (!P->b_own.p && P->b_own.alloc_zeroed(3 * (size_t)P->n_cams, P->stream) != hipSuccess) return fail(GSFM_ERR_HIP, "allocating the rank-local right-hand side failed");
     if (!resume) hipLaunchKernelGGL(k_mask_range, dim3(grid_for(P->n_cams)), dim3(GSFM_BLOCK), 0, P->stream, (const double*)(P->b_rhs ? P->b_rhs : P->b.p), P->own_begin, P->own_end, P->n_cams, P->b_own.p);
     P->b_rhs = P->b_own.p; P->pcg_local = true;
   }

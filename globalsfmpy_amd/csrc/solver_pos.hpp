@@ -5,7 +5,7 @@
 // iterations).
 // Memory: every array a problem always has lies in one slab laid out by FlatLayout and owned, with the problem's private non-blocking
 // stream, by a FlatCall member (flat_call.hpp).  The dense tiles and the callback buffers are allocated on first use.  Every copy and
-// memset in this file is ordered on that stream (the loss tables of a MAGSAC leaf are uploaded by build_dev_loss, solver_launch.hpp).
+// memset in this file is ordered on that stream (host_common.hpp, DevBuf: the transfer rule), the loss tables of a MAGSAC leaf included.
 #pragma once
 #include "host_common.hpp"
 #include "flat_call.hpp"
@@ -127,8 +127,8 @@ int pos_dense_step(gsfm_pos_problem* P, bool* ok, int* info_out, std::vector<dou
   if (T > GSFM_DENSE_MAX_T) return 0;
   const size_t elems = chol_num_tiles(T) * GSFM_TILE_ELEMS;
   if (!P->denseA.p) {
-    if (P->denseA.alloc(elems) != hipSuccess || P->denseL.alloc(elems, true, P->mem.s) != hipSuccess ||
-        P->dense_x.alloc((size_t)T * GSFM_CB, true, P->mem.s) != hipSuccess ||
+    if (P->denseA.alloc(elems) != hipSuccess || P->denseL.alloc_zeroed(elems, P->mem.s) != hipSuccess ||
+        P->dense_x.alloc_zeroed((size_t)T * GSFM_CB, P->mem.s) != hipSuccess ||
         P->dense_info.alloc(1) != hipSuccess) {
       P->denseA.release(); P->denseL.release(); P->dense_x.release(); (void)hipGetLastError();
       return 0;
@@ -462,7 +462,7 @@ gsfm_status gsfm_pos_set_loss(gsfm_pos_problem* P, const gsfm_loss_node* prog, i
   if (!P || (n > 0 && !prog)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
   DeviceGuard g(P->device);
   DevLoss L;
-  if (int st = build_dev_loss(prog, n, P->tables, L)) return (gsfm_status)st;
+  if (int st = build_dev_loss(prog, n, P->tables, P->mem.s, L)) return (gsfm_status)st;
   bool simple = n == 0;
   if (n == 1) {
     const int k = prog[0].kind;

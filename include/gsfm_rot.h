@@ -379,7 +379,9 @@ void gsfm_rot_options_default(gsfm_rot_options* opt);
  *   inlier_weight one double per edge = (#common tracks)/100 (estimator.cpp:263,268);
  *                 required for the *_INLIERS types, ignored otherwise.
  *   shard         NULL for a single GPU.
- * The current HIP device of the calling thread is used.                        */
+ * The current HIP device of the calling thread is used.  All transfers run on a
+ * stream the problem owns; the call returns with that stream synchronised (the
+ * input arrays may be freed, gsfm_rot_set_stream may follow at once).           */
 gsfm_status gsfm_rot_problem_create(uint32_t n_cams, uint64_t n_edges,
                                     const uint32_t* edge_i, const uint32_t* edge_j,
                                     const double* rel_aa, int32_t error_type,
@@ -389,7 +391,8 @@ gsfm_status gsfm_rot_problem_create(uint32_t n_cams, uint64_t n_edges,
 void gsfm_rot_problem_destroy(gsfm_rot_problem* p);
 
 /* Run all work of this problem on an existing hipStream_t (e.g. torch's current
- * stream).  NULL = a stream owned by the problem (default). */
+ * stream).  NULL = a stream owned by the problem (default).  The stream the
+ * problem leaves is synchronised first. */
 gsfm_status gsfm_rot_set_stream(gsfm_rot_problem* p, void* hip_stream);
 
 /* Replaces the ceres::LossFunction* argument.  n_nodes == 0 -> NULL loss. */
