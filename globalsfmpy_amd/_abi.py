@@ -79,6 +79,19 @@ class Summary(C.Structure):
         return d
 
 
+class StepInfo(C.Structure):
+    """gsfm_rot_step_info (gsfm_rot_step_check, a testing aid)"""
+    _fields_ = [
+        ("path", C.c_int32), ("cg_iterations", C.c_int32), ("loose_cg_iterations", C.c_int32), ("coarse_n", C.c_int32),
+        ("lin_is_lap", C.c_int32), ("column_sorted", C.c_int32), ("graph_launches", C.c_int32), ("dense_info", C.c_int32),
+        ("cg_rel", C.c_double), ("loose_cg_rel", C.c_double), ("cg_tolerance", C.c_double), ("gmax", C.c_double), ("cost", C.c_double),
+        ("step_sums", C.c_double * 5),
+    ]
+
+
+STEP_DENSE, STEP_PCG_TEXTBOOK, STEP_PCG_SINGLE_REDUCTION, STEP_COMPONENTS = range(4)
+
+
 class PosOptions(C.Structure):
     """gsfm_pos_options (include/gsfm_pos.h)"""
     _fields_ = [
@@ -251,6 +264,8 @@ def load_library():
     lib.gsfm_rot_edge_sq_norms.restype = C.c_int
     lib.gsfm_rot_dense_factor_check.argtypes = [C.c_int32, C.c_uint32, _U32P, _DP, _DP, C.POINTER(C.c_int32), _DP, _DP, C.POINTER(C.c_int32)]
     lib.gsfm_rot_dense_factor_check.restype = C.c_int
+    lib.gsfm_rot_step_check.argtypes = [C.c_void_p, _DP, C.c_double, C.c_double, C.POINTER(Options), _DP, _DP, _DP, _DP, _DP, _DP, _DP, C.POINTER(StepInfo)]
+    lib.gsfm_rot_step_check.restype = C.c_int
     lib.gsfm_rot_init_spanning_tree.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, _DP, C.POINTER(C.c_int32), _DP, C.POINTER(C.c_int64),
                                                 _U32P, _U32P, _U32P, _DP]
     lib.gsfm_rot_init_spanning_tree.restype = C.c_int

@@ -529,6 +529,100 @@ gsfm_status gsfm_rot_trial_lin_check(gsfm_rot_problem* P, const double* rot, con
   return (gsfm_status)sync_check(P, "trial_lin_check");
 }
 
+gsfm_status gsfm_rot_step_check(gsfm_rot_problem* P, const double* rot, double radius, double loose_tau, const gsfm_rot_options* opt, double* eta_out,
+                                double* delta_out, double* x_out, double* x_trial_out, double* lam_out, double* eta_loose_out, double* delta_loose_out,
+                                gsfm_rot_step_info* info) {
+  return guarded("the step check", [&]() -> gsfm_status {
+  if (!P || !rot) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
+  if (!(radius > 0.0) || !(loose_tau >= 0.0)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "radius must be positive and loose_tau non-negative");
+  if (P->sharded) return (gsfm_status)fail(GSFM_ERR_UNSUPPORTED, "step_check runs on unsharded problems");
+  DeviceGuard g(P->device);
+  gsfm_rot_options o = opt ? *opt : default_options();
+  o.initial_trust_region_radius = radius; o.max_num_iterations = std::max(o.max_num_iterations, 1);
+  o.pcg_forcing = 0; o.lm_device_control = 0;   // one host-controlled, tight step (loose_tau: LmSolve::check_step)
+  const size_t N = P->n_cams, pd = (size_t)P->param_dim;
+  if (int st = upload_state(P, rot)) return (gsfm_status)st;
+  gsfm_rot_summary sum;
+  LmSolve lm{P, o, o, &sum};
+  LmSolve::StepCheck c;
+  int st = lm.check_step(loose_tau, &c);
+  // (whatever was enqueued has run before the buffers below are read or the problem is used again, on the error path too)
+  if (int s2 = sync_check(P, "step_check")) st = st ? st : s2;
+  P->timer.resolve();
+  if (st) return (gsfm_status)st;
+  const LmSolve::Step& s = c.s;
+  const bool pcg = !s.dense_used && (!s.comp_used || !P->comps.all_dense);
+  const bool single = s.comp_used ? (P->coarse_n == 0 && use_single_reduction(P, lm.o)) : s.single_reduction;
+  double tol_eff = 0.0, last_rel = 0.0;
+  if (pcg) {
+    if (single) { Cg2Scalars h{}; if (int e = read_back(P, &h, P->cg2sc.p, sizeof(h), "step_check: PCG scalars")) return (gsfm_status)e; tol_eff = h.tol; last_rel = h.last_rel; }
+    else { CgScalars h{}; if (int e = read_back(P, &h, P->cgsc.p, sizeof(h), "step_check: PCG scalars")) return (gsfm_status)e; tol_eff = h.tol; last_rel = h.last_rel; }
+  }
+  std::vector<double> eta(3 * N), Ti(9 * N), Lm(6 * N), xt(pd * N), xs(pd * N);
+  if (int e = read_back(P, eta.data(), P->xcg.p, 24 * N, "step_check: eta")) return (gsfm_status)e;
+  if (int e = read_back(P, Ti.data(), P->Tinv.p, 72 * N, "step_check: Tinv")) return (gsfm_status)e;
+  if (int e = read_back(P, Lm.data(), P->Lam.p, 48 * N, "step_check: Lambda")) return (gsfm_status)e;
+  if (int e = read_back(P, xt.data(), P->x_trial.p, 8 * pd * N, "step_check: x_trial")) return (gsfm_status)e;
+  if (int e = read_back(P, xs.data(), P->x.p, 8 * pd * N, "step_check: x")) return (gsfm_status)e;
+  // internal camera k -> the caller's numbering
+  std::vector<size_t> ext(N);
+  for (size_t k = 0; k < N; ++k) ext[P->perm.empty() ? k : (size_t)P->perm[k]] = k;   // ext[internal] = caller's index
+  const auto put = [&](const double* src, double* dst, size_t width) {
+    if (dst) for (size_t k = 0; k < N; ++k) std::memcpy(dst + ext[k] * width, src + k * width, 8 * width);
+  };
+  // delta = Tinv eta, as k_cam_step forms it (the same products in the same order; the host compiler may contract them into fused
+  // multiply-adds where the device's did not, or the reverse: up to 3 u (|Tinv| |eta|) per component away from the device's own delta)
+  const auto apply_Tinv = [&](const double* e, std::vector<double>* d) {
+    d->resize(3 * N);
+    for (size_t k = 0; k < N; ++k) {
+      const double* T = &Ti[9 * k]; const double* v = e + 3 * k;
+      for (int r = 0; r < 3; ++r) (*d)[3 * k + r] = T[3 * r] * v[0] + T[3 * r + 1] * v[1] + T[3 * r + 2] * v[2];
+    }
+  };
+  std::vector<double> tmp;
+  put(eta.data(), eta_out, 3);
+  if (delta_out) { apply_Tinv(eta.data(), &tmp); put(tmp.data(), delta_out, 3); }
+  put(xt.data(), x_trial_out, pd);
+  put(xs.data(), x_out, pd);
+  if (c.loose_cg >= 0) {
+    put(c.eta_loose.data(), eta_loose_out, 3);
+    if (delta_loose_out) { apply_Tinv(c.eta_loose.data(), &tmp); put(tmp.data(), delta_loose_out, 3); }
+  }
+  if (lam_out) {   // Lambda_eta = Tinv^T diag(lam) Tinv (k_cam_prep keeps the block, not lam): lam_c = (T^T Lambda_eta T)_cc with T = inverse(Tinv), a few u relative
+    tmp.resize(3 * N);
+    for (size_t k = 0; k < N; ++k) {
+      const double* A = &Ti[9 * k]; const double* L6 = &Lm[6 * k];
+      const double L[9] = {L6[0], L6[1], L6[2], L6[1], L6[3], L6[4], L6[2], L6[4], L6[5]};
+      const double co[9] = {A[4] * A[8] - A[5] * A[7], A[2] * A[7] - A[1] * A[8], A[1] * A[5] - A[2] * A[4],
+                            A[5] * A[6] - A[3] * A[8], A[0] * A[8] - A[2] * A[6], A[2] * A[3] - A[0] * A[5],
+                            A[3] * A[7] - A[4] * A[6], A[1] * A[6] - A[0] * A[7], A[0] * A[4] - A[1] * A[3]};
+      const double det = A[0] * co[0] + A[1] * co[3] + A[2] * co[6];
+      for (int cc = 0; cc < 3; ++cc) {
+        const double t[3] = {co[cc] / det, co[3 + cc] / det, co[6 + cc] / det};   // column cc of T
+        double v = 0.0;
+        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) v += t[a] * L[3 * a + b] * t[b];
+        tmp[3 * k + cc] = v;
+      }
+    }
+    put(tmp.data(), lam_out, 3);
+  }
+  if (info) {
+    std::memset(info, 0, sizeof(*info));
+    info->path = s.dense_used && !s.comp_used ? GSFM_STEP_DENSE : s.comp_used ? GSFM_STEP_COMPONENTS : s.single_reduction ? GSFM_STEP_PCG_SINGLE_REDUCTION : GSFM_STEP_PCG_TEXTBOOK;
+    info->cg_iterations = s.cg + s.cg_spent; info->cg_tolerance = tol_eff;
+    // (the component step hands the LM loop a converged residual held against the 1e-14 rule of disconnected graphs, run_component_step:
+    // what its PCG solve -- at the requested tolerance where one large component is left -- ended on is in the scalars)
+    info->cg_rel = s.comp_used ? last_rel : s.cg_rel;
+    info->loose_cg_iterations = c.loose_cg; info->loose_cg_rel = c.loose_rel;
+    info->coarse_n = (int32_t)P->coarse_n; info->lin_is_lap = P->lin_is_lap ? 1 : 0; info->column_sorted = P->cs.active ? 1 : 0;
+    info->graph_launches = P->graph_launches; info->dense_info = lm.dense_info();
+    for (int k = 0; k < 5; ++k) info->step_sums[k] = lm.h[SC_STEP + k];
+    info->gmax = lm.gmax; info->cost = lm.x_cost;
+  }
+  return GSFM_OK;
+  });
+}
+
 gsfm_status gsfm_rot_dense_factor_check(int32_t schedule, uint32_t n_items, const uint32_t* n, const double* A, const double* b, const int32_t* active,
                                         double* x_out, double* L_out, int32_t* info_out) {
   return guarded("the dense factorisation check", dense_factor_check_impl, schedule, n_items, n, A, b, active, x_out, L_out, info_out);

@@ -679,6 +679,32 @@ struct LmSolve {
     if (s.step_loose) loose_applied = true;
     return count_accepted(row);
   }
+
+  // ---- gsfm_rot_step_check (a testing aid): iteration 1 of a solve from the uploaded state, up to its evaluated trial point -- through the
+  // phases above, nothing launched from here.  (The caller has switched the forcing schedule and the device-side LM control off: the step is
+  // host-controlled and tight.)  loose_tau > 0 (a PCG-solved step only): the solve first stops at the energy tolerance tau, its iterate is
+  // copied out, and it is continued to cg_relative_tolerance from where it stopped -- refine_loose's `tight` branch without its decisions.
+  struct StepCheck { Step s; int loose_cg = -1; double loose_rel = 0.0; std::vector<double> eta_loose; };
+  int check_step(double loose_tau, StepCheck* c) {
+    const auto ended = [](int r) { return r == 0 ? fail(GSFM_ERR_INVALID_ARG, "step_check: the solve ends before its first step here (zero gradient, non-finite cost, iteration or radius limits)") : r; };
+    if (int r = start(); r != LM_GO_ON) return ended(r);
+    pcg_struggles = true;   // (coarse_build: a forced coarse space is used whatever the graph's size)
+    Step& s = c->s;
+    int r = begin_iteration(s);
+    if (r == LM_GO_ON) r = component_step(s);
+    if (r != LM_GO_ON) return ended(r);
+    if (s.comp_used) return 0;   // (component_step has evaluated it)
+    if (!(loose_tau > 0.0) || s.dense_used) { r = pcg_step(s); return r == LM_GO_ON ? 0 : ended(r); }
+    if (int st = coarse_build(P, pcg_struggles)) return st;
+    if (int st = pcg_solve(P, o, o.cg_relative_tolerance, loose_tau * loose_tau, -1, &s.single_reduction, &s.cg, &s.cg_rel)) return st;
+    c->loose_cg = s.cg; c->loose_rel = s.cg_rel;
+    c->eta_loose.resize(3 * (size_t)P->n_cams);
+    if (int st = read_back(P, c->eta_loose.data(), P->xcg.p, 24 * (size_t)P->n_cams, "step_check: loose iterate")) return st;
+    if (s.cg_rel > o.cg_relative_tolerance) {
+      if (int st = pcg_solve(P, o, o.cg_relative_tolerance, 0.0, s.cg, &s.single_reduction, &s.cg, &s.cg_rel)) return st;
+    }
+    return evaluate(s);
+  }
 };
 
 int lm_solve(gsfm_rot_problem* P, const gsfm_rot_options& o_in, gsfm_rot_summary* sum) {

@@ -242,6 +242,31 @@ class RotationProblem(ProblemBase):
         self._check(st, "solve_resident")
         return s.as_dict()
 
+    def step_check(self, rot_aa, radius=1e4, loose_tau=0.0, **options):
+        """gsfm_rot_step_check (a testing aid): one LM step's linear algebra at rot_aa, as iteration 1 of a solve from there at `radius`, by the
+        solve's own phases.  Returns a dict: eta, delta (n x 3), x, x_trial (n x 3, or n x 4 for the quaternion types), lam (n x 3), the
+        fields of gsfm_rot_step_info (path, cg_iterations, cg_rel, cg_tolerance, coarse_n, lin_is_lap, column_sorted, graph_launches,
+        dense_info, gmax, cost, step_sums), model_cost_change from the step's sums, and with loose_tau > 0 on a PCG-solved step eta_loose,
+        delta_loose, loose_cg_iterations, loose_cg_rel (None / -1 otherwise)."""
+        rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(self.n_cams, 3)
+        o = self._options(options)
+        n = self.n_cams
+        pd = 3 if self.error_type in (_abi.ANGLE_AXIS_COVARIANCE, _abi.ANGLE_AXIS, _abi.ANGLE_AXIS_INLIERS, _abi.ANGLE_AXIS_COV_INLIERS,
+                                      _abi.ANGLE_AXIS_COVTRACE, _abi.ANGLE_AXIS_COVNORM) else 4
+        eta, delta, lam, xs, xt = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, pd)), np.zeros((n, pd))
+        eta_l, delta_l = np.zeros((n, 3)), np.zeros((n, 3))
+        info = _abi.StepInfo()
+        st = self._lib.gsfm_rot_step_check(self._h, _dp(rot), float(radius), float(loose_tau), C.byref(o), _dp(eta), _dp(delta), _dp(xs), _dp(xt), _dp(lam),
+                                           _dp(eta_l), _dp(delta_l), C.byref(info))
+        self._check(st, "step_check")
+        out = {name: getattr(info, name) for name, _ in info._fields_}
+        out["step_sums"] = np.array(list(info.step_sums))
+        s = out["step_sums"]
+        out["model_cost_change"] = -0.5 * s[0] + 0.5 * s[1] + 0.5 * s[2]
+        loose = info.loose_cg_iterations >= 0
+        out.update(eta=eta, delta=delta, x=xs, x_trial=xt, lam=lam, eta_loose=eta_l if loose else None, delta_loose=delta_l if loose else None)
+        return out
+
     def time_sweep(self, rot_aa, reps=20):
         rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(self.n_cams, 3)
         ms = C.c_double(0)

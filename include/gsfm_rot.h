@@ -455,6 +455,50 @@ gsfm_status gsfm_rot_normal_matvec(gsfm_rot_problem* p, const double* v, double*
  * the linearisation at rot_aa (blocks, gD, quaternions) came through the (not accepted) trial unchanged.  Leaves the problem linearised
  * at rot_aa.  GSFM_ERR_UNSUPPORTED where the problem has no fused evaluation (no spare set, kernel or loss without one, GSFM_TRIAL_LIN=0). */
 gsfm_status gsfm_rot_trial_lin_check(gsfm_rot_problem* p, const double* rot_aa, const double* rot_trial, double* cost_out, int32_t* same_out);
+/* A TESTING AID, not part of a pipeline: one LM step's linear algebra at rot_aa, as iteration 1 of a gsfm_rot_solve from there with the trust
+ * radius `radius`, run by the solve's own phases (state upload, cost and linearisation, the damping with the Jacobi scaling initialised, then
+ * what the iteration itself runs: the exact Cholesky step, the component step of a disconnected graph, or the coarse matrix and the PCG solve;
+ * the trial point and the step's sums) and stopped before the trust-region decision.  `opt` (NULL: defaults) applies as in a solve, except
+ * that initial_trust_region_radius is `radius`, the forcing schedule and the device-side LM control are off (pcg_forcing = 0,
+ * lm_device_control = 0: one host-controlled step at cg_relative_tolerance) and a two-level preconditioner the problem was created with
+ * (GSFM_PCG_COARSE) is used at once, as in a solve that has seen PCG struggle.  A disconnected graph keeps the solve's 1e-14 rule.
+ * Outputs, each may be NULL, per camera in the caller's numbering:
+ *   eta_out      3: the solution of (J^T J + Lambda) eta = -g in the solver's internal (left) tangent, by whichever path ran
+ *   delta_out    3: Tinv eta, the step in the reference's own parameters (additive angle-axis / the quaternion tangent).  Formed on the host
+ *                from the downloaded eta and Tinv with k_cam_step's expression: within 3 u |Tinv| |eta| per component of the device's own
+ *                delta (the two compilers may contract the products differently), which x_trial_out carries
+ *   x_out        3 or 4 (the quaternion types: x, y, z, w): the state x at rot_aa as the device holds it
+ *   x_trial_out  as x_out: Plus(x, delta) as the device formed it
+ *   lam_out      3: the damping diagonal in the reference's parameters (lam[c] of k_cam_prep), recovered on the host from the stored block
+ *                Lambda_eta = Tinv^T diag(lam) Tinv as diag(T^T Lambda_eta T), T = inverse(Tinv): a few u relative
+ *   loose_tau > 0 (a PCG-solved step only; ignored on the other paths, info->loose_cg_iterations = -1): the solve first stops where the
+ *                estimated relative energy error falls below loose_tau (as a loose solve of the forcing schedule: etol2 = loose_tau^2), the
+ *                iterate goes to eta_loose_out / delta_loose_out, and the solve is continued to cg_relative_tolerance from where it
+ *                stopped, as the schedule's refinement continues it; eta_out / delta_out are the continued solve's
+ * Leaves the problem linearised at rot_aa.                                                                                              */
+enum { GSFM_STEP_DENSE = 0, GSFM_STEP_PCG_TEXTBOOK = 1, GSFM_STEP_PCG_SINGLE_REDUCTION = 2, GSFM_STEP_COMPONENTS = 3 };
+typedef struct {
+  int32_t path;                 /* GSFM_STEP_*: what solved the step */
+  int32_t cg_iterations;        /* PCG iterations of the step (the loose part included) */
+  int32_t loose_cg_iterations;  /* iterations at which the loose solve stopped; -1: there was none */
+  int32_t coarse_n;             /* aggregates of the two-level preconditioner in use (0: block-Jacobi) */
+  int32_t lin_is_lap;           /* 1: the mat-vec runs on the body-frame (Laplacian) blocks, 0: on the general ones */
+  int32_t column_sorted;        /* 1: the column-sorted layout (K2c / K3c) */
+  int32_t graph_launches;       /* hipGraph replays of this call */
+  int32_t dense_info;           /* status word of the factorisation(s): 0, or 1 + the first bad pivot */
+  double cg_rel;                /* relative residual sqrt(r.M^-1 r / b.M^-1 b) as the PCG solve reports it (component step: the last one its
+                                   kernels saw; the LM loop is handed that value held against the 1e-14 rule of disconnected graphs) */
+  double loose_cg_rel;          /* ... of the loose solve where it stopped */
+  double cg_tolerance;          /* the tolerance the PCG kernels tested against: cg_relative_tolerance raised to the absolute floor
+                                   (2e-14 rad per camera) where that binds; 0 without PCG */
+  double gmax;                  /* gradient max norm at rot_aa */
+  double cost;                  /* cost at rot_aa */
+  double step_sums[5];          /* k_cam_step's sums: eta.g, eta.r_cg, eta^T Lambda eta, |x - x_trial|^2, |x_trial|^2 (active cameras);
+                                   model cost change = -1/2 [0] + 1/2 [1] + 1/2 [2] */
+} gsfm_rot_step_info;
+gsfm_status gsfm_rot_step_check(gsfm_rot_problem* p, const double* rot_aa, double radius, double loose_tau, const gsfm_rot_options* opt,
+                                double* eta_out, double* delta_out, double* x_out, double* x_trial_out, double* lam_out,
+                                double* eta_loose_out, double* delta_loose_out, gsfm_rot_step_info* info);
 /* Check of the exact step's factorisation (no problem object needed): factorises the SPD matrices A and solves A x = b with the launches the
  * LM step itself runs (the dense tiled Cholesky of dense_cholesky_max_cams / dense_cholesky_auto_cams).  schedule 0: one matrix, the default
  * schedule (two block columns per launch); 1: one matrix, the fused step (GSFM_CHOL_FUSED=1); 2: n_items matrices side by side, as the

@@ -362,3 +362,223 @@ def c_row(deg, c0=64):
     recursive-summation term (Higham: n - 1 additions of a row's summands, whatever the order and grouping)."""
     return (c0 + np.asarray(deg, float))
 
+
+
+# ---- the damped normal system of one LM step, in the reference's parameters (tests/test_hp_step_reference.py, test_gpu_hp_step.py) ----
+# The device solves (J^T J + Lambda) eta = -g in its internal tangent eta = T delta and stops PCG on sqrt(r.M^-1 r / b.M^-1 b) with M the
+# damped diagonal blocks.  With K* = T^T K_eta T, b* = T^T b_eta, M* = T^T M_eta T and r* = b* - K* delta = T^T r_eta:
+#   r*.M*^-1 r* = r_eta^T T (T^-1 M_eta^-1 T^-T) T^T r_eta = r_eta.M_eta^-1 r_eta   (likewise for b),
+# so the stopping quantity is the same number here, and a device step delta = T^-1 eta can be judged without knowing T.
+def sym3_inverse(M):
+    """Inverses of n symmetric 3 x 3 matrices (n x 3 x 3, long double) by cofactors."""
+    M = np.asarray(M, LD)
+    a, b, c, d, e, f = M[:, 0, 0], M[:, 0, 1], M[:, 0, 2], M[:, 1, 1], M[:, 1, 2], M[:, 2, 2]
+    c00, c01, c02 = d * f - e * e, c * e - b * f, b * e - c * d
+    det = a * c00 + b * c01 + c * c02
+    out = np.empty_like(M)
+    out[:, 0, 0], out[:, 0, 1], out[:, 0, 2] = c00, c01, c02
+    out[:, 1, 1], out[:, 1, 2], out[:, 2, 2] = a * f - c * c, b * c - a * e, a * d - b * b
+    out[:, 1, 0], out[:, 2, 0], out[:, 2, 1] = out[:, 0, 1], out[:, 0, 2], out[:, 1, 2]
+    return out / det[:, None, None]
+
+
+def damped_system(A, radius, jacobi_scaling=True, min_diag=1e-6, max_diag=1e32):
+    """LevenbergMarquardtStrategy's system from assemble()'s output: lam* (n x 3), b* = -g*, the blocks M_k = D*_k + diag(lam*_k) and
+    their inverses.  A camera without an edge has D = 0, g = 0: lam = min_diag / radius, b = 0."""
+    D = A["D"]
+    dd = np.stack([D[:, 0, 0], D[:, 1, 1], D[:, 2, 2]], axis=1)
+    sc = 1 / (1 + np.sqrt(dd)) if jacobi_scaling else np.ones_like(dd)
+    lam = np.clip(sc * sc * dd, LD(min_diag), LD(max_diag)) / (LD(radius) * sc * sc)
+    M = D.copy()
+    for c in range(3):
+        M[:, c, c] += lam[:, c]
+    return {"lam": lam, "b": -A["g"], "M": M, "Minv": sym3_inverse(M), "radius": radius}
+
+
+def system_apply(lin, sysm, n_cams, edge_i, edge_j, delta):
+    """(K* delta, the magnitude sum that bounds |K*| |delta| to first order, H* delta)."""
+    delta = np.asarray(delta, LD).reshape(n_cams, 3)
+    y, ym, _ = matvec(lin, n_cams, edge_i, edge_j, delta)
+    return y + sysm["lam"] * delta, ym + sysm["lam"] * np.abs(delta), y
+
+
+def mnorm(sysm, z, cams=None):
+    """||z||_{M^-1}, over all cameras or the subset `cams`."""
+    z = np.asarray(z, LD).reshape(-1, 3)
+    Mi = sysm["Minv"]
+    if cams is not None:
+        z, Mi = z[cams], Mi[cams]
+    return np.sqrt(np.einsum("ka,kab,kb->", z, Mi, z))
+
+
+def step_residual(lin, A, sysm, n_cams, edge_i, edge_j, delta, cams=None, c0=64.0, ca=16.0):
+    """The true relative residual of `delta` in the M^-1 norm, sqrt(r.M^-1 r / b.M^-1 b), r = b* - K* delta, and the rounding floor
+       || c0 u (|K*||delta| + |b*|) + c_row(deg, ca) u (|K*||delta| + g_mag) ||_{M^-1} / ||b*||_{M^-1}:
+    what a double-precision evaluation of r at this delta can be off by -- c0 roundings on the operands' magnitudes (the block's
+    products, the subtraction from b), the assembled quantities' own bound (test_gpu_hp_linearization.py: c_k = ca + deg(k) on the
+    first-order magnitude sums of the mat-vec and of the gradient).  cams: restrict both norms to a subset (one connected component)."""
+    Kd, aKd, _ = system_apply(lin, sysm, n_cams, edge_i, edge_j, delta)
+    r = sysm["b"] - Kd
+    ck = c_row(A["deg"], ca)[:, None]
+    e = c0 * U * (aKd + np.abs(sysm["b"])) + ck * U * (aKd + A["g_mag"])
+    bn = mnorm(sysm, sysm["b"], cams)
+    return float(mnorm(sysm, r, cams) / bn), float(mnorm(sysm, e, cams) / bn), r
+
+
+def model_cost_change(lin, A, n_cams, edge_i, edge_j, delta):
+    """-delta.g* - 1/2 delta^T H* delta, and the magnitude sum |delta|.|g*| + 1/2 |delta|^T |H*| |delta| of its terms."""
+    delta = np.asarray(delta, LD).reshape(n_cams, 3)
+    y, ym, _ = matvec(lin, n_cams, edge_i, edge_j, delta)
+    ad = np.abs(delta)
+    return -(delta * A["g"]).sum() - LD(0.5) * (delta * y).sum(), (ad * (np.abs(A["g"]) + A["g_mag"])).sum() + LD(0.5) * (ad * ym).sum()
+
+
+def system_matrix(lin, sysm, n_cams, edge_i, edge_j):
+    """The dense K* = H* + diag(lam*) (3n x 3n, long double)."""
+    K = normal_matrix(lin, n_cams, edge_i, edge_j)
+    K[np.diag_indices(3 * n_cams)] += sysm["lam"].reshape(-1)
+    return K
+
+
+def solve_refined(K, b, sweeps=3):
+    """K x = b: a float64 LAPACK solve refined with long-double residuals (each sweep gains ~1 / (kappa u) digits)."""
+    Kf = np.array(K, float)
+    import scipy.linalg as sla
+    cf = sla.cho_factor(Kf)
+    b = np.asarray(b, LD).reshape(-1)
+    x = np.zeros_like(b)
+    for _ in range(sweeps + 1):
+        x = x + sla.cho_solve(cf, np.array(b - K @ x, float)).astype(LD)
+    return x
+
+
+# ---- the graphs of the step tests --------------------------------------------------------------------------------------------------
+def _rel_measured(gt_aa, i, j, noise_aa):
+    """rel_aa of edge (i, j): Exp(noise) R_j R_i^T (R_j = R_ij R_i)."""
+    from globalsfmpy_amd import synth
+    q = synth.aa_to_quat(gt_aa)
+    qr = synth.quat_mul(synth.quat_mul(synth.aa_to_quat(noise_aa), q[j]), synth.quat_conj(q[i]))
+    return synth.quat_to_aa(qr)
+
+
+def iso_cov6(n_edges, seed):
+    """Per-edge isotropic covariances sigma_e^2 I, sigma_e log-uniform over a decade (0.5 to 5 degrees), scaled as synth.make_graph scales
+    its own (3e-4 Sigma): kappa(Sigma) = 1, so the whitening's own error term C_WHITEN kappa u, which puts the step floor of make_graph's
+    covariances (kappa up to 96) at 2.3-3.8e-10, vanishes from the bound.  Measured with these on the main graph under Huber(0.5), radius 1e4: floor 1.63e-13 for
+    ANGLE_AXIS_COVARIANCE and 1.95e-13 for ANGLE_AXIS_COV_INLIERS (tests/test_hp_step_reference.py prints them)."""
+    rng = np.random.default_rng(seed)
+    s2 = 3e-4 * np.deg2rad(10.0 ** rng.uniform(np.log10(0.5), np.log10(5.0), n_edges)) ** 2
+    c = np.zeros((n_edges, 6))
+    c[:, 0] = c[:, 1] = c[:, 2] = s2
+    return c
+
+
+def _with_hubs(g, hubs, seed, noise_deg=1.0):
+    """Adds edges from the hub cameras (camera, target degree) to cameras that are not yet their neighbours, alternating the edge's
+    orientation, measured from the ground truth with `noise_deg` of noise."""
+    rng = np.random.default_rng(seed)
+    n = g["n_cams"]
+    ei, ej, rel = list(g["edge_i"]), list(g["edge_j"]), list(g["rel_aa"])
+    hub_ids = set(h for h, _ in hubs)
+    for hub, target in hubs:
+        nb = set(j for i, j in zip(ei, ej) if i == hub) | set(i for i, j in zip(ei, ej) if j == hub)
+        deg = len([1 for i, j in zip(ei, ej) if hub in (i, j)])
+        free = [c for c in range(n) if c not in nb and c not in hub_ids]
+        picks = rng.permutation(free)[:target - deg]
+        assert len(picks) == target - deg
+        for k, m in enumerate(picks):
+            i, j = (hub, int(m)) if k % 2 else (int(m), hub)
+            ei.append(i); ej.append(j)
+            rel.append(_rel_measured(g["gt_aa"], i, j, np.deg2rad(noise_deg) * rng.standard_normal(3)))
+    E = len(ei)
+    out = dict(g)
+    out.update(edge_i=np.array(ei, dtype=np.uint32), edge_j=np.array(ej, dtype=np.uint32), rel_aa=np.array(rel),
+               cov6=iso_cov6(E, seed + 1), inlier_weight=np.random.default_rng(seed + 2).uniform(0.2, 3.0, E), rot=g["init_aa"])
+    return out
+
+
+def step_main_graph(seed=11):
+    """600 cameras -- three blocks of 256 of the camera kernels, the last partial -- from synth.make_graph(600, 1500) with its init_aa as
+    the linearisation point (2 degrees from the ground truth) and hubs of degree 63 / 64 / 65 / 300 on top: about 2000 edges.  A tenth of
+    make_graph's non-chain edges are outliers (uniform random rotations), so that Huber(0.5) and the Tolerant loss are on their
+    non-trivial branches on some edges."""
+    from globalsfmpy_amd import synth
+    g = synth.make_graph(600, 1500, seed, outlier_frac=0.1)
+    return _with_hubs(g, ((0, 300), (1, 63), (2, 64), (3, 65)), seed)
+
+
+def step_delta_graph(seed=12):
+    """150 cameras (450 unknowns: a long-double Cholesky solve is affordable), one hub of degree 65."""
+    from globalsfmpy_amd import synth
+    g = synth.make_graph(150, 400, seed, outlier_frac=0.1)
+    return _with_hubs(g, ((0, 65),), seed)
+
+
+def step_two_component_graph(seed=13):
+    """A component of 36 cameras (factorised under dense_cholesky_max_cams = 40) beside one of 300 (PCG) and two cameras without an
+    edge, interleaved in the numbering.  comp: 0 the large component, 1 the small one, 2 the isolated cameras."""
+    from globalsfmpy_amd import synth
+    a = _with_hubs(synth.make_graph(300, 800, seed, outlier_frac=0.1), ((0, 65),), seed)
+    b = _with_hubs(synth.make_graph(36, 90, seed + 5, outlier_frac=0.1), (), seed + 5)
+    n = 338
+    ids = np.random.default_rng(seed).permutation(n)
+    ia, ib = np.sort(ids[:300]), np.sort(ids[300:336])
+    out = {"n_cams": n, "comp": np.full(n, 2)}
+    out["comp"][ia], out["comp"][ib] = 0, 1
+    out["edge_i"] = np.concatenate([ia[a["edge_i"]], ib[b["edge_i"]]]).astype(np.uint32)
+    out["edge_j"] = np.concatenate([ia[a["edge_j"]], ib[b["edge_j"]]]).astype(np.uint32)
+    for k in ("rel_aa", "cov6", "inlier_weight"):
+        out[k] = np.concatenate([a[k], b[k]])
+    out["rot"] = 0.1 * np.random.default_rng(seed + 9).standard_normal((n, 3))
+    out["rot"][ia], out["rot"][ib] = a["rot"], b["rot"]
+    return out
+
+
+STEP_LOSSES = {"none": (None, ()), "huber": ("huber", (0.5,)), "tolerant": ("tolerant", (0.05, 0.01))}
+STEP_GRAPHS = {"main": step_main_graph, "delta": step_delta_graph, "twocomp": step_two_component_graph}
+# every (graph, error type, loss, radius) the device tests linearise at: the CPU test asserts the floor condition on each of them
+STEP_CASES = [("main", _abi.ANGLE_AXIS, "huber", 1e4), ("main", _abi.ANGLE_AXIS, "huber", 1e12), ("main", _abi.ANGLE_AXIS, "none", 1e4),
+              ("main", _abi.ANGLE_AXIS, "tolerant", 1e4), ("main", _abi.QUATERNION_COSINE, "huber", 1e4),
+              ("main", _abi.QUATERNION_NORM, "huber", 1e4), ("main", _abi.ANGLE_AXIS_COVARIANCE, "huber", 1e4),
+              ("main", _abi.ANGLE_AXIS_COV_INLIERS, "huber", 1e4), ("twocomp", _abi.ANGLE_AXIS, "huber", 1e4),
+              ("delta", _abi.ANGLE_AXIS, "huber", 1e4), ("delta", _abi.ANGLE_AXIS, "huber", 1e12)]
+STEP_FLOOR_MAX = 5e-13   # tol / 2 at cg_relative_tolerance = 1e-12: the reference's own floor at the exact solution must stay below
+_STEP_CACHE = {}
+
+
+def step_graph(name):
+    if ("g", name) not in _STEP_CACHE:
+        _STEP_CACHE[("g", name)] = STEP_GRAPHS[name]()
+    return _STEP_CACHE[("g", name)]
+
+
+def step_reference(name, et, lname, radius):
+    """(graph, lin, A, sysm) of a step case, cached per process: the tier-1 edge set per (graph, error type), the corrected
+    linearisation per loss, the damped system per radius."""
+    g = step_graph(name)
+    n, ei, ej = g["n_cams"], g["edge_i"], g["edge_j"]
+    k1 = ("e", name, et)
+    if k1 not in _STEP_CACHE:
+        _STEP_CACHE[k1] = edge_set(et, ei, ej, g["rel_aa"], g["rot"], g["cov6"], g["inlier_weight"])
+    k2 = ("l", name, et, lname)
+    if k2 not in _STEP_CACHE:
+        kind, params = STEP_LOSSES[lname]
+        lin = corrected(_STEP_CACHE[k1], kind, params)
+        if kind == "huber":   # no edge at the knee, where finite differences and a kernel may disagree
+            assert np.all(np.abs(lin["s"].astype(float) - 0.25) > 1e-9 * 0.25)
+        _STEP_CACHE[k2] = (lin, assemble(lin, n, ei, ej))
+    lin, A = _STEP_CACHE[k2]
+    k3 = ("s", name, et, lname, radius)
+    if k3 not in _STEP_CACHE:
+        _STEP_CACHE[k3] = damped_system(A, radius)
+    return g, lin, A, _STEP_CACHE[k3]
+
+
+def step_solution(name, et, lname, radius):
+    """delta* = K*^-1 b* (n x 3, long double), cached."""
+    k = ("x", name, et, lname, radius)
+    if k not in _STEP_CACHE:
+        g, lin, A, sysm = step_reference(name, et, lname, radius)
+        K = system_matrix(lin, sysm, g["n_cams"], g["edge_i"], g["edge_j"])
+        _STEP_CACHE[k] = solve_refined(K, sysm["b"]).reshape(-1, 3)
+    return _STEP_CACHE[k]

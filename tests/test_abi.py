@@ -52,6 +52,25 @@ def test_oracle_and_product_share_option_defaults(oracle):
     assert bytes(a) == bytes(b)
 
 
+def test_step_check_is_exported_with_its_prototype_and_info_struct():
+    """gsfm_rot_step_check (a testing aid): the export, the ctypes prototype -- thirteen arguments, the last a gsfm_rot_step_info -- and the
+    struct's fields in the header's order."""
+    from globalsfmpy_amd import _abi
+    lib = _abi.load_library()
+    assert hasattr(lib, "gsfm_rot_step_check")
+    f = lib.gsfm_rot_step_check
+    assert f.restype is C.c_int and len(f.argtypes) == 13
+    assert f.argtypes[2] is C.c_double and f.argtypes[3] is C.c_double
+    assert f.argtypes[4] is C.POINTER(_abi.Options) and f.argtypes[12] is C.POINTER(_abi.StepInfo)
+    hdr = open(os.path.join(ROOT, "include", "gsfm_rot.h")).read()
+    body = hdr[hdr.index("typedef struct {\n  int32_t path;"):hdr.index("} gsfm_rot_step_info;")]
+    names_h = re.findall(r"^\s+(?:int32_t|double)\s+(\w+)(?:\[\d+\])?;", body, flags=re.M)
+    assert names_h == [n for n, _ in _abi.StepInfo._fields_], names_h
+    assert C.sizeof(_abi.StepInfo) == 8 * 4 + 8 * 10
+    assert "TESTING AID" in hdr[hdr.index("enum { GSFM_STEP_DENSE") - 4000:hdr.index("enum { GSFM_STEP_DENSE")]
+    assert (_abi.STEP_DENSE, _abi.STEP_PCG_TEXTBOOK, _abi.STEP_PCG_SINGLE_REDUCTION, _abi.STEP_COMPONENTS) == (0, 1, 2, 3)
+
+
 @pytest.mark.skipif(have_gpu(), reason="CPU-only behaviour")
 def test_fails_loudly_without_a_gpu():
     from globalsfmpy_amd.solver import RotationProblem, SolverError
