@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""The reference's scripts/sfm_pipeline.py 1DSfM branch through step 7: rotations, FilterRotations(), OptimizePairwiseTranslations() (every
+"""The reference's scripts/sfm_pipeline.py 1DSfM branch through BundleAdjustCameraPositionsAndPoints: rotations, FilterRotations(), OptimizePairwiseTranslations() (every
 pair's position_2 refined with the estimated rotations), FilterRelativeTranslation() (the 1DSfM filter), then camera positions
 (EstimatePosition(HuberLoss(0.1), PositionErrorType.BASELINE) there; NonlinearPositionEstimator.EstimatePositions here), then
-EstimateStructure(refine=True) (every track triangulated, refined per track when the flags say bundle_adjust_tracks, and gated) and the PLY with the estimated tracks' points
-and the estimated camera positions.
+EstimateStructure(refine=True) (every track triangulated, refined per track when the flags say bundle_adjust_tracks, and gated),
+SetUnderconstrainedAsUnestimated and BundleAdjustCameraPositionsAndPoints() (camera positions and points adjusted together, orientations and
+intrinsics held), and the PLY with the estimated tracks' points and the estimated camera positions.
 usage: position_pipeline.py <dataset_dir with EGs.txt, cc.txt> [flags.yaml]"""
 import os
 import sys
@@ -16,7 +17,8 @@ import GlobalSfMpy as sfm  # noqa: E402
 from globalsfmpy_amd.loss_functions import HuberLoss  # noqa: E402
 
 
-def position_pipeline(dataset_dir, flagfile=None):
+def run_pipeline(dataset_dir, flagfile=None):
+    """(reconstruction, position estimator, reconstruction estimator)"""
     opts = sfm.ReconstructionBuilderOptions()
     if flagfile:
         sfm.load_1DSFM_config(flagfile, opts)
@@ -34,13 +36,20 @@ def position_pipeline(dataset_dir, flagfile=None):
                                        sfm.PositionErrorType.BASELINE), estimator.LastError()
     sfm.SetReconstructionFromEstimatedPoses(solver.orientations, positions, scene)
     solver.EstimateStructure(refine=True)        # a dataset without tracks.txt has nothing to triangulate
-    return scene, estimator
+    sfm.SetUnderconstrainedAsUnestimated(scene)
+    assert solver.BundleAdjustCameraPositionsAndPoints(), solver.LastBundleAdjustmentSummary()
+    return scene, estimator, solver
+
+
+def position_pipeline(dataset_dir, flagfile=None):
+    return run_pipeline(dataset_dir, flagfile)[:2]
 
 
 if __name__ == "__main__":
     dataset = sys.argv[1]
-    scene, estimator = position_pipeline(dataset, sys.argv[2] if len(sys.argv) > 2 else None)
+    scene, estimator, solver = run_pipeline(dataset, sys.argv[2] if len(sys.argv) > 2 else None)
     print("estimated %d positions (view %d held at the origin); solver summary: %s"
           % (len(scene.EstimatedPositions()), estimator.FixedView(), estimator.LastSummary()))
     print("estimated %d of %d tracks" % (scene.NumEstimatedTracks(), scene.NumTracks()))
+    print("bundle adjustment of positions and points: %s" % solver.LastBundleAdjustmentSummary())
     sfm.WritePlyFile(os.path.join(dataset, "positions_out.ply"), scene, 2)

@@ -127,6 +127,42 @@ class PosSummary(C.Structure):
         return d
 
 
+class BaOptions(C.Structure):
+    """gsfm_ba_options (include/gsfm_ba.h)"""
+    _fields_ = [
+        ("max_num_iterations", C.c_int32), ("jacobi_scaling", C.c_int32),
+        ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
+        ("parameter_tolerance", C.c_double), ("initial_trust_region_radius", C.c_double),
+        ("max_trust_region_radius", C.c_double), ("min_trust_region_radius", C.c_double),
+        ("min_relative_decrease", C.c_double), ("min_lm_diagonal", C.c_double),
+        ("max_lm_diagonal", C.c_double), ("max_cg_iterations", C.c_int32),
+        ("cg_check_interval", C.c_int32), ("cg_relative_tolerance", C.c_double),
+        ("cg_stall_iterations", C.c_int32), ("remove_gauge", C.c_int32),
+        ("verbose", C.c_int32), ("reserved_", C.c_int32),
+    ]
+
+
+class BaSummary(C.Structure):
+    """gsfm_ba_summary (include/gsfm_ba.h)"""
+    _fields_ = [
+        ("termination", C.c_int32), ("num_iterations", C.c_int32),
+        ("num_successful_steps", C.c_int32), ("num_unsuccessful_steps", C.c_int32),
+        ("num_cg_iterations", C.c_int32), ("num_pcg_stalled_steps", C.c_int32),
+        ("num_residual_sweeps", C.c_int32), ("num_linearizations", C.c_int32),
+        ("nonfinite", C.c_int32), ("reserved_", C.c_int32),
+        ("num_observations_used", C.c_uint64), ("num_active_cameras", C.c_uint64),
+        ("num_active_points", C.c_uint64),
+        ("initial_cost", C.c_double), ("final_cost", C.c_double),
+        ("final_gradient_max_norm", C.c_double), ("final_radius", C.c_double),
+        ("max_radius", C.c_double), ("t_total_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
+        d["termination_name"] = TERMINATION_NAMES[self.termination] if 0 <= self.termination < 5 else "?"
+        return d
+
+
 class TrackRefineOptions(C.Structure):
     """gsfm_tracks_refine_options (include/gsfm_tracks.h)"""
     _fields_ = [
@@ -277,6 +313,7 @@ def load_library():
     lib.gsfm_magsac_constants.argtypes = [C.c_int32, _DP, _DP, _DP]; lib.gsfm_magsac_constants.restype = C.c_int
     declare_position_signatures(lib)
     declare_track_signatures(lib)
+    declare_ba_signatures(lib)
     _lib = lib
     return lib
 
@@ -319,3 +356,21 @@ def declare_track_signatures(lib):
                                                    C.POINTER(TrackRefineOptions), C.POINTER(LossNode), C.c_int32,
                                                    _DP, i32p, i32p, _DP, i32p, _DP, _DP, i32p, u64p, _DP]
     lib.gsfm_tracks_triangulate_refine.restype = C.c_int
+
+
+def declare_ba_signatures(lib):
+    """include/gsfm_ba.h"""
+    u8p, u64p, i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    lib.gsfm_ba_abi_version.restype = C.c_int
+    lib.gsfm_ba_options_default.argtypes = [C.POINTER(BaOptions)]; lib.gsfm_ba_options_default.restype = None
+    lib.gsfm_ba_problem_create.argtypes = [C.c_uint32, _DP, _DP, u8p, C.c_uint64, u64p, _U32P, _DP, u8p, C.POINTER(C.c_void_p)]
+    lib.gsfm_ba_problem_create.restype = C.c_int
+    lib.gsfm_ba_set_loss.argtypes = [C.c_void_p, C.POINTER(LossNode), C.c_int32]; lib.gsfm_ba_set_loss.restype = C.c_int
+    lib.gsfm_ba_solve.argtypes = [C.c_void_p, _DP, _DP, C.POINTER(BaOptions), C.POINTER(BaSummary)]; lib.gsfm_ba_solve.restype = C.c_int
+    lib.gsfm_ba_residuals.argtypes = [C.c_void_p, _DP, _DP, _DP, _DP]; lib.gsfm_ba_residuals.restype = C.c_int
+    lib.gsfm_ba_linearize.argtypes = [C.c_void_p, _DP, _DP, _DP, _DP, _DP, _DP, _DP]; lib.gsfm_ba_linearize.restype = C.c_int
+    lib.gsfm_ba_schur_matvec.argtypes = [C.c_void_p, _DP, C.c_double, C.POINTER(BaOptions), _DP]; lib.gsfm_ba_schur_matvec.restype = C.c_int
+    lib.gsfm_ba_step_check.argtypes = [C.c_void_p, _DP, _DP, C.c_double, C.POINTER(BaOptions), _DP, _DP, _DP, _DP, _DP, _DP, i32p]
+    lib.gsfm_ba_step_check.restype = C.c_int
+    lib.gsfm_ba_time_kernels.argtypes = [C.c_void_p, _DP, _DP, C.c_double, C.c_int32, _DP]; lib.gsfm_ba_time_kernels.restype = C.c_int
+    lib.gsfm_ba_problem_destroy.argtypes = [C.c_void_p]; lib.gsfm_ba_problem_destroy.restype = None

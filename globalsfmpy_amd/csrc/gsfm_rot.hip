@@ -20,6 +20,7 @@
 #include "trans_refine.hpp"
 #include "triangulate.hpp"
 #include "track_refine.hpp"
+#include "solver_ba.hpp"
 
 // =============================================================================================
 extern "C" {

@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include "triangulate_kernels.hpp"
 #include "loss_dev.hpp"
+#include "reproj_dev.hpp"
 
 namespace gsfm {
 
@@ -47,29 +48,12 @@ __device__ __forceinline__ void trr_pass(const TriArgs& a, const DevLossNode& le
     if (cam[15] == 0.0) continue;
     const double2 xy = a.obs_xy[tk.ob + k];
     const double v0 = X[0] - cam[9], v1 = X[1] - cam[10], v2 = X[2] - cam[11];
-    const double px = cam[0] * v0 + cam[1] * v1 + cam[2] * v2, py = cam[3] * v0 + cam[4] * v1 + cam[5] * v2, pz = cam[6] * v0 + cam[7] * v1 + cam[8] * v2;
-    const double ex = cam[12] * px / pz + cam[13] - xy.x, ey = cam[12] * py / pz + cam[14] - xy.y;
-    const double sq = ex * ex + ey * ey;
-    const Rho3 rho = loss_leaf_simple(leaf, sq);
-    const Corrector c = make_corrector(sq, rho);
-    const double fz = cam[12] / pz, ax = px / pz, ay = py / pz;
-    double J0[3], J1[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { J0[j] = fz * (cam[j] - ax * cam[6 + j]); J1[j] = fz * (cam[3 + j] - ay * cam[6 + j]); }
-    if (c.alpha_sq_norm != 0.0) {                      // Corrector::CorrectJacobian: J <- J - alpha / s r r^T J
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const double t = c.alpha_sq_norm * (ex * J0[j] + ey * J1[j]);
-        J0[j] -= ex * t; J1[j] -= ey * t;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { J0[j] *= c.sqrt_rho1; J1[j] *= c.sqrt_rho1; }
-    const double r0 = c.residual_scaling * ex, r1 = c.residual_scaling * ey;
+    double J0[3], J1[3], r0, r1, rho0;
+    reproj_corrected(cam, xy, v0, v1, v2, leaf, J0, J1, r0, r1, rho0);   // (reproj_dev.hpp: shared with the bundle adjustment)
     s[0] += J0[0] * J0[0] + J1[0] * J1[0]; s[1] += J0[0] * J0[1] + J1[0] * J1[1]; s[2] += J0[0] * J0[2] + J1[0] * J1[2];
     s[3] += J0[1] * J0[1] + J1[1] * J1[1]; s[4] += J0[1] * J0[2] + J1[1] * J1[2]; s[5] += J0[2] * J0[2] + J1[2] * J1[2];
     s[6] += J0[0] * r0 + J1[0] * r1; s[7] += J0[1] * r0 + J1[1] * r1; s[8] += J0[2] * r0 + J1[2] * r1;
-    s[9] += 0.5 * rho.r0;
+    s[9] += 0.5 * rho0;
   }
 #pragma unroll
   for (int k = 0; k < 10; ++k) S[k] = tri_group_allsum<G>(s[k]);

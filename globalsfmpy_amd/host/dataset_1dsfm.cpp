@@ -14,6 +14,7 @@
 #include "../../include/gsfm/view_graph.hpp"
 #include "../../include/gsfm_rot.h"
 #include "../../include/gsfm_tracks.h"
+#include "../../include/gsfm_ba.h"
 
 namespace gsfm {
 
@@ -261,6 +262,90 @@ EstimateStructureStats EstimateStructure(double min_angle_degrees, double max_er
   }
   stats.num_tracks = T;
   stats.num_estimated = (size_t)stats.counts[0];
+  return stats;
+}
+
+UnderconstrainedStats SetUnderconstrainedAsUnestimated(theia::Reconstruction* rec) {
+  UnderconstrainedStats stats;
+  if (!rec->tracks) return stats;
+  const auto& tracks = rec->tracks->tracks;
+  auto view_estimated = [&](theia::ViewId v) { return rec->views.count(v) && rec->orientation.count(v) && rec->position.count(v); };
+  auto track_estimated = [&](size_t t) { return t < rec->track_estimated.size() && rec->track_estimated[t] != 0; };
+  int views = -1, removed_tracks = -1;
+  while (views != 0 && removed_tracks != 0) {
+    ++stats.rounds;
+    // views with fewer than 3 estimated tracks (a track counts once per view, as a view's set of track ids does)
+    std::unordered_map<theia::ViewId, int> seen;
+    for (size_t t = 0; t < tracks.size(); ++t) {
+      if (!track_estimated(t)) continue;
+      std::vector<theia::ViewId> vs;
+      for (const auto& ob : tracks[t]) vs.push_back(ob.first);
+      std::sort(vs.begin(), vs.end());
+      vs.erase(std::unique(vs.begin(), vs.end()), vs.end());
+      for (theia::ViewId v : vs) ++seen[v];
+    }
+    std::vector<theia::ViewId> drop;
+    for (theia::ViewId v : rec->views)
+      if (view_estimated(v) && seen[v] < 3) drop.push_back(v);
+    for (theia::ViewId v : drop) { rec->orientation.erase(v); rec->position.erase(v); }
+    views = (int)drop.size();
+    // tracks with fewer than 2 estimated views
+    removed_tracks = 0;
+    for (size_t t = 0; t < tracks.size(); ++t) {
+      if (!track_estimated(t)) continue;
+      std::vector<theia::ViewId> vs;
+      for (const auto& ob : tracks[t]) if (view_estimated(ob.first)) vs.push_back(ob.first);
+      std::sort(vs.begin(), vs.end());
+      vs.erase(std::unique(vs.begin(), vs.end()), vs.end());
+      if (vs.size() < 2) { rec->track_estimated[t] = 0; ++removed_tracks; }
+    }
+    stats.views_removed += views; stats.tracks_removed += removed_tracks;
+  }
+  return stats;
+}
+
+BundleAdjustmentStats BundleAdjustCameraPositionsAndPoints(const std::string& loss_function, double loss_width, int max_num_iterations,
+                                                           theia::Reconstruction* rec) {
+  BundleAdjustmentStats stats;
+  stats.max_num_iterations = max_num_iterations;
+  gsfm_loss_node loss{};
+  if (loss_function == "TRIVIAL") loss.kind = GSFM_LOSS_TRIVIAL;
+  else if (loss_function == "HUBER") loss.kind = GSFM_LOSS_HUBER;
+  else if (loss_function == "SOFTLONE") loss.kind = GSFM_LOSS_SOFT_L1;
+  else throw std::runtime_error("BundleAdjustCameraPositionsAndPoints: no loss " + loss_function + " (TRIVIAL, HUBER, SOFTLONE)");
+  loss.p[0] = loss_width;
+  if (!rec->tracks || rec->tracks->tracks.empty()) return stats;
+  FlatTracks f;
+  FlattenTracks(*rec, &f);
+  const size_t T = f.track_ptr.size() - 1, N = f.views.size();
+  std::vector<uint8_t> point_estimated(T, 0);
+  std::vector<double> points(3 * T, 0.0);
+  for (size_t t = 0; t < T && t < rec->track_estimated.size(); ++t) {
+    point_estimated[t] = rec->track_estimated[t];
+    for (int k = 0; k < 3; ++k) points[3 * t + k] = rec->track_point[t][k];
+  }
+  gsfm_ba_problem* problem = nullptr;
+  gsfm_status st = gsfm_ba_problem_create((uint32_t)N, f.rot_aa.data(), f.intrinsics.data(), f.cam_estimated.data(), T, f.track_ptr.data(), f.obs_cam.data(),
+                                          f.obs_xy.data(), point_estimated.data(), &problem);
+  if (st != GSFM_OK) throw std::runtime_error(std::string("BundleAdjustCameraPositionsAndPoints: ") + gsfm_last_error());
+  gsfm_ba_options o;
+  gsfm_ba_options_default(&o);
+  o.max_num_iterations = max_num_iterations;
+  gsfm_ba_summary s;
+  st = gsfm_ba_set_loss(problem, &loss, 1);
+  if (st == GSFM_OK) st = gsfm_ba_solve(problem, f.cam_pos.data(), points.data(), &o, &s);
+  gsfm_ba_problem_destroy(problem);
+  if (st != GSFM_OK) throw std::runtime_error(std::string("BundleAdjustCameraPositionsAndPoints: ") + gsfm_last_error());
+  for (size_t c = 0; c < N; ++c)
+    if (f.cam_estimated[c]) rec->position[f.views[c]] = Eigen::Vector3d(f.cam_pos[3 * c], f.cam_pos[3 * c + 1], f.cam_pos[3 * c + 2]);
+  for (size_t t = 0; t < T; ++t)
+    if (point_estimated[t]) rec->track_point[t] = Eigen::Vector3d(points[3 * t], points[3 * t + 1], points[3 * t + 2]);
+  stats.ran = true;
+  stats.usable = s.termination != GSFM_TERM_FAILURE;
+  stats.termination = s.termination; stats.num_iterations = s.num_iterations; stats.num_successful_steps = s.num_successful_steps;
+  stats.num_unsuccessful_steps = s.num_unsuccessful_steps; stats.num_cg_iterations = s.num_cg_iterations;
+  stats.num_observations = s.num_observations_used; stats.num_cameras = s.num_active_cameras; stats.num_points = s.num_active_points;
+  stats.initial_cost = s.initial_cost; stats.final_cost = s.final_cost; stats.t_total_ms = s.t_total_ms;
   return stats;
 }
 

@@ -117,6 +117,7 @@ struct ReconstructionEstimatorOptions {
   bool bundle_adjust_tracks = true;                          // :284; honoured by EstimateStructure(refine=True) only: the default call does not refine tracks
   std::string bundle_adjustment_loss_function_type = "TRIVIAL";   // :248 (LossFunctionType::TRIVIAL); the YAML's bundle_adjustment_robust_loss_function
   double bundle_adjustment_robust_loss_width = 10.0;         // :251
+  int min_cameras_for_iterative_solver = 1000;               // :258; from this many views on BundleAdjustCameraPositionsAndPoints takes 1.5 x the iterations
 };
 struct ReconstructionBuilderOptions {
   int num_threads = 1;
@@ -248,6 +249,18 @@ class GlobalReconstructionEstimator {
     structure_refine_asked_ = refine;
     return structure_;
   }
+  // Theia's BundleAdjustCameraPositionsAndPoints: positions and points move, orientations and intrinsics are held; the loss of
+  // bundle_adjustment_loss_function_type / _width; 100 iterations, x 1.5 from min_cameras_for_iterative_solver views on (Theia's
+  // SetBundleAdjustmentOptions).  Returns the reference's bool: the solution is usable.
+  bool BundleAdjustCameraPositionsAndPoints() {
+    if (!reconstruction_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
+    int iterations = 100;
+    if (reconstruction_->NumViews() >= options_.min_cameras_for_iterative_solver) iterations = (int)(iterations * 1.5);
+    bundle_ = gsfm::BundleAdjustCameraPositionsAndPoints(options_.bundle_adjustment_loss_function_type, options_.bundle_adjustment_robust_loss_width,
+                                                         iterations, reconstruction_);
+    return bundle_.usable;
+  }
+  gsfm::BundleAdjustmentStats bundle_;
   bool structure_refine_asked_ = false;
   gsfm::EstimateStructureStats structure_;
   ReconstructionEstimatorOptions options_;
@@ -285,6 +298,16 @@ py::dict structure_dict(const gsfm::EstimateStructureStats& st, bool bundle_adju
   return d;
 }
 
+py::dict bundle_dict(const gsfm::BundleAdjustmentStats& st) {
+  py::dict d;
+  d["ran"] = st.ran; d["usable"] = st.usable; d["termination"] = st.termination; d["num_iterations"] = st.num_iterations;
+  d["num_successful_steps"] = st.num_successful_steps; d["num_unsuccessful_steps"] = st.num_unsuccessful_steps;
+  d["num_cg_iterations"] = st.num_cg_iterations; d["max_num_iterations"] = st.max_num_iterations;
+  d["num_observations"] = st.num_observations; d["num_cameras"] = st.num_cameras; d["num_points"] = st.num_points;
+  d["initial_cost"] = st.initial_cost; d["final_cost"] = st.final_cost; d["t_total_ms"] = st.t_total_ms;
+  return d;
+}
+
 py::dict pos_summary_dict(const gsfm_pos_summary& s) {
   py::dict d;
   d["termination"] = s.termination; d["num_iterations"] = s.num_iterations;
@@ -313,6 +336,7 @@ void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions
   get("bundle_adjust_tracks", options.reconstruction_estimator_options.bundle_adjust_tracks);
   get("bundle_adjustment_robust_loss_function", options.reconstruction_estimator_options.bundle_adjustment_loss_function_type);
   get("bundle_adjustment_robust_loss_width", options.reconstruction_estimator_options.bundle_adjustment_robust_loss_width);
+  get("min_cameras_for_iterative_solver", options.reconstruction_estimator_options.min_cameras_for_iterative_solver);
 }
 
 }  // namespace
@@ -400,7 +424,8 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def_readwrite("triangulation_max_reprojection_error_in_pixels", &ReconstructionEstimatorOptions::triangulation_max_reprojection_error_in_pixels)
       .def_readwrite("bundle_adjust_tracks", &ReconstructionEstimatorOptions::bundle_adjust_tracks)
       .def_readwrite("bundle_adjustment_loss_function_type", &ReconstructionEstimatorOptions::bundle_adjustment_loss_function_type)
-      .def_readwrite("bundle_adjustment_robust_loss_width", &ReconstructionEstimatorOptions::bundle_adjustment_robust_loss_width);
+      .def_readwrite("bundle_adjustment_robust_loss_width", &ReconstructionEstimatorOptions::bundle_adjustment_robust_loss_width)
+      .def_readwrite("min_cameras_for_iterative_solver", &ReconstructionEstimatorOptions::min_cameras_for_iterative_solver);
   py::class_<ReconstructionBuilderOptions>(m, "ReconstructionBuilderOptions")
       .def(py::init<>())
       .def_readwrite("num_threads", &ReconstructionBuilderOptions::num_threads)
@@ -445,6 +470,13 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
         d["views"] = arr(f.views, 1); d["rot_aa"] = arr(f.rot_aa, 3); d["cam_pos"] = arr(f.cam_pos, 3); d["intrinsics"] = arr(f.intrinsics, 3);
         d["cam_estimated"] = arr(f.cam_estimated, 1); d["track_ptr"] = arr(f.track_ptr, 1); d["obs_cam"] = arr(f.obs_cam, 1); d["obs_xy"] = arr(f.obs_xy, 2);
         return d;
+      })
+      // what EstimateStructure stores per track, settable (a reconstruction assembled by hand)
+      .def("SetTrack", [](Reconstruction& r, size_t t, const Eigen::Vector3d& point, bool estimated) {
+        if (t >= (size_t)r.NumTracks()) throw py::index_error("no such track");
+        r.track_point.resize((size_t)r.NumTracks(), Eigen::Vector3d(0, 0, 0));
+        r.track_estimated.resize((size_t)r.NumTracks(), 0);
+        r.track_point[t] = point; r.track_estimated[t] = estimated;
       })
       .def("EstimatedOrientations", [](const Reconstruction& r) { return r.orientation; })
       .def("EstimatedPositions", [](const Reconstruction& r) { return r.position; })
@@ -519,6 +551,9 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
         { py::gil_scoped_release release; st = e.EstimateStructure(refine); }
         return structure_dict(st, e.options_.bundle_adjust_tracks, refine);
       }, py::arg("refine") = false)
+      .def("BundleAdjustCameraPositionsAndPoints", &GlobalReconstructionEstimator::BundleAdjustCameraPositionsAndPoints,
+           py::call_guard<py::gil_scoped_release>())
+      .def("LastBundleAdjustmentSummary", [](const GlobalReconstructionEstimator& e) { return bundle_dict(e.bundle_); })
       .def("LastStructureSummary", [](const GlobalReconstructionEstimator& e) { return structure_dict(e.structure_, e.options_.bundle_adjust_tracks, e.structure_refine_asked_); })
       .def("LastSummary", [](const GlobalReconstructionEstimator& e) { return summary_dict(e.summary_); })
       .def("LastError", [](const GlobalReconstructionEstimator& e) { return e.error_; });
@@ -637,6 +672,13 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
   });
   // bind :631 / Theia io/write_ply_file.cc:74-123: the estimated tracks' points, then the positions of the estimated views as green
   // vertices (gsfm::WritePlyFile).  Without an estimated track the file holds the views alone.
+  // Theia's SetUnderconstrainedAsUnestimated; returns the counters (the reference returns None)
+  m.def("SetUnderconstrainedAsUnestimated", [](Reconstruction* rec) {
+    const gsfm::UnderconstrainedStats st = gsfm::SetUnderconstrainedAsUnestimated(rec);
+    py::dict d;
+    d["rounds"] = st.rounds; d["views_removed"] = st.views_removed; d["tracks_removed"] = st.tracks_removed;
+    return d;
+  });
   m.def("WritePlyFile", [](const std::string& ply_file, const Reconstruction& rec, int min_num_observations_per_point) {
     if (ply_file.empty()) throw std::invalid_argument("WritePlyFile: empty file name");
     return gsfm::WritePlyFile(ply_file, rec, min_num_observations_per_point);

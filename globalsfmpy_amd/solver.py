@@ -594,3 +594,152 @@ class PositionProblem(ProblemBase):
 
     def set_edge_weights(self, w):
         raise NotImplementedError("position residuals have weight 1 (the reference's BASELINE error)")
+
+
+class BundleProblem(object):
+    """Bundle adjustment of camera positions and points with fixed orientations (include/gsfm_ba.h): Theia's
+    BundleAdjustCameraPositionsAndPoints on the device, the points eliminated and the reduced camera system solved by PCG.
+    rot_aa: N x 3, intrinsics: N x 3 (f u v); track_ptr / obs_cam / obs_xy: the track CSR of triangulate_tracks; cam_estimated (N) and
+    point_estimated (T): flags or None (all estimated).  A new problem has Ceres' NULL loss."""
+
+    def __init__(self, rot_aa, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated=None, point_estimated=None):
+        lib = _abi.load_library()
+        rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(-1, 3)
+        K = np.ascontiguousarray(intrinsics, dtype=np.float64).reshape(-1, 3)
+        tp = np.ascontiguousarray(track_ptr, dtype=np.uint64).reshape(-1)
+        oc = np.ascontiguousarray(obs_cam, dtype=np.uint32).reshape(-1)
+        xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
+        n = rot.shape[0]
+        if K.shape[0] != n:
+            raise ValueError("rot_aa and intrinsics must describe the same cameras")
+        if tp.shape[0] < 1 or xy.shape[0] != oc.shape[0]:
+            raise ValueError("track_ptr needs n_tracks + 1 entries, and obs_cam and obs_xy one row per observation")
+        T = tp.shape[0] - 1
+        if int(tp.max()) > oc.shape[0]:
+            raise ValueError("track_ptr points past the end of the observations")
+
+        def flags(a, count, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8).reshape(-1)
+            if a.shape[0] != count:
+                raise ValueError("%s needs one flag per entry" % what)
+            return a
+        ce, pe = flags(cam_estimated, n, "cam_estimated"), flags(point_estimated, T, "point_estimated")
+        u8p = C.POINTER(C.c_uint8)
+        h = C.c_void_p()
+        st = lib.gsfm_ba_problem_create(n, _dp(rot), _dp(K), None if ce is None else ce.ctypes.data_as(u8p), T,
+                                        tp.ctypes.data_as(C.POINTER(C.c_uint64)), _u32p(oc), _dp(xy),
+                                        None if pe is None else pe.ctypes.data_as(u8p), C.byref(h))
+        _raise_if_failed(lib, "gsfm_ba_problem_create", st)
+        self._lib, self._h = lib, h
+        self.n_cams, self.n_tracks, self.n_obs = n, T, int(oc.shape[0])
+
+    def _check(self, st, what):
+        if st != 0:
+            raise SolverError("%s failed with status %d: %s" % (what, st, self._lib.gsfm_last_error().decode("utf-8", "replace")))
+
+    def close(self):
+        if self._h is not None:
+            self._lib.gsfm_ba_problem_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_loss(self, loss):
+        """loss: None (Ceres' NULL loss), a list of (kind, p0, p1, p2) nodes or an object with .native_program(); one Trivial / Huber /
+        SoftLOne / Tukey / GemanMcClure leaf."""
+        if loss is None:
+            nodes = []
+        elif isinstance(loss, (list, tuple)):
+            nodes = list(loss)
+        elif hasattr(loss, "native_program") and loss.native_program() is not None:
+            nodes = loss.native_program()
+        else:
+            raise TypeError("the bundle adjustment needs a loss with a native descriptor, got %r" % (loss,))
+        arr, n = _abi.make_program(nodes)
+        self._check(self._lib.gsfm_ba_set_loss(self._h, arr, n), "set_loss")
+
+    def default_options(self):
+        o = _abi.BaOptions()
+        self._lib.gsfm_ba_options_default(C.byref(o))
+        return o
+
+    def _options(self, kw):
+        o = self.default_options()
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise TypeError("unknown solver option %r" % k)
+            setattr(o, k, v)
+        return o
+
+    def _point(self, cam_pos, points):
+        return (np.array(cam_pos, dtype=np.float64, order="C").reshape(self.n_cams, 3),
+                np.array(points, dtype=np.float64, order="C").reshape(self.n_tracks, 3))
+
+    def solve(self, cam_pos, points, **options):
+        """Returns (camera positions N x 3, points T x 3, summary dict); inactive and unestimated rows are returned as given."""
+        c, p = self._point(cam_pos, points)
+        o, s = self._options(options), _abi.BaSummary()
+        self._check(self._lib.gsfm_ba_solve(self._h, _dp(c), _dp(p), C.byref(o), C.byref(s)), "solve")
+        return c, p, s.as_dict()
+
+    def residuals(self, cam_pos, points):
+        """(r: n_obs x 2, rho: n_obs); zeros for an unused observation"""
+        c, p = self._point(cam_pos, points)
+        r, rho = np.zeros((self.n_obs, 2)), np.zeros(self.n_obs)
+        self._check(self._lib.gsfm_ba_residuals(self._h, _dp(c), _dp(p), _dp(r), _dp(rho)), "residuals")
+        return r, rho
+
+    def linearize(self, cam_pos, points):
+        """dict(cost, grad_cam N x 3, grad_point T x 3, diag_cam N x 3 x 3, diag_point T x 3 x 3)"""
+        c, p = self._point(cam_pos, points)
+        cost = np.zeros(1)
+        gc, gp = np.zeros((self.n_cams, 3)), np.zeros((self.n_tracks, 3))
+        dc, dp = np.zeros((self.n_cams, 3, 3)), np.zeros((self.n_tracks, 3, 3))
+        self._check(self._lib.gsfm_ba_linearize(self._h, _dp(c), _dp(p), _dp(cost), _dp(gc), _dp(gp), _dp(dc), _dp(dp)), "linearize")
+        return {"cost": float(cost[0]), "grad_cam": gc, "grad_point": gp, "diag_cam": dc, "diag_point": dp}
+
+    def schur_matvec(self, v, radius=1e4, **options):
+        """y = Sc v (N x 3) for the last linearize / step_check, damped at `radius`"""
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(self.n_cams, 3)
+        y = np.zeros((self.n_cams, 3))
+        o = self._options(options)
+        self._check(self._lib.gsfm_ba_schur_matvec(self._h, _dp(v), float(radius), C.byref(o), _dp(y)), "schur_matvec")
+        return y
+
+    def step_check(self, cam_pos, points, radius=1e4, **options):
+        """gsfm_ba_step_check: dict(rhs, y_cam, y_point, delta_cam, delta_point, model_cost_change, dg, dld, cg_rel, cg_iterations, stalled)"""
+        c, p = self._point(cam_pos, points)
+        o = self._options(options)
+        N, T = self.n_cams, self.n_tracks
+        rhs, yc, yp, dc, dp = np.zeros((N, 3)), np.zeros((N, 3)), np.zeros((T, 3)), np.zeros((N, 3)), np.zeros((T, 3))
+        scal, info = np.zeros(4), np.zeros(2, dtype=np.int32)
+        st = self._lib.gsfm_ba_step_check(self._h, _dp(c), _dp(p), float(radius), C.byref(o), _dp(rhs), _dp(yc), _dp(yp), _dp(dc), _dp(dp), _dp(scal),
+                                          info.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._check(st, "step_check")
+        return {"rhs": rhs, "y_cam": yc, "y_point": yp, "delta_cam": dc, "delta_point": dp, "model_cost_change": scal[0], "dg": scal[1],
+                "dld": scal[2], "cg_rel": scal[3], "cg_iterations": int(info[0]), "stalled": bool(info[1])}
+
+
+    def time_kernels(self, cam_pos, points, radius=1e4, reps=10):
+        """mean device microseconds of the kernels of one linearisation and one Schur product (gsfm_ba_time_kernels)"""
+        c, p = self._point(cam_pos, points)
+        out = np.zeros(6)
+        self._check(self._lib.gsfm_ba_time_kernels(self._h, _dp(c), _dp(p), float(radius), int(reps), _dp(out)), "time_kernels")
+        return dict(zip(("lin_tracks", "lin_cameras", "cost", "point_pass", "camera_pass", "preconditioner"), out))
+
+
+def bundle_adjust_positions_and_points(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, points, cam_estimated=None, point_estimated=None,
+                                       loss=None, **options):
+    """One call: BundleProblem(...).set_loss(loss).solve(cam_pos, points, **options).  Returns (cam_pos, points, summary dict)."""
+    prob = BundleProblem(rot_aa, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated)
+    try:
+        prob.set_loss(loss)
+        return prob.solve(cam_pos, points, **options)
+    finally:
+        prob.close()

@@ -187,6 +187,29 @@ EstimateStructureStats EstimateStructure(double min_triangulation_angle_degrees,
 // ascending track index where Theia walks a hash set), then the estimated views' positions in green.  A view without a position is
 // written at the origin (a rotation-only reconstruction).  Returns false when the file cannot be written.
 bool WritePlyFile(const std::string& ply_file, const theia::Reconstruction& reconstruction, int min_num_observations_per_point);
+
+// Theia's SetUnderconstrainedAsUnestimated (sfm/set_underconstrained_as_unestimated.cc), the step before the bundle adjustment: estimated
+// views that see fewer than 3 estimated tracks become unestimated (their orientation and position leave the reconstruction), then
+// estimated tracks seen by fewer than 2 estimated views become unestimated; both passes alternate until either changes nothing.  A view is
+// estimated when the reconstruction holds an orientation and a position for it (FlattenTracks' rule).  Host code.
+struct UnderconstrainedStats {
+  int rounds = 0, views_removed = 0, tracks_removed = 0;
+};
+UnderconstrainedStats SetUnderconstrainedAsUnestimated(theia::Reconstruction* reconstruction);
+
+// GlobalReconstructionEstimator::BundleAdjustCameraPositionsAndPoints (src/GSfM_global_reconstruction_estimator.cpp -> Theia's
+// BundleAdjuster with fixed orientations and intrinsics) on the device: gsfm_ba_solve under the definition of include/gsfm_ba.h, over
+// FlattenTracks' arrays plus track_estimated / track_point.  Writes the positions of the estimated views and the points of the estimated
+// tracks back.  usable: Ceres' IsSolutionUsable (every termination but FAILURE).  The loss as BundleAdjustmentOptions names it (TRIVIAL,
+// HUBER, SOFTLONE; anything else throws std::runtime_error).  A reconstruction without tracks is left alone (usable, ran = false).
+struct BundleAdjustmentStats {
+  bool ran = false, usable = true;
+  int termination = -1, num_iterations = 0, num_successful_steps = 0, num_unsuccessful_steps = 0, num_cg_iterations = 0, max_num_iterations = 0;
+  uint64_t num_observations = 0, num_cameras = 0, num_points = 0;
+  double initial_cost = 0.0, final_cost = 0.0, t_total_ms = 0.0;
+};
+BundleAdjustmentStats BundleAdjustCameraPositionsAndPoints(const std::string& loss_function, double loss_width, int max_num_iterations,
+                                                           theia::Reconstruction* reconstruction);
 #endif
 
 // two_views.txt of scripts/read_colmap_database.py:52-133 as AddColmapMatchesToReconstructionBuilder reads it

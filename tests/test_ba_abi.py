@@ -1,0 +1,91 @@
+"""include/gsfm_ba.h: every declared entry point is exported, the ctypes mirrors follow the header's structs field for field, the defaults
+are Theia's BundleAdjustmentOptions / Ceres 1.14's, the header is C99, and the argument checks of gsfm_ba_problem_create run before any
+device call (on a machine without a device a bad argument is reported as such, not as the missing device)."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import have_gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HDR = open(os.path.join(ROOT, "include", "gsfm_ba.h")).read()
+
+
+def test_library_exports_every_declared_entry_point():
+    from globalsfmpy_amd import _abi
+    lib = _abi.load_library()
+    txt = re.sub(r"/\*.*?\*/", "", HDR, flags=re.S)
+    names = sorted(set(re.findall(r"\b(gsfm_ba_[a-z0-9_]+)\s*\(", txt)))
+    assert names == ["gsfm_ba_abi_version", "gsfm_ba_linearize", "gsfm_ba_options_default", "gsfm_ba_problem_create", "gsfm_ba_problem_destroy",
+                     "gsfm_ba_residuals", "gsfm_ba_schur_matvec", "gsfm_ba_set_loss", "gsfm_ba_solve", "gsfm_ba_step_check", "gsfm_ba_time_kernels"]
+    for n in names:
+        assert hasattr(lib, n), "libgsfm_rot.so does not export %s" % n
+    assert lib.gsfm_ba_abi_version() == 1 and "#define GSFM_BA_ABI_VERSION 1" in HDR
+
+
+def _fields(struct_name, first):
+    body = HDR[HDR.index("typedef struct {\n  int32_t %s;" % first):HDR.index("} %s;" % struct_name)]
+    return re.findall(r"^\s+(?:int32_t|uint64_t|double)\s+(\w+);", body, flags=re.M)
+
+
+def test_struct_mirrors_and_defaults():
+    from globalsfmpy_amd import _abi
+    lib = _abi.load_library()
+    assert _fields("gsfm_ba_options", "max_num_iterations") == [n for n, _ in _abi.BaOptions._fields_]
+    assert _fields("gsfm_ba_summary", "termination") == [n for n, _ in _abi.BaSummary._fields_]
+    assert C.sizeof(_abi.BaOptions) == 4 * 8 + 8 * 10 and C.sizeof(_abi.BaSummary) == 4 * 10 + 8 * 9
+    o = _abi.BaOptions()
+    lib.gsfm_ba_options_default(C.byref(o))
+    assert (o.max_num_iterations, o.function_tolerance, o.gradient_tolerance, o.parameter_tolerance) == (100, 1e-6, 1e-10, 1e-8)
+    assert (o.initial_trust_region_radius, o.max_trust_region_radius, o.min_trust_region_radius, o.min_relative_decrease) == (1e4, 1e12, 1e-32, 1e-3)
+    assert (o.min_lm_diagonal, o.max_lm_diagonal, o.jacobi_scaling, o.cg_relative_tolerance, o.remove_gauge, o.verbose) == (1e-6, 1e32, 1, 1e-12, 1, 0)
+    p = _abi.PosOptions()
+    lib.gsfm_pos_options_default(C.byref(p))
+    assert (o.max_cg_iterations, o.cg_check_interval, o.cg_stall_iterations) == (p.max_cg_iterations, p.cg_check_interval, p.cg_stall_iterations)
+    f = lib.gsfm_ba_step_check
+    assert f.restype is C.c_int and len(f.argtypes) == 12 and f.argtypes[3] is C.c_double and f.argtypes[4] is C.POINTER(_abi.BaOptions)
+    assert len(lib.gsfm_ba_problem_create.argtypes) == 10 and len(lib.gsfm_ba_linearize.argtypes) == 8
+
+
+def test_header_is_pedantic_c99(tmp_path):
+    if shutil.which("gcc") is None:
+        pytest.skip("no gcc")
+    src = tmp_path / "use_ba.c"
+    src.write_text('#include "gsfm_ba.h"\nint main(void) { gsfm_ba_options o; gsfm_ba_options_default(&o); return o.max_num_iterations == 100 ? 0 : 1; }\n')
+    exe = str(tmp_path / "use_ba")
+    lib_dir = os.path.join(ROOT, "globalsfmpy_amd")
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-L" + lib_dir,
+                        "-lgsfm_rot", "-Wl,-rpath," + lib_dir, "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert subprocess.run([exe]).returncode == 0
+
+
+def test_argument_checks_run_before_any_device_call():
+    """With or without a device: a bad argument is GSFM_ERR_INVALID_ARG (status 1), never the device's error."""
+    from globalsfmpy_amd.solver import BundleProblem, SolverError
+    rot, K = np.zeros((3, 3)), np.tile([1000.0, 500.0, 400.0], (3, 1))
+    xy = np.zeros((4, 2))
+    cases = {"track_ptr[0]": (np.array([1, 2, 4], np.uint64), np.array([0, 1, 2, 0], np.uint32)),
+             "decreasing": (np.array([0, 3, 2, 4], np.uint64), np.array([0, 1, 2, 0], np.uint32)),
+             "camera index": (np.array([0, 2, 4], np.uint64), np.array([0, 1, 3, 0], np.uint32))}
+    for what, (tp, oc) in cases.items():
+        with pytest.raises(SolverError, match="status 1"):
+            BundleProblem(rot, K, tp, oc, xy)
+    from globalsfmpy_amd import _abi
+    lib = _abi.load_library()
+    h = C.c_void_p()
+    assert lib.gsfm_ba_problem_create(3, None, None, None, 0, None, None, None, None, C.byref(h)) == 1
+    assert lib.gsfm_ba_problem_create(0, None, None, None, 0, None, None, None, None, None) == 1
+    assert lib.gsfm_ba_set_loss(None, None, 0) == 1 and lib.gsfm_ba_solve(None, None, None, None, None) == 1
+
+
+@pytest.mark.skipif(have_gpu(), reason="CPU-only behaviour")
+def test_fails_loudly_without_a_gpu():
+    from globalsfmpy_amd.solver import BundleProblem, SolverError
+    with pytest.raises(SolverError, match="no HIP device"):
+        BundleProblem(np.zeros((2, 3)), np.ones((2, 3)), np.array([0, 2], np.uint64), np.array([0, 1], np.uint32), np.zeros((2, 2)))
