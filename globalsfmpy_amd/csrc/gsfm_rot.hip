@@ -21,6 +21,7 @@
 #include "triangulate.hpp"
 #include "track_refine.hpp"
 #include "solver_ba.hpp"
+#include "solver_ba6.hpp"
 
 // =============================================================================================
 extern "C" {

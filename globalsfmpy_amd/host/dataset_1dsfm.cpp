@@ -15,6 +15,7 @@
 #include "../../include/gsfm_rot.h"
 #include "../../include/gsfm_tracks.h"
 #include "../../include/gsfm_ba.h"
+#include "../../include/gsfm_ba6.h"
 
 namespace gsfm {
 
@@ -338,6 +339,53 @@ BundleAdjustmentStats BundleAdjustCameraPositionsAndPoints(const std::string& lo
   if (st != GSFM_OK) throw std::runtime_error(std::string("BundleAdjustCameraPositionsAndPoints: ") + gsfm_last_error());
   for (size_t c = 0; c < N; ++c)
     if (f.cam_estimated[c]) rec->position[f.views[c]] = Eigen::Vector3d(f.cam_pos[3 * c], f.cam_pos[3 * c + 1], f.cam_pos[3 * c + 2]);
+  for (size_t t = 0; t < T; ++t)
+    if (point_estimated[t]) rec->track_point[t] = Eigen::Vector3d(points[3 * t], points[3 * t + 1], points[3 * t + 2]);
+  stats.ran = true;
+  stats.usable = s.termination != GSFM_TERM_FAILURE;
+  stats.termination = s.termination; stats.num_iterations = s.num_iterations; stats.num_successful_steps = s.num_successful_steps;
+  stats.num_unsuccessful_steps = s.num_unsuccessful_steps; stats.num_cg_iterations = s.num_cg_iterations;
+  stats.num_observations = s.num_observations_used; stats.num_cameras = s.num_active_cameras; stats.num_points = s.num_active_points;
+  stats.initial_cost = s.initial_cost; stats.final_cost = s.final_cost; stats.t_total_ms = s.t_total_ms;
+  return stats;
+}
+
+BundleAdjustmentStats BundleAdjustment(const std::string& loss_function, double loss_width, int max_num_iterations, theia::Reconstruction* rec) {
+  BundleAdjustmentStats stats;
+  stats.max_num_iterations = max_num_iterations;
+  gsfm_loss_node loss{};
+  if (loss_function == "TRIVIAL") loss.kind = GSFM_LOSS_TRIVIAL;
+  else if (loss_function == "HUBER") loss.kind = GSFM_LOSS_HUBER;
+  else if (loss_function == "SOFTLONE") loss.kind = GSFM_LOSS_SOFT_L1;
+  else throw std::runtime_error("BundleAdjustment: no loss " + loss_function + " (TRIVIAL, HUBER, SOFTLONE)");
+  loss.p[0] = loss_width;
+  if (!rec->tracks || rec->tracks->tracks.empty()) return stats;
+  FlatTracks f;
+  FlattenTracks(*rec, &f);
+  const size_t T = f.track_ptr.size() - 1, N = f.views.size();
+  std::vector<uint8_t> point_estimated(T, 0);
+  std::vector<double> points(3 * T, 0.0);
+  for (size_t t = 0; t < T && t < rec->track_estimated.size(); ++t) {
+    point_estimated[t] = rec->track_estimated[t];
+    for (int k = 0; k < 3; ++k) points[3 * t + k] = rec->track_point[t][k];
+  }
+  gsfm_ba6_problem* problem = nullptr;
+  gsfm_status st = gsfm_ba6_problem_create((uint32_t)N, f.intrinsics.data(), f.cam_estimated.data(), T, f.track_ptr.data(), f.obs_cam.data(), f.obs_xy.data(),
+                                           point_estimated.data(), &problem);
+  if (st != GSFM_OK) throw std::runtime_error(std::string("BundleAdjustment: ") + gsfm_last_error());
+  gsfm_ba_options o;
+  gsfm_ba6_options_default(&o);
+  o.max_num_iterations = max_num_iterations;
+  gsfm_ba_summary s;
+  st = gsfm_ba6_set_loss(problem, &loss, 1);
+  if (st == GSFM_OK) st = gsfm_ba6_solve(problem, f.rot_aa.data(), f.cam_pos.data(), points.data(), &o, &s);
+  gsfm_ba6_problem_destroy(problem);
+  if (st != GSFM_OK) throw std::runtime_error(std::string("BundleAdjustment: ") + gsfm_last_error());
+  for (size_t c = 0; c < N; ++c)
+    if (f.cam_estimated[c]) {
+      rec->orientation[f.views[c]] = Eigen::Vector3d(f.rot_aa[3 * c], f.rot_aa[3 * c + 1], f.rot_aa[3 * c + 2]);
+      rec->position[f.views[c]] = Eigen::Vector3d(f.cam_pos[3 * c], f.cam_pos[3 * c + 1], f.cam_pos[3 * c + 2]);
+    }
   for (size_t t = 0; t < T; ++t)
     if (point_estimated[t]) rec->track_point[t] = Eigen::Vector3d(points[3 * t], points[3 * t + 1], points[3 * t + 2]);
   stats.ran = true;

@@ -260,7 +260,17 @@ class GlobalReconstructionEstimator {
                                                          iterations, reconstruction_);
     return bundle_.usable;
   }
-  gsfm::BundleAdjustmentStats bundle_;
+  // Theia's BundleAdjustment (the solve of BundleAdjustmentAndRemoveOutlierPoints; SetOutlierTracksToUnestimated is not part of it): all
+  // estimated views and tracks, orientations, positions and points move, intrinsics are held; loss and iteration rule as above.  The new
+  // orientations and positions are written back to the reconstruction.
+  bool BundleAdjustment() {
+    if (!reconstruction_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
+    int iterations = 100;
+    if (reconstruction_->NumViews() >= options_.min_cameras_for_iterative_solver) iterations = (int)(iterations * 1.5);
+    bundle_ = gsfm::BundleAdjustment(options_.bundle_adjustment_loss_function_type, options_.bundle_adjustment_robust_loss_width, iterations, reconstruction_);
+    return bundle_.usable;
+  }
+  gsfm::BundleAdjustmentStats bundle_;   // of the last bundle adjustment, either kind
   bool structure_refine_asked_ = false;
   gsfm::EstimateStructureStats structure_;
   ReconstructionEstimatorOptions options_;
@@ -553,6 +563,7 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       }, py::arg("refine") = false)
       .def("BundleAdjustCameraPositionsAndPoints", &GlobalReconstructionEstimator::BundleAdjustCameraPositionsAndPoints,
            py::call_guard<py::gil_scoped_release>())
+      .def("BundleAdjustment", &GlobalReconstructionEstimator::BundleAdjustment, py::call_guard<py::gil_scoped_release>())
       .def("LastBundleAdjustmentSummary", [](const GlobalReconstructionEstimator& e) { return bundle_dict(e.bundle_); })
       .def("LastStructureSummary", [](const GlobalReconstructionEstimator& e) { return structure_dict(e.structure_, e.options_.bundle_adjust_tracks, e.structure_refine_asked_); })
       .def("LastSummary", [](const GlobalReconstructionEstimator& e) { return summary_dict(e.summary_); })

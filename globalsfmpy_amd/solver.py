@@ -596,25 +596,28 @@ class PositionProblem(ProblemBase):
         raise NotImplementedError("position residuals have weight 1 (the reference's BASELINE error)")
 
 
-class BundleProblem(object):
-    """Bundle adjustment of camera positions and points with fixed orientations (include/gsfm_ba.h): Theia's
-    BundleAdjustCameraPositionsAndPoints on the device, the points eliminated and the reduced camera system solved by PCG.
-    rot_aa: N x 3, intrinsics: N x 3 (f u v); track_ptr / obs_cam / obs_xy: the track CSR of triangulate_tracks; cam_estimated (N) and
-    point_estimated (T): flags or None (all estimated).  A new problem has Ceres' NULL loss."""
+class _BundleProblemBase(object):
+    """What BundleProblem and FullBundleProblem share: the handle, the loss, the options, the argument arrays.  A subclass sets _PREFIX (the
+    C prefix of its entry points), creates the problem in __init__ and ends it with self._adopt(lib, handle, n_cams, n_tracks, n_obs)."""
+    _PREFIX = None
+    _h = None
 
-    def __init__(self, rot_aa, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated=None, point_estimated=None):
-        lib = _abi.load_library()
-        rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(-1, 3)
+    def _adopt(self, lib, handle, n_cams, n_tracks, n_obs):
+        self._lib, self._h = lib, handle
+        self.n_cams, self.n_tracks, self.n_obs = n_cams, n_tracks, n_obs
+
+    def _fn(self, name):
+        return getattr(self._lib, self._PREFIX + name)
+
+    @staticmethod
+    def _track_arrays(intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated):
+        """(K, track_ptr, obs_cam, obs_xy, cam flags or None, point flags or None) as contiguous arrays, shapes checked"""
         K = np.ascontiguousarray(intrinsics, dtype=np.float64).reshape(-1, 3)
         tp = np.ascontiguousarray(track_ptr, dtype=np.uint64).reshape(-1)
         oc = np.ascontiguousarray(obs_cam, dtype=np.uint32).reshape(-1)
         xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
-        n = rot.shape[0]
-        if K.shape[0] != n:
-            raise ValueError("rot_aa and intrinsics must describe the same cameras")
         if tp.shape[0] < 1 or xy.shape[0] != oc.shape[0]:
             raise ValueError("track_ptr needs n_tracks + 1 entries, and obs_cam and obs_xy one row per observation")
-        T = tp.shape[0] - 1
         if int(tp.max()) > oc.shape[0]:
             raise ValueError("track_ptr points past the end of the observations")
 
@@ -625,15 +628,7 @@ class BundleProblem(object):
             if a.shape[0] != count:
                 raise ValueError("%s needs one flag per entry" % what)
             return a
-        ce, pe = flags(cam_estimated, n, "cam_estimated"), flags(point_estimated, T, "point_estimated")
-        u8p = C.POINTER(C.c_uint8)
-        h = C.c_void_p()
-        st = lib.gsfm_ba_problem_create(n, _dp(rot), _dp(K), None if ce is None else ce.ctypes.data_as(u8p), T,
-                                        tp.ctypes.data_as(C.POINTER(C.c_uint64)), _u32p(oc), _dp(xy),
-                                        None if pe is None else pe.ctypes.data_as(u8p), C.byref(h))
-        _raise_if_failed(lib, "gsfm_ba_problem_create", st)
-        self._lib, self._h = lib, h
-        self.n_cams, self.n_tracks, self.n_obs = n, T, int(oc.shape[0])
+        return K, tp, oc, xy, flags(cam_estimated, K.shape[0], "cam_estimated"), flags(point_estimated, tp.shape[0] - 1, "point_estimated")
 
     def _check(self, st, what):
         if st != 0:
@@ -641,7 +636,7 @@ class BundleProblem(object):
 
     def close(self):
         if self._h is not None:
-            self._lib.gsfm_ba_problem_destroy(self._h)
+            self._fn("problem_destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -662,11 +657,11 @@ class BundleProblem(object):
         else:
             raise TypeError("the bundle adjustment needs a loss with a native descriptor, got %r" % (loss,))
         arr, n = _abi.make_program(nodes)
-        self._check(self._lib.gsfm_ba_set_loss(self._h, arr, n), "set_loss")
+        self._check(self._fn("set_loss")(self._h, arr, n), "set_loss")
 
     def default_options(self):
         o = _abi.BaOptions()
-        self._lib.gsfm_ba_options_default(C.byref(o))
+        self._fn("options_default")(C.byref(o))
         return o
 
     def _options(self, kw):
@@ -680,6 +675,29 @@ class BundleProblem(object):
     def _point(self, cam_pos, points):
         return (np.array(cam_pos, dtype=np.float64, order="C").reshape(self.n_cams, 3),
                 np.array(points, dtype=np.float64, order="C").reshape(self.n_tracks, 3))
+
+
+class BundleProblem(_BundleProblemBase):
+    """Bundle adjustment of camera positions and points with fixed orientations (include/gsfm_ba.h): Theia's
+    BundleAdjustCameraPositionsAndPoints on the device, the points eliminated and the reduced camera system solved by PCG.
+    rot_aa: N x 3, intrinsics: N x 3 (f u v); track_ptr / obs_cam / obs_xy: the track CSR of triangulate_tracks; cam_estimated (N) and
+    point_estimated (T): flags or None (all estimated).  A new problem has Ceres' NULL loss."""
+    _PREFIX = "gsfm_ba_"
+
+    def __init__(self, rot_aa, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated=None, point_estimated=None):
+        lib = _abi.load_library()
+        rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(-1, 3)
+        K, tp, oc, xy, ce, pe = self._track_arrays(intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated)
+        n, T = rot.shape[0], tp.shape[0] - 1
+        if K.shape[0] != n:
+            raise ValueError("rot_aa and intrinsics must describe the same cameras")
+        u8p = C.POINTER(C.c_uint8)
+        h = C.c_void_p()
+        st = lib.gsfm_ba_problem_create(n, _dp(rot), _dp(K), None if ce is None else ce.ctypes.data_as(u8p), T,
+                                        tp.ctypes.data_as(C.POINTER(C.c_uint64)), _u32p(oc), _dp(xy),
+                                        None if pe is None else pe.ctypes.data_as(u8p), C.byref(h))
+        _raise_if_failed(lib, "gsfm_ba_problem_create", st)
+        self._adopt(lib, h, n, T, int(oc.shape[0]))
 
     def solve(self, cam_pos, points, **options):
         """Returns (camera positions N x 3, points T x 3, summary dict); inactive and unestimated rows are returned as given."""
@@ -741,5 +759,89 @@ def bundle_adjust_positions_and_points(rot_aa, cam_pos, intrinsics, track_ptr, o
     try:
         prob.set_loss(loss)
         return prob.solve(cam_pos, points, **options)
+    finally:
+        prob.close()
+
+
+class FullBundleProblem(_BundleProblemBase):
+    """The full bundle adjustment (include/gsfm_ba6.h): Theia's GlobalReconstructionEstimator::BundleAdjustment on the device, camera
+    orientations, camera positions and points moving together (intrinsics held), the points eliminated and the reduced 6 x 6-block camera
+    system solved by PCG.  The arguments are BundleProblem's without rot_aa: the orientations are a start value of solve()."""
+    _PREFIX = "gsfm_ba6_"
+
+    def __init__(self, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated=None, point_estimated=None):
+        lib = _abi.load_library()
+        K, tp, oc, xy, ce, pe = self._track_arrays(intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated)
+        n, T = K.shape[0], tp.shape[0] - 1
+        u8p = C.POINTER(C.c_uint8)
+        h = C.c_void_p()
+        st = lib.gsfm_ba6_problem_create(n, _dp(K), None if ce is None else ce.ctypes.data_as(u8p), T, tp.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                         _u32p(oc), _dp(xy), None if pe is None else pe.ctypes.data_as(u8p), C.byref(h))
+        _raise_if_failed(lib, "gsfm_ba6_problem_create", st)
+        self._adopt(lib, h, n, T, int(oc.shape[0]))
+
+    def _point6(self, rot_aa, cam_pos, points):
+        return (np.array(rot_aa, dtype=np.float64, order="C").reshape(self.n_cams, 3), ) + self._point(cam_pos, points)
+
+    def solve(self, rot_aa, cam_pos, points, **options):
+        """Returns (orientations N x 3, camera positions N x 3, points T x 3, summary dict); inactive and unestimated rows are returned as given."""
+        w, c, p = self._point6(rot_aa, cam_pos, points)
+        o, s = self._options(options), _abi.BaSummary()
+        self._check(self._lib.gsfm_ba6_solve(self._h, _dp(w), _dp(c), _dp(p), C.byref(o), C.byref(s)), "solve")
+        return w, c, p, s.as_dict()
+
+    def residuals(self, rot_aa, cam_pos, points):
+        """(r: n_obs x 2, rho: n_obs); zeros for an unused observation"""
+        w, c, p = self._point6(rot_aa, cam_pos, points)
+        r, rho = np.zeros((self.n_obs, 2)), np.zeros(self.n_obs)
+        self._check(self._lib.gsfm_ba6_residuals(self._h, _dp(w), _dp(c), _dp(p), _dp(r), _dp(rho)), "residuals")
+        return r, rho
+
+    def linearize(self, rot_aa, cam_pos, points):
+        """dict(cost, grad_rot N x 3, grad_pos N x 3, grad_point T x 3, diag_cam N x 6 x 6 (w then o), diag_point T x 3 x 3)"""
+        w, c, p = self._point6(rot_aa, cam_pos, points)
+        cost = np.zeros(1)
+        gr, gc, gp = np.zeros((self.n_cams, 3)), np.zeros((self.n_cams, 3)), np.zeros((self.n_tracks, 3))
+        dc, dp = np.zeros((self.n_cams, 6, 6)), np.zeros((self.n_tracks, 3, 3))
+        self._check(self._lib.gsfm_ba6_linearize(self._h, _dp(w), _dp(c), _dp(p), _dp(cost), _dp(gr), _dp(gc), _dp(gp), _dp(dc), _dp(dp)), "linearize")
+        return {"cost": float(cost[0]), "grad_rot": gr, "grad_pos": gc, "grad_point": gp, "diag_cam": dc, "diag_point": dp}
+
+    def schur_matvec(self, v, radius=1e4, **options):
+        """y = Sc v (N x 6, per camera w then o) for the last linearize / step_check, damped at `radius`"""
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(self.n_cams, 6)
+        y = np.zeros((self.n_cams, 6))
+        o = self._options(options)
+        self._check(self._lib.gsfm_ba6_schur_matvec(self._h, _dp(v), float(radius), C.byref(o), _dp(y)), "schur_matvec")
+        return y
+
+    def step_check(self, rot_aa, cam_pos, points, radius=1e4, **options):
+        """gsfm_ba6_step_check: dict(rhs, y_cam (N x 6), y_point, delta_rot, delta_pos, delta_point, j_delta (n_obs x 2), model_cost_change, dg,
+        jd2, cg_rel, cg_iterations, stalled)"""
+        w, c, p = self._point6(rot_aa, cam_pos, points)
+        o = self._options(options)
+        N, T = self.n_cams, self.n_tracks
+        rhs, yc, yp = np.zeros((N, 6)), np.zeros((N, 6)), np.zeros((T, 3))
+        dr, dc, dp, jd = np.zeros((N, 3)), np.zeros((N, 3)), np.zeros((T, 3)), np.zeros((self.n_obs, 2))
+        scal, info = np.zeros(4), np.zeros(2, dtype=np.int32)
+        st = self._lib.gsfm_ba6_step_check(self._h, _dp(w), _dp(c), _dp(p), float(radius), C.byref(o), _dp(rhs), _dp(yc), _dp(yp), _dp(dr), _dp(dc), _dp(dp),
+                                           _dp(jd), _dp(scal), info.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._check(st, "step_check")
+        return {"rhs": rhs, "y_cam": yc, "y_point": yp, "delta_rot": dr, "delta_pos": dc, "delta_point": dp, "j_delta": jd, "model_cost_change": scal[0],
+                "dg": scal[1], "jd2": scal[2], "cg_rel": scal[3], "cg_iterations": int(info[0]), "stalled": bool(info[1])}
+
+    def time_kernels(self, rot_aa, cam_pos, points, radius=1e4, reps=10):
+        """mean device microseconds of the kernels of one linearisation and one Schur product (gsfm_ba6_time_kernels)"""
+        w, c, p = self._point6(rot_aa, cam_pos, points)
+        out = np.zeros(8)
+        self._check(self._lib.gsfm_ba6_time_kernels(self._h, _dp(w), _dp(c), _dp(p), float(radius), int(reps), _dp(out)), "time_kernels")
+        return dict(zip(("camera_records", "lin_tracks", "lin_cameras", "cost", "point_pass", "camera_pass", "preconditioner", "quadratic_form"), out))
+
+
+def bundle_adjust(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, points, cam_estimated=None, point_estimated=None, loss=None, **options):
+    """One call: FullBundleProblem(...).set_loss(loss).solve(rot_aa, cam_pos, points, **options).  Returns (rot_aa, cam_pos, points, summary dict)."""
+    prob = FullBundleProblem(intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated)
+    try:
+        prob.set_loss(loss)
+        return prob.solve(rot_aa, cam_pos, points, **options)
     finally:
         prob.close()

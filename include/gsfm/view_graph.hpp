@@ -210,6 +210,10 @@ struct BundleAdjustmentStats {
 };
 BundleAdjustmentStats BundleAdjustCameraPositionsAndPoints(const std::string& loss_function, double loss_width, int max_num_iterations,
                                                            theia::Reconstruction* reconstruction);
+// GlobalReconstructionEstimator::BundleAdjustment (the solve of BundleAdjustmentAndRemoveOutlierPoints; intrinsics_to_optimize = NONE) on the
+// device: gsfm_ba6_solve under the definition of include/gsfm_ba6.h, over all estimated views and tracks.  As above, and the orientations of
+// the estimated views are written back as well.
+BundleAdjustmentStats BundleAdjustment(const std::string& loss_function, double loss_width, int max_num_iterations, theia::Reconstruction* reconstruction);
 #endif
 
 // two_views.txt of scripts/read_colmap_database.py:52-133 as AddColmapMatchesToReconstructionBuilder reads it
