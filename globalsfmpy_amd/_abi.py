@@ -357,6 +357,9 @@ def declare_track_signatures(lib):
                                                    C.POINTER(TrackRefineOptions), C.POINTER(LossNode), C.c_int32,
                                                    _DP, i32p, i32p, _DP, i32p, _DP, _DP, i32p, u64p, _DP]
     lib.gsfm_tracks_triangulate_refine.restype = C.c_int
+    lib.gsfm_tracks_outlier_tracks.argtypes = [C.c_uint32, _DP, _DP, _DP, C.POINTER(C.c_uint8), C.c_uint64, u64p, _U32P, _DP, _DP, C.POINTER(C.c_uint8),
+                                               C.c_double, C.c_double, i32p, i32p, _DP, u64p, _DP]
+    lib.gsfm_tracks_outlier_tracks.restype = C.c_int
 
 
 def declare_ba_signatures(lib):

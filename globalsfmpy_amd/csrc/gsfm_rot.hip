@@ -20,6 +20,7 @@
 #include "trans_refine.hpp"
 #include "triangulate.hpp"
 #include "track_refine.hpp"
+#include "outlier_tracks.hpp"
 #include "solver_ba.hpp"
 #include "solver_ba6.hpp"
 
@@ -380,6 +381,16 @@ gsfm_status gsfm_tracks_triangulate_refine(uint32_t n_cams, const double* rot_aa
   return guarded("the track refinement", tri_refine_impl, n_cams, rot_aa, cam_pos, intrinsics, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy,
                  min_triangulation_angle_degrees, max_reprojection_error_pixels, options, loss_program, n_loss_nodes, point_out, status_out,
                  n_views_out, mean_sq_err_out, iterations_out, initial_cost_out, final_cost_out, termination_out, counts_out, kernel_ms);
+}
+
+gsfm_status gsfm_tracks_outlier_tracks(uint32_t n_cams, const double* rot_aa, const double* cam_pos, const double* intrinsics,
+                                       const uint8_t* cam_estimated, uint64_t n_tracks, const uint64_t* track_ptr, const uint32_t* obs_cam,
+                                       const double* obs_xy, const double* points, const uint8_t* point_estimated,
+                                       double max_reprojection_error_pixels, double min_triangulation_angle_degrees, int32_t* status_out,
+                                       int32_t* n_views_out, double* mean_sq_err_out, uint64_t* counts_out, double* kernel_ms) {
+  return guarded("the outlier rule", outlier_tracks_impl, n_cams, rot_aa, cam_pos, intrinsics, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy,
+                 points, point_estimated, max_reprojection_error_pixels, min_triangulation_angle_degrees, status_out, n_views_out,
+                 mean_sq_err_out, counts_out, kernel_ms);
 }
 
 gsfm_status gsfm_tracks_launch_order(uint64_t n_tracks, const uint64_t* track_ptr, uint32_t* order_out, uint64_t* class_begin_out) {

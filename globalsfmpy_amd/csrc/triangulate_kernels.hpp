@@ -18,7 +18,8 @@
 //                   gate    lane l re-reads its observations' pixels and camera records: depth sign and squared pixel error, butterfly.
 // The ray store is written and read by different lanes of ONE wavefront: a work-group fence orders the two.  No atomics, nothing waits
 // for another work-group, no host round trip.  Front (pass 1, angle, solve) and gate are __device__ functions: k_tri_refine_tracks
-// (track_refine_kernels.hpp) runs the same text around its refinement.  A track's arithmetic depends on its own length and data alone (the class, the lane
+// (track_refine_kernels.hpp) runs the same text around its refinement, and k_outlier_tracks (outlier_kernels.hpp) runs the angle sweep
+// (tri_angle) and the gate on a point it is given.  A track's arithmetic depends on its own length and data alone (the class, the lane
 // stride and the butterfly are functions of the length), so two calls return the same bytes and so does a call with the tracks permuted.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -108,6 +109,27 @@ __device__ __forceinline__ TriTrack tri_track(const TriArgs& a, double* lds_rays
   return k;
 }
 
+// Step 3 of include/gsfm_tracks.h over the group's ray store: true when some pair i < j has d_i . d_j < cos(min angle).  Row block i0 = 0,
+// G, ...: lane l holds ray i0 + l in registers and all lanes read ray j together; the group leaves at the first j at which any lane's pair
+// passes.  The same value in every lane.  Also the angle test of k_outlier_tracks (outlier_kernels.hpp), whose rays come from the point.
+template <int G>
+__device__ __forceinline__ bool tri_angle(const TriTrack& tk, int l, int lane_in_wave, double cos_min_angle) {
+  const uint32_t len = tk.len;
+  const double* const rx = tk.rx, * const ry = tk.ry, * const rz = tk.rz;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  bool found = false;
+  for (uint32_t i0 = 0; i0 < len && !found; i0 += G) {
+    const uint32_t i = i0 + l;
+    double e0 = nan, e1 = nan, e2 = nan;
+    if (i < len) { e0 = rx[i]; e1 = ry[i]; e2 = rz[i]; }
+    for (uint32_t j = i0 + 1; j < len; ++j) {
+      const double dot = e0 * rx[j] + e1 * ry[j] + e2 * rz[j];
+      if (tri_group_any<G>(j > i && dot < cos_min_angle, lane_in_wave)) { found = true; break; }
+    }
+  }
+  return found;
+}
+
 // Steps 1 to 4 of include/gsfm_tracks.h, the text both track kernels run: the rays and the sums, the angle test, the midpoint.  Returns the
 // status (0: X holds the midpoint; 1, 2, 3: X is zero); n is the count of observations in estimated views.  The same values in every lane.
 template <int G>
@@ -144,20 +166,7 @@ __device__ __forceinline__ int tri_front(const TriArgs& a, const TriTrack& tk, i
   int status = 0;
   X[0] = 0.0; X[1] = 0.0; X[2] = 0.0;
   if (n < 2) status = 1;
-  else {
-    // ---- the angle: some pair i < j with d_i . d_j < cos(min angle) ----
-    bool found = false;
-    for (uint32_t i0 = 0; i0 < len && !found; i0 += G) {
-      const uint32_t i = i0 + l;
-      double e0 = nan, e1 = nan, e2 = nan;
-      if (i < len) { e0 = rx[i]; e1 = ry[i]; e2 = rz[i]; }
-      for (uint32_t j = i0 + 1; j < len; ++j) {
-        const double dot = e0 * rx[j] + e1 * ry[j] + e2 * rz[j];
-        if (tri_group_any<G>(j > i && dot < a.cos_min_angle, lane_in_wave)) { found = true; break; }
-      }
-    }
-    if (!found) status = 2;
-  }
+  else if (!tri_angle<G>(tk, l, lane_in_wave, a.cos_min_angle)) status = 2;   // the angle: some pair i < j with d_i . d_j < cos(min angle)
   if (status == 0) {
     // ---- M X = q by Cholesky, M = L L^T ----
     const double p0 = s[0];

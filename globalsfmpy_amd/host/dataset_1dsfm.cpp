@@ -214,7 +214,24 @@ void FlattenTracks(const theia::Reconstruction& rec, FlatTracks* out) {
   }
 }
 
-EstimateStructureStats EstimateStructure(double min_angle_degrees, double max_error_pixels, theia::Reconstruction* rec, const TrackRefinement* refinement) {
+void KeepUnestimatedTracks(const theia::Reconstruction& rec, FlatTracks* out, std::vector<uint64_t>* track_index) {
+  track_index->clear();
+  std::vector<uint64_t> ptr(1, 0);
+  std::vector<uint32_t> cam;
+  std::vector<double> xy;
+  for (size_t t = 0; t + 1 < out->track_ptr.size(); ++t) {
+    if (t < rec.track_estimated.size() && rec.track_estimated[t]) continue;
+    const uint64_t b = out->track_ptr[t], e = out->track_ptr[t + 1];
+    cam.insert(cam.end(), out->obs_cam.begin() + b, out->obs_cam.begin() + e);
+    xy.insert(xy.end(), out->obs_xy.begin() + 2 * b, out->obs_xy.begin() + 2 * e);
+    ptr.push_back(cam.size());
+    track_index->push_back(t);
+  }
+  out->track_ptr.swap(ptr); out->obs_cam.swap(cam); out->obs_xy.swap(xy);
+}
+
+EstimateStructureStats EstimateStructure(double min_angle_degrees, double max_error_pixels, theia::Reconstruction* rec, const TrackRefinement* refinement,
+                                         bool only_unestimated) {
   EstimateStructureStats stats;
   gsfm_loss_node loss{};
   if (refinement) {
@@ -228,6 +245,9 @@ EstimateStructureStats EstimateStructure(double min_angle_degrees, double max_er
   if (!rec->tracks || rec->tracks->tracks.empty()) return stats;   // a dataset without tracks.txt: nothing to triangulate
   FlatTracks f;
   FlattenTracks(*rec, &f);
+  const size_t num_all = f.track_ptr.size() - 1;
+  std::vector<uint64_t> track_index;
+  if (only_unestimated) KeepUnestimatedTracks(*rec, &f, &track_index);
   const size_t T = f.track_ptr.size() - 1;
   std::vector<double> point(3 * T, 0.0);
   std::vector<int32_t> status(T, 0);
@@ -255,6 +275,17 @@ EstimateStructureStats EstimateStructure(double min_angle_degrees, double max_er
                                  status.data(), nullptr, nullptr, stats.counts, &stats.kernel_ms);
   }
   if (st != GSFM_OK) throw std::runtime_error(std::string("EstimateStructure: ") + gsfm_last_error());
+  if (only_unestimated) {   // scatter by index; the estimated tracks keep point and flag
+    rec->track_point.resize(num_all, Eigen::Vector3d(0.0, 0.0, 0.0));
+    rec->track_estimated.resize(num_all, 0);
+    for (size_t k = 0; k < T; ++k) {
+      rec->track_point[track_index[k]] = Eigen::Vector3d(point[3 * k], point[3 * k + 1], point[3 * k + 2]);
+      rec->track_estimated[track_index[k]] = status[k] == 0;
+    }
+    stats.num_tracks = T;
+    stats.num_estimated = (size_t)stats.counts[0];
+    return stats;
+  }
   rec->track_point.assign(T, Eigen::Vector3d());
   rec->track_estimated.assign(T, 0);
   for (size_t t = 0; t < T; ++t) {
@@ -302,6 +333,30 @@ UnderconstrainedStats SetUnderconstrainedAsUnestimated(theia::Reconstruction* re
     }
     stats.views_removed += views; stats.tracks_removed += removed_tracks;
   }
+  return stats;
+}
+
+OutlierTracksStats SetOutlierTracksToUnestimated(double max_error_pixels, double min_angle_degrees, theia::Reconstruction* rec) {
+  OutlierTracksStats stats;
+  if (!rec->tracks || rec->tracks->tracks.empty()) return stats;
+  FlatTracks f;
+  FlattenTracks(*rec, &f);
+  const size_t T = f.track_ptr.size() - 1;
+  std::vector<uint8_t> point_estimated(T, 0);
+  std::vector<double> points(3 * T, 0.0);
+  for (size_t t = 0; t < T && t < rec->track_estimated.size(); ++t) {
+    point_estimated[t] = rec->track_estimated[t];
+    for (int k = 0; k < 3; ++k) points[3 * t + k] = rec->track_point[t][k];
+  }
+  std::vector<int32_t> status(T, 0);
+  const gsfm_status st = gsfm_tracks_outlier_tracks((uint32_t)f.views.size(), f.rot_aa.data(), f.cam_pos.data(), f.intrinsics.data(), f.cam_estimated.data(), T,
+                                                    f.track_ptr.data(), f.obs_cam.data(), f.obs_xy.data(), points.data(), point_estimated.data(),
+                                                    max_error_pixels, min_angle_degrees, status.data(), nullptr, nullptr, stats.counts, &stats.kernel_ms);
+  if (st != GSFM_OK) throw std::runtime_error(std::string("SetOutlierTracksToUnestimated: ") + gsfm_last_error());
+  for (size_t t = 0; t < T && t < rec->track_estimated.size(); ++t)
+    if (status[t] >= 2) rec->track_estimated[t] = 0;   // the point stays, as in Theia
+  stats.num_examined = T - (size_t)stats.counts[1];
+  stats.num_removed = (size_t)(stats.counts[2] + stats.counts[3] + stats.counts[4]);
   return stats;
 }
 

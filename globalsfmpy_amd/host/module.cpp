@@ -118,6 +118,9 @@ struct ReconstructionEstimatorOptions {
   std::string bundle_adjustment_loss_function_type = "TRIVIAL";   // :248 (LossFunctionType::TRIVIAL); the YAML's bundle_adjustment_robust_loss_function
   double bundle_adjustment_robust_loss_width = 10.0;         // :251
   int min_cameras_for_iterative_solver = 1000;               // :258; from this many views on BundleAdjustCameraPositionsAndPoints takes 1.5 x the iterations
+  double max_reprojection_error_in_pixels = 5.0;             // :115; the outlier rule after a bundle adjustment (the YAML's max_reprojection_error_pixels)
+  int num_retriangulation_iterations = 1;                    // :237; the pipeline's structure loop runs 1 + this many times
+  bool refine_camera_positions_and_points_after_position_estimation = true;   // :229; the partial adjustment of the loop's first pass
 };
 struct ReconstructionBuilderOptions {
   int num_threads = 1;
@@ -238,14 +241,16 @@ class GlobalReconstructionEstimator {
   // gated on angle and reprojection error, over the views SetReconstructionFromEstimatedPoses marked, in one device call
   // refine = true honours options_.bundle_adjust_tracks: Theia's BundleAdjustTrack between the midpoint and the gate, in the same device call,
   // with the loss of bundle_adjustment_loss_function_type / bundle_adjustment_robust_loss_width
-  gsfm::EstimateStructureStats EstimateStructure(bool refine = false) {
+  // only_unestimated = true is Theia's TrackEstimator::EstimateTracks: the tracks that are estimated already keep their (bundle-adjusted)
+  // points, the others are triangulated; the summary then counts those others alone
+  gsfm::EstimateStructureStats EstimateStructure(bool refine = false, bool only_unestimated = false) {
     if (!reconstruction_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
     gsfm::TrackRefinement r;
     r.loss_function = options_.bundle_adjustment_loss_function_type;
     r.loss_width = options_.bundle_adjustment_robust_loss_width;
     const bool refined = refine && options_.bundle_adjust_tracks;
     structure_ = gsfm::EstimateStructure(options_.min_triangulation_angle_degrees, options_.triangulation_max_reprojection_error_in_pixels, reconstruction_,
-                                         refined ? &r : nullptr);
+                                         refined ? &r : nullptr, only_unestimated);
     structure_refine_asked_ = refine;
     return structure_;
   }
@@ -260,6 +265,15 @@ class GlobalReconstructionEstimator {
                                                          iterations, reconstruction_);
     return bundle_.usable;
   }
+  // bind_src/GlobalSfMpy.cpp:591-608: BundleAdjustment(); an unusable solution returns at once and removes nothing; otherwise Theia's
+  // SetOutlierTracksToUnestimated with max_reprojection_error_in_pixels and min_triangulation_angle_degrees (gsfm_tracks_outlier_tracks).
+  bool BundleAdjustmentAndRemoveOutlierPoints() {
+    outlier_ = gsfm::OutlierTracksStats();
+    if (!BundleAdjustment()) return false;
+    outlier_ = gsfm::SetOutlierTracksToUnestimated(options_.max_reprojection_error_in_pixels, options_.min_triangulation_angle_degrees, reconstruction_);
+    return true;
+  }
+  gsfm::OutlierTracksStats outlier_;     // of the last BundleAdjustmentAndRemoveOutlierPoints (zeros when the adjustment was not usable)
   // Theia's BundleAdjustment (the solve of BundleAdjustmentAndRemoveOutlierPoints; SetOutlierTracksToUnestimated is not part of it): all
   // estimated views and tracks, orientations, positions and points move, intrinsics are held; loss and iteration rule as above.  The new
   // orientations and positions are written back to the reconstruction.
@@ -318,6 +332,15 @@ py::dict bundle_dict(const gsfm::BundleAdjustmentStats& st) {
   return d;
 }
 
+py::dict outlier_dict(const gsfm::OutlierTracksStats& st) {
+  py::dict d;
+  d["num_examined"] = st.num_examined; d["num_removed"] = st.num_removed; d["kernel_ms"] = st.kernel_ms;
+  d["counts"] = std::vector<uint64_t>(st.counts, st.counts + 5);
+  d["num_bad_reprojections"] = st.counts[2] + st.counts[3];            // what Theia's log calls them
+  d["num_insufficient_viewing_angles"] = st.counts[4];
+  return d;
+}
+
 py::dict pos_summary_dict(const gsfm_pos_summary& s) {
   py::dict d;
   d["termination"] = s.termination; d["num_iterations"] = s.num_iterations;
@@ -347,6 +370,10 @@ void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions
   get("bundle_adjustment_robust_loss_function", options.reconstruction_estimator_options.bundle_adjustment_loss_function_type);
   get("bundle_adjustment_robust_loss_width", options.reconstruction_estimator_options.bundle_adjustment_robust_loss_width);
   get("min_cameras_for_iterative_solver", options.reconstruction_estimator_options.min_cameras_for_iterative_solver);
+  get("max_reprojection_error_pixels", options.reconstruction_estimator_options.max_reprojection_error_in_pixels);
+  get("num_retriangulation_iterations", options.reconstruction_estimator_options.num_retriangulation_iterations);
+  get("refine_camera_positions_and_points_after_position_estimation",
+      options.reconstruction_estimator_options.refine_camera_positions_and_points_after_position_estimation);
 }
 
 }  // namespace
@@ -435,7 +462,11 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def_readwrite("bundle_adjust_tracks", &ReconstructionEstimatorOptions::bundle_adjust_tracks)
       .def_readwrite("bundle_adjustment_loss_function_type", &ReconstructionEstimatorOptions::bundle_adjustment_loss_function_type)
       .def_readwrite("bundle_adjustment_robust_loss_width", &ReconstructionEstimatorOptions::bundle_adjustment_robust_loss_width)
-      .def_readwrite("min_cameras_for_iterative_solver", &ReconstructionEstimatorOptions::min_cameras_for_iterative_solver);
+      .def_readwrite("min_cameras_for_iterative_solver", &ReconstructionEstimatorOptions::min_cameras_for_iterative_solver)
+      .def_readwrite("max_reprojection_error_in_pixels", &ReconstructionEstimatorOptions::max_reprojection_error_in_pixels)
+      .def_readwrite("num_retriangulation_iterations", &ReconstructionEstimatorOptions::num_retriangulation_iterations)
+      .def_readwrite("refine_camera_positions_and_points_after_position_estimation",
+                     &ReconstructionEstimatorOptions::refine_camera_positions_and_points_after_position_estimation);
   py::class_<ReconstructionBuilderOptions>(m, "ReconstructionBuilderOptions")
       .def(py::init<>())
       .def_readwrite("num_threads", &ReconstructionBuilderOptions::num_threads)
@@ -466,10 +497,13 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
         return ids;
       })
       // the flat arrays EstimateStructure() hands to gsfm_tracks_triangulate (solver.triangulate_tracks takes the same)
-      .def("FlattenedTracks", [](const Reconstruction& r) -> py::object {
+      // only_unestimated: the sub-batch EstimateStructure(only_unestimated=True) runs (gsfm::KeepUnestimatedTracks), plus track_index
+      .def("FlattenedTracks", [](const Reconstruction& r, bool only_unestimated) -> py::object {
         if (!r.tracks) return py::none();
         gsfm::FlatTracks f;
         gsfm::FlattenTracks(r, &f);
+        std::vector<uint64_t> track_index;
+        if (only_unestimated) gsfm::KeepUnestimatedTracks(r, &f, &track_index);
         auto arr = [](const auto& v, py::ssize_t cols) {
           using T = typename std::decay_t<decltype(v)>::value_type;
           py::array_t<T> a = cols > 1 ? py::array_t<T>({(py::ssize_t)(v.size() / cols), cols}) : py::array_t<T>((py::ssize_t)v.size());
@@ -479,8 +513,9 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
         py::dict d;
         d["views"] = arr(f.views, 1); d["rot_aa"] = arr(f.rot_aa, 3); d["cam_pos"] = arr(f.cam_pos, 3); d["intrinsics"] = arr(f.intrinsics, 3);
         d["cam_estimated"] = arr(f.cam_estimated, 1); d["track_ptr"] = arr(f.track_ptr, 1); d["obs_cam"] = arr(f.obs_cam, 1); d["obs_xy"] = arr(f.obs_xy, 2);
+        if (only_unestimated) d["track_index"] = arr(track_index, 1);
         return d;
-      })
+      }, py::arg("only_unestimated") = false)
       // what EstimateStructure stores per track, settable (a reconstruction assembled by hand)
       .def("SetTrack", [](Reconstruction& r, size_t t, const Eigen::Vector3d& point, bool estimated) {
         if (t >= (size_t)r.NumTracks()) throw py::index_error("no such track");
@@ -556,11 +591,20 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
         return refine_stats_dict(st);
       })
       .def("FilterRelativeTranslation", &GlobalReconstructionEstimator::FilterRelativeTranslation, py::call_guard<py::gil_scoped_release>())
-      .def("EstimateStructure", [](GlobalReconstructionEstimator& e, bool refine) {
+      .def("EstimateStructure", [](GlobalReconstructionEstimator& e, bool refine, bool only_unestimated) {
         gsfm::EstimateStructureStats st;
-        { py::gil_scoped_release release; st = e.EstimateStructure(refine); }
+        { py::gil_scoped_release release; st = e.EstimateStructure(refine, only_unestimated); }
         return structure_dict(st, e.options_.bundle_adjust_tracks, refine);
-      }, py::arg("refine") = false)
+      }, py::arg("refine") = false, py::arg("only_unestimated") = false)
+      // the reference returns its BundleAdjustmentSummary: the LastBundleAdjustmentSummary() dict plus success and num_points_removed
+      .def("BundleAdjustmentAndRemoveOutlierPoints", [](GlobalReconstructionEstimator& e) {
+        bool ok;
+        { py::gil_scoped_release release; ok = e.BundleAdjustmentAndRemoveOutlierPoints(); }
+        py::dict d = bundle_dict(e.bundle_);
+        d["success"] = ok; d["num_points_removed"] = e.outlier_.num_removed;
+        return d;
+      })
+      .def("LastOutlierSummary", [](const GlobalReconstructionEstimator& e) { return outlier_dict(e.outlier_); })
       .def("BundleAdjustCameraPositionsAndPoints", &GlobalReconstructionEstimator::BundleAdjustCameraPositionsAndPoints,
            py::call_guard<py::gil_scoped_release>())
       .def("BundleAdjustment", &GlobalReconstructionEstimator::BundleAdjustment, py::call_guard<py::gil_scoped_release>())
@@ -690,6 +734,10 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
     d["rounds"] = st.rounds; d["views_removed"] = st.views_removed; d["tracks_removed"] = st.tracks_removed;
     return d;
   });
+  // Theia's SetOutlierTracksToUnestimated, its name, argument order and return value (the number of tracks removed)
+  m.def("SetOutlierTracksToUnestimated", [](double max_inlier_reprojection_error, double min_triangulation_angle_degrees, Reconstruction* rec) {
+    return (int)gsfm::SetOutlierTracksToUnestimated(max_inlier_reprojection_error, min_triangulation_angle_degrees, rec).num_removed;
+  }, py::call_guard<py::gil_scoped_release>());
   m.def("WritePlyFile", [](const std::string& ply_file, const Reconstruction& rec, int min_num_observations_per_point) {
     if (ply_file.empty()) throw std::invalid_argument("WritePlyFile: empty file name");
     return gsfm::WritePlyFile(ply_file, rec, min_num_observations_per_point);

@@ -513,6 +513,54 @@ def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, 
     return {"points": points, "status": status, "n_views": n_views, "mean_sq_err": err, "counts": counts, "kernel_ms": ms.value}
 
 
+def outlier_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, points, cam_estimated=None, point_estimated=None,
+                   max_reprojection_error_pixels=5.0, min_triangulation_angle_degrees=4.0):
+    """gsfm_tracks_outlier_tracks: the outlier rule after a bundle adjustment (Theia's SetOutlierTracksToUnestimated under the definition of
+    include/gsfm_tracks.h) on the device, a group of 4, 16 or 64 lanes per estimated track.  The cameras and tracks of triangulate_tracks;
+    points: T x 3; point_estimated: T flags or None (all estimated).  The defaults are Theia's.  Nothing is modified: the caller drops the
+    tracks of the statuses 2 to 4.
+    Returns dict(status (0 kept, 1 not estimated on input, 2 behind a camera, 3 reprojection error, 4 insufficient viewing angle), n_views,
+    mean_sq_err, counts (5), kernel_ms)."""
+    lib = _abi.load_library()
+    rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(-1, 3)
+    n = rot.shape[0]
+    pos = np.ascontiguousarray(cam_pos, dtype=np.float64).reshape(-1, 3)
+    K = np.ascontiguousarray(intrinsics, dtype=np.float64).reshape(-1, 3)
+    tp = np.ascontiguousarray(track_ptr, dtype=np.uint64).reshape(-1)
+    oc = np.ascontiguousarray(obs_cam, dtype=np.uint32).reshape(-1)
+    xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    if pos.shape[0] != n or K.shape[0] != n:
+        raise ValueError("rot_aa, cam_pos and intrinsics must describe the same cameras")
+    if tp.shape[0] < 1 or xy.shape[0] != oc.shape[0]:
+        raise ValueError("track_ptr needs n_tracks + 1 entries, and obs_cam and obs_xy one row per observation")
+    T = tp.shape[0] - 1
+    if int(tp.max()) > oc.shape[0]:
+        raise ValueError("track_ptr points past the end of the observations")
+    if pts.shape[0] != T:
+        raise ValueError("points needs one row per track")
+    u8p = C.POINTER(C.c_uint8)
+    est = pest = None
+    if cam_estimated is not None:
+        est = np.ascontiguousarray(np.asarray(cam_estimated) != 0, dtype=np.uint8).reshape(-1)
+        if est.shape[0] != n:
+            raise ValueError("cam_estimated needs one flag per camera")
+    if point_estimated is not None:
+        pest = np.ascontiguousarray(np.asarray(point_estimated) != 0, dtype=np.uint8).reshape(-1)
+        if pest.shape[0] != T:
+            raise ValueError("point_estimated needs one flag per track")
+    status, n_views = np.zeros(T, dtype=np.int32), np.zeros(T, dtype=np.int32)
+    err, counts = np.zeros(T), np.zeros(5, dtype=np.uint64)
+    ms = C.c_double(0)
+    i32p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    st = lib.gsfm_tracks_outlier_tracks(n, _dp(rot), _dp(pos), _dp(K), None if est is None else est.ctypes.data_as(u8p), T, tp.ctypes.data_as(u64p),
+                                        _u32p(oc), _dp(xy), _dp(pts), None if pest is None else pest.ctypes.data_as(u8p),
+                                        float(max_reprojection_error_pixels), float(min_triangulation_angle_degrees), status.ctypes.data_as(i32p),
+                                        n_views.ctypes.data_as(i32p), _dp(err), counts.ctypes.data_as(u64p), C.byref(ms))
+    _raise_if_failed(lib, "gsfm_tracks_outlier_tracks", st)
+    return {"status": status, "n_views": n_views, "mean_sq_err": err, "counts": counts, "kernel_ms": ms.value}
+
+
 def track_launch_order(track_ptr):
     """gsfm_tracks_launch_order (host code): (order, class_begin) -- the tracks by lane class 4, 16, 64, longest first inside a class."""
     lib = _abi.load_library()

@@ -162,6 +162,9 @@ struct FlatTracks {
   std::vector<double> obs_xy;
 };
 void FlattenTracks(const theia::Reconstruction& reconstruction, FlatTracks* out);
+// The sub-CSR of the tracks that are NOT estimated (track_estimated 0 or not yet set), in ascending track order: track_ptr, obs_cam and obs_xy
+// of `out` are replaced by those tracks' slices, the cameras stay; track_index[k] is the track the sub-batch's k-th track is.  Host code.
+void KeepUnestimatedTracks(const theia::Reconstruction& reconstruction, FlatTracks* out, std::vector<uint64_t>* track_index);
 struct EstimateStructureStats {
   size_t num_tracks = 0, num_estimated = 0;
   uint64_t counts[6] = {0, 0, 0, 0, 0, 0};           // tracks per status of gsfm_tracks_triangulate
@@ -181,8 +184,24 @@ struct TrackRefinement {
 };
 // One call of gsfm_tracks_triangulate -- with `refinement`, of gsfm_tracks_triangulate_refine -- over all tracks; stores point and estimated flag per track in the reconstruction.  A reconstruction
 // without tracks is left alone.  Throws std::runtime_error when no device is usable (there is no CPU fallback) or the device call fails.
+// only_unestimated (Theia's TrackEstimator::EstimateTracks, which skips the estimated tracks): the same entry runs on KeepUnestimatedTracks'
+// sub-batch and its points and flags are scattered back by index; an estimated track keeps its point bytes and its flag, and the stats
+// count the sub-batch.  The entry's permutation guarantee makes a track's result that of a call over all tracks.
 EstimateStructureStats EstimateStructure(double min_triangulation_angle_degrees, double max_reprojection_error_pixels,
-                                         theia::Reconstruction* reconstruction, const TrackRefinement* refinement = nullptr);
+                                         theia::Reconstruction* reconstruction, const TrackRefinement* refinement = nullptr,
+                                         bool only_unestimated = false);
+// Theia's SetOutlierTracksToUnestimated (sfm/set_outlier_tracks_to_unestimated.cc) on the device: gsfm_tracks_outlier_tracks under the
+// definition of include/gsfm_tracks.h, over FlattenTracks' arrays plus track_point / track_estimated.  Clears the flag of every track of
+// status 2, 3 or 4 and leaves track_point alone, as Theia leaves the point.  num_removed is Theia's return value.  A reconstruction without
+// tracks is left alone.  Throws std::runtime_error when no device is usable (there is no CPU fallback) or the device call fails.
+struct OutlierTracksStats {
+  size_t num_examined = 0;                           // tracks estimated on input
+  uint64_t counts[5] = {0, 0, 0, 0, 0};              // tracks per status of gsfm_tracks_outlier_tracks
+  size_t num_removed = 0;                            // counts[2] + counts[3] + counts[4]
+  double kernel_ms = 0.0;
+};
+OutlierTracksStats SetOutlierTracksToUnestimated(double max_reprojection_error_pixels, double min_triangulation_angle_degrees,
+                                                 theia::Reconstruction* reconstruction);
 // Theia's io/write_ply_file.cc: the points of the estimated tracks with at least min_num_observations_per_point views (no colour: 0 0 0;
 // ascending track index where Theia walks a hash set), then the estimated views' positions in green.  A view without a position is
 // written at the origin (a rotation-only reconstruction).  Returns false when the file cannot be written.

@@ -147,6 +147,54 @@ gsfm_status gsfm_tracks_triangulate_refine(uint32_t n_cams, const double* rot_aa
                                            int32_t* iterations_out, double* initial_cost_out, double* final_cost_out, int32_t* termination_out,
                                            uint64_t* counts_out, double* kernel_ms);
 
+/* ---- The outlier rule after a bundle adjustment: gsfm_tracks_outlier_tracks ----
+ *
+ * Restates Theia's SetOutlierTracksToUnestimated (sfm/set_outlier_tracks_to_unestimated.cc), the second half of the reference pipeline's
+ * BundleAdjustmentAndRemoveOutlierPoints(): every estimated track is tested on the reprojection error of its point and on the angle under
+ * which its estimated views see that point.  The cameras and tracks of gsfm_tracks_triangulate, with the same meaning and the same checks;
+ * points (n_tracks x 3, the tracks' points in the world) and point_estimated (n_tracks bytes, non-zero = estimated; NULL = every track is
+ * estimated).  Nothing is written to the inputs: the caller clears the flags of the statuses 2 to 4.
+ *
+ * Per track that is estimated on input, over its observations whose camera is estimated, in the order given (n of them; the others are
+ * skipped everywhere), with the track's point X:
+ *   1. gate quantities   step 5 of gsfm_tracks_triangulate on X, its text unchanged: p = R (X - o) per observation, behind = some p_z < 0,
+ *                        mean = sum |(f p_x / p_z + u, f p_y / p_z + v) - (x, y)|^2 / n, the sum in that entry's order (below).  Given the
+ *                        point gsfm_tracks_triangulate returned for a track, mean_sq_err_out is that call's mean_sq_err_out bit for bit.
+ *   2. ray               d = (X - o) / |X - o|, |v| = sqrt(v_x^2 + v_y^2 + v_z^2), in the world frame: Theia's Point().hnormalized() -
+ *                        GetPosition(), normalised.  It comes from the point, not from the pixel.  A point at a camera centre gives a NaN
+ *                        ray, which passes no comparison.
+ *   3. status, decided in this order:
+ *        2  behind: some p_z < 0.  Theia counts this as a bad reprojection; it stops at the first such view, and the result does not depend
+ *           on which one that is.
+ *        3  mean > max_reprojection_error_pixels^2.  Strict, as in Theia: a NaN mean (p_z = 0 with p_x = 0, or n = 0) is NOT removed here and
+ *           goes on to the angle test; +inf is removed.
+ *        4  no pair i < j with d_i . d_j < c, c = cos(min_triangulation_angle_degrees pi / 180) computed once on the host in fp64 (step 3 of
+ *           gsfm_tracks_triangulate on these rays).  n < 2 lands here, n = 0 included, as Theia's empty loop does.
+ *        0  kept.
+ *   A track that is not estimated on input is status 1: it is not examined and its optional outputs are 0.
+ *   Departure that decides nothing at the tolerances of interest: p is formed with the matrix R, as in gsfm_tracks_triangulate.
+ * Outputs: status_out (n_tracks, required); optional (NULL: not returned) n_views_out (n_tracks: the count n), mean_sq_err_out (n_tracks: the
+ * mean of step 1, whatever the status 0, 2, 3 or 4; NaN where n = 0), counts_out[5] (tracks per status; Theia's return value is
+ * counts[2] + counts[3] + counts[4], its log reports 2 and 3 together as bad reprojection errors and 4 alone as insufficient viewing angles),
+ * kernel_ms (device time of the kernels).
+ *
+ * Order of the sums: that of gsfm_tracks_triangulate.  The lane class is a function of the track's CSR length (len <= 8: G = 4;
+ * 9 <= len <= 64: G = 16; len >= 65: G = 64), lane l adds the squared errors of the observations at places l, l + G, ... in that order
+ * starting from 0, then the xor butterfly.  A track's result depends on its own length and data alone: two calls return the same bytes,
+ * permuting the tracks permutes the outputs bit for bit, and another track's point_estimated changes nothing for this one.  The estimated
+ * tracks run in the order gsfm_tracks_launch_order gives (the others are left out of it and never reach the device).
+ *
+ * Device memory: that of gsfm_tracks_triangulate, 20 B per observation (+ 24 B per observation when an estimated track of 65 or more
+ * observations exists) + 52 B per track + O(n_cams); the points take the place of that entry's point_out and point_estimated stays on the host.
+ * GSFM_ERR_INVALID_ARG before any device call by the rules of gsfm_tracks_triangulate, and for NULL points, NULL status_out, a bound or an
+ * angle that is negative or not finite.  No tracks, or none estimated: GSFM_OK with kernel_ms = 0 and no device call.  Otherwise without a
+ * device GSFM_ERR_NO_DEVICE: there is no host fallback. */
+gsfm_status gsfm_tracks_outlier_tracks(uint32_t n_cams, const double* rot_aa, const double* cam_pos, const double* intrinsics,
+                                       const uint8_t* cam_estimated, uint64_t n_tracks, const uint64_t* track_ptr, const uint32_t* obs_cam,
+                                       const double* obs_xy, const double* points, const uint8_t* point_estimated,
+                                       double max_reprojection_error_pixels, double min_triangulation_angle_degrees, int32_t* status_out,
+                                       int32_t* n_views_out, double* mean_sq_err_out, uint64_t* counts_out, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
