@@ -9,7 +9,7 @@
 // Unknowns are one array of (2 n_cams + n_tracks) x 3: the cameras' angle-axis vectors, the cameras' positions, the points -- three kinds
 // of 3-vector nodes, so that the node-wise kernels of pos_kernels.hpp and ba_kernels.hpp (dots, reductions, Jacobi scale, D^2, the PCG
 // direction) run unchanged; the points' inverses are this file's (k_ba6_prep_points: kept and applied in double-double).  `active` has one byte per node (a camera's two nodes carry the same byte), Dg holds the
-// three 3 x 3 diagonal blocks per kind; the 3 x 3 block between a camera's two nodes goes to Bx (for gsfm_ba6_linearize only).
+// three 3 x 3 diagonal blocks per kind; the 3 x 3 block between a camera's two nodes goes to Bx (for gsfm_ba6_linearize, and for the last resort of k_ba6_cam_precond).
 //
 // Layout.  Per observation in the caller's (track-major) order: Jt (12 doubles: Jp rows 0 1, Jr rows 0 1) and Rt (2: r~), written by the
 // POINT side of the linearisation, the only place that evaluates an observation.  The camera side copies Jt into its own order, Jc (one
@@ -71,59 +71,7 @@ __global__ void __launch_bounds__(256) k_ba6_cameras(uint32_t n_cams, const doub
   for (int k = 25; k < GSFM_BA6_CAM_DOUBLES; ++k) o[k] = 0.0;
 }
 
-// ---- double-double pieces (the point solve) ------------------------------------------------------------------------------------------
-// Far from the minimum a point's damped block C~_t can be nearly singular.  Its inverse then has entries of size cond(C~_t), the sums it is
-// applied to cancel, and B~ - E~ C~^-1 E~^T cancels again: in plain fp64 the reduced system carries errors of u cond(C~_t) that a solver
-// which does not eliminate never sees.  So the inverse is kept as an unevaluated sum hi + lo, and the track sums it is
-// applied to are accumulated in double-double.  (contract(off): under the device default, -ffp-contract=fast, a + p with p = x y would become
-// fma(x, y, a) and the two-sums below would lose their error terms.)
-__device__ __forceinline__ void ba6_two_sum(double a, double b, double& s, double& e) {
-#pragma clang fp contract(off)
-  s = a + b;
-  const double bb = s - a;
-  e = (a - (s - bb)) + (b - bb);
-}
-// (hi, lo) += a b: the product by fma (error-free), the sum by Knuth's two-sum
-__device__ __forceinline__ void ba6_dd_mac(double a, double b, double& hi, double& lo) {
-#pragma clang fp contract(off)
-  const double p = a * b, pe = fma(a, b, -p);
-  double sum, se;
-  ba6_two_sum(hi, p, sum, se);
-  hi = sum; lo += se + pe;
-}
-// (hi, lo) += a (bh + bl)
-__device__ __forceinline__ void ba6_dd_mac2(double a, double bh, double bl, double& hi, double& lo) {
-  ba6_dd_mac(a, bh, hi, lo);
-  lo += a * bl;
-}
-__device__ __forceinline__ void ba6_dd_add(double& hi, double& lo, double ohi, double olo) {
-#pragma clang fp contract(off)
-  double sum, se;
-  ba6_two_sum(hi, ohi, sum, se);
-  lo = (lo + olo) + se;   // (symmetric in the two operands: both lanes of a butterfly pair get the same pair)
-  hi = sum;
-}
-template <int G>
-__device__ __forceinline__ void ba6_group_allsum_dd(double& hi, double& lo) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) {
-    const double ohi = __shfl_xor(hi, off, G), olo = __shfl_xor(lo, off, G);
-    ba6_dd_add(hi, lo, ohi, olo);
-  }
-}
-// w = (Xh + Xl) (th + tl), rounded once: Ci holds the inverse as 9 + 9 doubles (row-major hi, then lo)
-__device__ __forceinline__ void ba6_apply_inv_dd(const double* Ci, const double* th, const double* tl, double* w) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    double hi = 0.0, lo = 0.0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      ba6_dd_mac(Ci[3 * r + c], th[c], hi, lo);
-      lo += Ci[3 * r + c] * tl[c] + Ci[9 + 3 * r + c] * th[c];
-    }
-    w[r] = hi + lo;
-  }
-}
+// (the double-double pieces of the point solve -- ba6_two_sum .. ba6_apply_inv_dd, ba6_refine_inv3 -- are in ba_kernels.hpp, which uses them too)
 
 // ---- point side ------------------------------------------------------------------------------------------------------------------
 // Linearisation at x: per observation Jp, Jr and r~ (stored in track order), per point C_t = sum Jp^T Jp into Dg and g_t = sum Jp^T r~ into g.
@@ -350,9 +298,11 @@ __global__ void __launch_bounds__(256) k_ba6_cam_pass(Ba6Dev a6, const double* _
   }
 }
 
-// Cholesky M = L L^T of a symmetric positive definite 6 x 6 (full, row-major) and Minv = L^-T L^-1, in one lane
-__device__ __forceinline__ void ba6_inv6(const double* M, double* Minv) {
+// Cholesky M = L L^T of a symmetric positive definite 6 x 6 (full, row-major) and Minv = L^-T L^-1, in one lane.  false: a pivot was not
+// positive (or not finite) -- M is not positive definite as computed and Minv is not to be used.
+__device__ __forceinline__ bool ba6_inv6(const double* M, double* Minv) {
   double L[36], Li[36];
+  bool ok = true;
 #pragma unroll
   for (int i = 0; i < 36; ++i) { L[i] = 0.0; Li[i] = 0.0; }
 #pragma unroll
@@ -360,6 +310,7 @@ __device__ __forceinline__ void ba6_inv6(const double* M, double* Minv) {
     double d = M[6 * c + c];
 #pragma unroll
     for (int k = 0; k < c; ++k) d -= L[6 * c + k] * L[6 * c + k];
+    ok = ok && d > 0.0 && d <= DBL_MAX;
     const double l = sqrt(d);
     L[6 * c + c] = l;
 #pragma unroll
@@ -391,11 +342,40 @@ __device__ __forceinline__ void ba6_inv6(const double* M, double* Minv) {
       for (int k = r; k < 6; ++k) s += Li[6 * k + r] * Li[6 * k + c];
       Minv[6 * r + c] = s; Minv[6 * c + r] = s;
     }
+  return ok;
 }
 
 // The preconditioner, the 6 x 6 block diagonal of the Schur complement (Ceres' SCHUR_JACOBI), inverted per camera:
 //   M_k = S_k (sum_{e in k} Jc^T (I - Jp G_t Jp^T) Jc) S_k + D2_k,   G_t = S_t C~_t^-1 S_t;   the identity on inactive rows.
+// G_t is plain fp64.  Where a point's block has lost rank (beyond the Tukey cut: one observation left) and is held up by the damping alone
+// (1e-10 of its scaled diagonal at radius 1e10), Jp G_t Jp^T carries u cond(C~_t), W = I - Jp G_t Jp^T (of the damping's size) is noise and M_k
+// can come out indefinite: its Cholesky fails.  Such a row is summed again with W from the pair inverse of k_ba6_prep_points, 1 - t^T C~^-1 t
+// accumulated in double-double (t = S_t Jp^T); should that block fail too, the row takes the block of B~ alone, S_k B_k S_k + D2_k (Dg and Bx of
+// k_ba6_cam_lin), positive definite by the damping.  Rows whose first Cholesky succeeds keep their bytes.  (Before, the NaNs of the failed
+// factorisation made r.z NaN and the PCG returned y = 0 without a word.)
+__device__ __forceinline__ void ba6_precond_add(const double* j, double w00, double w01, double w11, double* acc) {
+  // the rows of Jc = [Jr, -Jp] and of W Jc
+  double c0[6], c1[6], d0[6], d1[6];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { c0[c] = j[6 + c]; c1[c] = j[9 + c]; c0[3 + c] = -j[c]; c1[3 + c] = -j[3 + c]; }
+#pragma unroll
+  for (int c = 0; c < 6; ++c) { d0[c] = w00 * c0[c] + w01 * c1[c]; d1[c] = w01 * c0[c] + w11 * c1[c]; }
+  int q = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c) acc[q++] += c0[r] * d0[c] + c1[r] * d1[c];
+}
+__device__ __forceinline__ bool ba6_precond_invert(const double* acc, const double* s, const double* dd, double* M, double* inv) {
+  int q = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c) { const double m = s[r] * acc[q++] * s[c] + (r == c ? dd[r] : 0.0); M[6 * r + c] = m; M[6 * c + r] = m; }
+  return ba6_inv6(M, inv);
+}
 __global__ void __launch_bounds__(256) k_ba6_cam_precond(Ba6Dev a6, const double* __restrict__ S, const double* __restrict__ D2, const double* __restrict__ Gt,
+                                                          const double* __restrict__ Cinv, const double* __restrict__ Dg, const double* __restrict__ Bx,
                                                           double* __restrict__ Minv) {
   const BaDev& a = a6.b;
   const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -418,61 +398,61 @@ __global__ void __launch_bounds__(256) k_ba6_cam_precond(Ba6Dev a6, const double
     ba_sym_mac(gt, j[0], j[1], j[2], a0, a1, a2);
     ba_sym_mac(gt, j[3], j[4], j[5], b0, b1, b2);
     const double w00 = 1.0 - (j[0] * a0 + j[1] * a1 + j[2] * a2), w01 = -(j[0] * b0 + j[1] * b1 + j[2] * b2), w11 = 1.0 - (j[3] * b0 + j[4] * b1 + j[5] * b2);
-    // the rows of Jc = [Jr, -Jp] and of W Jc
-    double c0[6], c1[6], d0[6], d1[6];
+    ba6_precond_add(j, w00, w01, w11, acc);
+  }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) { c0[c] = j[6 + c]; c1[c] = j[9 + c]; c0[3 + c] = -j[c]; c1[3 + c] = -j[3 + c]; }
+  for (int q = 0; q < 21; ++q) acc[q] = wave_sum(acc[q]);
+  const size_t r3 = 3 * (size_t)row, p3 = 3 * ((size_t)a.n_cams + row);
+  const double s[6] = {S[r3], S[r3 + 1], S[r3 + 2], S[p3], S[p3 + 1], S[p3 + 2]};
+  const double dd[6] = {D2[r3], D2[r3 + 1], D2[r3 + 2], D2[p3], D2[p3 + 1], D2[p3 + 2]};
+  int ok = 1;
+  if (lane == 0) {
+    double M[36], inv[36];
+    ok = ba6_precond_invert(acc, s, dd, M, inv) ? 1 : 0;
+    if (ok) for (int i = 0; i < 36; ++i) Mi[i] = inv[i];
+  }
+  if (__shfl(ok, 0, 64)) return;   // (wave-uniform)
+  // the row again, W through the pair inverse
 #pragma unroll
-    for (int c = 0; c < 6; ++c) { d0[c] = w00 * c0[c] + w01 * c1[c]; d1[c] = w01 * c0[c] + w11 * c1[c]; }
-    int q = 0;
+  for (int q = 0; q < 21; ++q) acc[q] = 0.0;
+  for (uint32_t d = a.crow_ptr[row] + lane; d < end; d += 64) {
+    double j[12];
+    ba6_load_j(a6.Jc, d, j);
+    const size_t t = a.ctrk[d], node = 2 * (size_t)a.n_cams + t;
+    const double* Ci = Cinv + 18 * t;
+    const double zl[3] = {0.0, 0.0, 0.0};
+    double t0[3], t1[3], x0[3], x1[3];
 #pragma unroll
-    for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 3; ++c) { t0[c] = S[3 * node + c] * j[c]; t1[c] = S[3 * node + c] * j[3 + c]; }
+    ba6_apply_inv_dd(Ci, t0, zl, x0);
+    ba6_apply_inv_dd(Ci, t1, zl, x1);
+    double h00 = -1.0, l00 = 0.0, h01 = 0.0, l01 = 0.0, h11 = -1.0, l11 = 0.0;
 #pragma unroll
-      for (int c = r; c < 6; ++c) acc[q++] += c0[r] * d0[c] + c1[r] * d1[c];
+    for (int c = 0; c < 3; ++c) { ba6_dd_mac(t0[c], x0[c], h00, l00); ba6_dd_mac(t0[c], x1[c], h01, l01); ba6_dd_mac(t1[c], x1[c], h11, l11); }
+    ba6_precond_add(j, -(h00 + l00), -(h01 + l01), -(h11 + l11), acc);
   }
 #pragma unroll
   for (int q = 0; q < 21; ++q) acc[q] = wave_sum(acc[q]);
   if (lane == 0) {
-    const size_t r3 = 3 * (size_t)row, p3 = 3 * ((size_t)a.n_cams + row);
-    const double s[6] = {S[r3], S[r3 + 1], S[r3 + 2], S[p3], S[p3 + 1], S[p3 + 2]};
-    const double dd[6] = {D2[r3], D2[r3 + 1], D2[r3 + 2], D2[p3], D2[p3 + 1], D2[p3 + 2]};
     double M[36], inv[36];
-    int q = 0;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int c = r; c < 6; ++c) { const double m = s[r] * acc[q++] * s[c] + (r == c ? dd[r] : 0.0); M[6 * r + c] = m; M[6 * c + r] = m; }
-    ba6_inv6(M, inv);
+    if (!ba6_precond_invert(acc, s, dd, M, inv)) {
+      // Last resort, reached by no test since the row is summed again above: B~'s block is positive definite by construction (a sum of
+      // Jc^T Jc plus D2 > 0), so the result of its factorisation is not looked at; NaN inputs stay NaN and end as a stall in b6_pcg.
+      const double* Dr = Dg + 6 * (size_t)row, * Dp = Dg + 6 * ((size_t)a.n_cams + row), * X = Bx + 9 * (size_t)row;
+      const double Br[9] = {Dr[0], Dr[1], Dr[2], Dr[1], Dr[3], Dr[4], Dr[2], Dr[4], Dr[5]}, Bp[9] = {Dp[0], Dp[1], Dp[2], Dp[1], Dp[3], Dp[4], Dp[2], Dp[4], Dp[5]};
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+          M[6 * r + c] = s[r] * Br[3 * r + c] * s[c] + (r == c ? dd[r] : 0.0);
+          M[6 * (3 + r) + 3 + c] = s[3 + r] * Bp[3 * r + c] * s[3 + c] + (r == c ? dd[3 + r] : 0.0);
+          M[6 * r + 3 + c] = M[6 * (3 + c) + r] = s[r] * X[3 * r + c] * s[3 + c];
+        }
+      ba6_inv6(M, inv);
+    }
     for (int i = 0; i < 36; ++i) Mi[i] = inv[i];
   }
 }
 
 // ---- the points' inverses ------------------------------------------------------------------------------------------------------------
-// One Newton step X + X (I - M X) for the symmetric 3 x 3 M (00 01 02 11 12 22) and its approximate inverse X (full, row-major), the
-// residual I - M X accumulated in double-double so that the step sees the residual and not its rounding.  corr == NULL: X is replaced by
-// the step's result; else X stays and the correction X (I - M X) goes to corr, so that X + corr is the inverse as an unevaluated pair.
-__device__ __forceinline__ void ba6_refine_inv3(const double* m, double* X, double* corr) {
-  const double M9[9] = {m[0], m[1], m[2], m[1], m[3], m[4], m[2], m[4], m[5]};
-  double R[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      double hi = (r == c) ? -1.0 : 0.0, lo = 0.0;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) ba6_dd_mac(M9[3 * r + k], X[3 * k + c], hi, lo);
-      R[3 * r + c] = -(hi + lo);
-    }
-  double Y[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) Y[3 * r + c] = X[3 * r] * R[c] + X[3 * r + 1] * R[3 + c] + X[3 * r + 2] * R[6 + c];
-  // (the inverse of a symmetric matrix: the two triangles of the correction are averaged)
-  Y[1] = Y[3] = 0.5 * (Y[1] + Y[3]); Y[2] = Y[6] = 0.5 * (Y[2] + Y[6]); Y[5] = Y[7] = 0.5 * (Y[5] + Y[7]);
-#pragma unroll
-  for (int k = 0; k < 9; ++k) { if (corr) corr[k] = Y[k]; else X[k] += Y[k]; }
-}
 // k_ba_prep_points with the inverse as a pair: C~_t = S_t C_t S_t + D2_t inverted by cofactors, two Newton steps and the third step's
 // correction kept beside it (Cinv: 18 doubles per point); zneg through the pair, G_t (the preconditioner's) from its first half.
 __global__ void k_ba6_prep_points(uint32_t n_cam_nodes, uint32_t n_tracks, const uint8_t* __restrict__ active, const double* __restrict__ Dg,

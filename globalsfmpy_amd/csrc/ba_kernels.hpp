@@ -87,6 +87,96 @@ __device__ __forceinline__ void ba_sym_mac(const double* h, double v0, double v1
   y2 += h[2] * v0 + h[4] * v1 + h[5] * v2;
 }
 
+// ---- double-double pieces (the point solve) ------------------------------------------------------------------------------------------
+// Far from the minimum a point's damped block C~_t can be nearly singular.  Its inverse then has entries of size cond(C~_t), the sums it is
+// applied to cancel, and B~ - E~ C~^-1 E~^T cancels again: in plain fp64 the reduced system carries errors of u cond(C~_t) that a solver
+// which does not eliminate never sees.  So the inverse is kept as an unevaluated sum hi + lo, and the track sums it is
+// applied to are accumulated in double-double.  (contract(off): under the device default, -ffp-contract=fast, a + p with p = x y would become
+// fma(x, y, a) and the two-sums below would lose their error terms.)
+__device__ __forceinline__ void ba6_two_sum(double a, double b, double& s, double& e) {
+#pragma clang fp contract(off)
+  s = a + b;
+  const double bb = s - a;
+  e = (a - (s - bb)) + (b - bb);
+}
+// (hi, lo) += a b: the product by fma (error-free), the sum by Knuth's two-sum
+__device__ __forceinline__ void ba6_dd_mac(double a, double b, double& hi, double& lo) {
+#pragma clang fp contract(off)
+  const double p = a * b, pe = fma(a, b, -p);
+  double sum, se;
+  ba6_two_sum(hi, p, sum, se);
+  hi = sum; lo += se + pe;
+}
+// (hi, lo) += a (bh + bl)
+__device__ __forceinline__ void ba6_dd_mac2(double a, double bh, double bl, double& hi, double& lo) {
+  ba6_dd_mac(a, bh, hi, lo);
+  lo += a * bl;
+}
+__device__ __forceinline__ void ba6_dd_add(double& hi, double& lo, double ohi, double olo) {
+#pragma clang fp contract(off)
+  double sum, se;
+  ba6_two_sum(hi, ohi, sum, se);
+  lo = (lo + olo) + se;   // (symmetric in the two operands: both lanes of a butterfly pair get the same pair)
+  hi = sum;
+}
+template <int G>
+__device__ __forceinline__ void ba6_group_allsum_dd(double& hi, double& lo) {
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) {
+    const double ohi = __shfl_xor(hi, off, G), olo = __shfl_xor(lo, off, G);
+    ba6_dd_add(hi, lo, ohi, olo);
+  }
+}
+// w = (Xh + Xl) (th + tl), rounded once: Ci holds the inverse as 9 + 9 doubles (row-major hi, then lo)
+__device__ __forceinline__ void ba6_apply_inv_dd(const double* Ci, const double* th, const double* tl, double* w) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    double hi = 0.0, lo = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      ba6_dd_mac(Ci[3 * r + c], th[c], hi, lo);
+      lo += Ci[3 * r + c] * tl[c] + Ci[9 + 3 * r + c] * th[c];
+    }
+    w[r] = hi + lo;
+  }
+}
+
+// One Newton step X + X (I - M X) for the symmetric 3 x 3 M (00 01 02 11 12 22) and its approximate inverse X (full, row-major), the
+// residual I - M X accumulated in double-double so that the step sees the residual and not its rounding.  corr == NULL: X is replaced by
+// the step's result; else X stays and the correction X (I - M X) goes to corr, so that X + corr is the inverse as an unevaluated pair.
+__device__ __forceinline__ void ba6_refine_inv3(const double* m, double* X, double* corr) {
+  const double M9[9] = {m[0], m[1], m[2], m[1], m[3], m[4], m[2], m[4], m[5]};
+  double R[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double hi = (r == c) ? -1.0 : 0.0, lo = 0.0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) ba6_dd_mac(M9[3 * r + k], X[3 * k + c], hi, lo);
+      R[3 * r + c] = -(hi + lo);
+    }
+  double Y[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Y[3 * r + c] = X[3 * r] * R[c] + X[3 * r + 1] * R[3 + c] + X[3 * r + 2] * R[6 + c];
+  // (the inverse of a symmetric matrix: the two triangles of the correction are averaged)
+  Y[1] = Y[3] = 0.5 * (Y[1] + Y[3]); Y[2] = Y[6] = 0.5 * (Y[2] + Y[6]); Y[5] = Y[7] = 0.5 * (Y[5] + Y[7]);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) { if (corr) corr[k] = Y[k]; else X[k] += Y[k]; }
+}
+// A point whose damped block is badly conditioned -- max |C~| max |C~^-1| above GSFM_BA_DD_COND, as it is for a block that lost rank beyond
+// the Tukey cut and is held up by the damping alone -- is "flagged": k_ba_prep_points refines its inverse to a pair (Cinv: the refined X,
+// Cfix[0..8]: the correction, Cfix[9] = 1) and k_ba_point_pass / k_ba_cam_precond run its sums in double-double, as ba6_kernels.hpp does for
+// every point (DESIGN.md sections 16, 17).  Every other point keeps the plain fp64 path and its bytes.
+#define GSFM_BA_DD_COND 1e5
+#define GSFM_BA_FIX_DOUBLES 10
+__device__ __forceinline__ void ba_pair(const double* Ci, const double* fix, double* X18) {
+#pragma unroll
+  for (int c = 0; c < 9; ++c) { X18[c] = Ci[c]; X18[9 + c] = fix[c]; }
+}
+
 // ---- point side ------------------------------------------------------------------------------------------------------------------
 // Linearisation at x: per observation H_e and a_e (stored in track order), per point C_t = sum H_e into Dg and g_t = sum a_e into g.
 template <int G>
@@ -160,10 +250,43 @@ __global__ void GSFM_BA_TRACK_BOUNDS(G) k_ba_cost_tracks(BaDev a, BaSlots sl, co
 // cameras (0 on inactive ones), add = the node vector b or NULL.  scaled_out: out_t = S_t u_t (the z_t the camera pass gathers), else u_t.
 template <int G>
 __global__ void GSFM_BA_TRACK_BOUNDS(G) k_ba_point_pass(BaDev a, BaSlots sl, const double* __restrict__ q, const double* __restrict__ S,
-                                                         const double* __restrict__ Cinv, const double* __restrict__ add, double* __restrict__ out,
-                                                         int scaled_out) {
+                                                         const double* __restrict__ Cinv, const double* __restrict__ Cfix, const double* __restrict__ add,
+                                                         double* __restrict__ out, int scaled_out) {
   const BaTrack tk = ba_track<G>(a, sl);
   const int l = threadIdx.x % G;
+  if (tk.live && Cfix[GSFM_BA_FIX_DOUBLES * (size_t)tk.t + 9] != 0.0) {   // a flagged point (the whole group): the sums and the inverse as pairs
+    double yh[3] = {0.0, 0.0, 0.0}, yl[3] = {0.0, 0.0, 0.0};
+    for (uint32_t k = l; k < tk.len; k += G) {
+      const size_t e = tk.ob + k;
+      const size_t c = a.obs_cam[e];
+      double h[6];
+      ba_load_h(a.Ht, e, h);
+      const double H9[9] = {h[0], h[1], h[2], h[1], h[3], h[4], h[2], h[4], h[5]};
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) ba6_dd_mac(H9[3 * r + i], q[3 * c + i], yh[r], yl[r]);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ba6_group_allsum_dd<G>(yh[i], yl[i]);
+    if (l == 0) {
+      const size_t node = (size_t)a.n_cams + tk.t;
+      const double sc[3] = {S[3 * node], S[3 * node + 1], S[3 * node + 2]};
+      double th[3], tl[3], u[3], X18[18];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        double hi = 0.0, lo = 0.0;
+        ba6_dd_mac2(sc[i], yh[i], yl[i], hi, lo);
+        if (add) ba6_dd_add(hi, lo, add[3 * node + i], 0.0);
+        th[i] = hi; tl[i] = lo;
+      }
+      ba_pair(Cinv + 9 * (size_t)tk.t, Cfix + GSFM_BA_FIX_DOUBLES * (size_t)tk.t, X18);
+      ba6_apply_inv_dd(X18, th, tl, u);
+      double* o = out + 3 * (size_t)tk.t;
+      o[0] = scaled_out ? sc[0] * u[0] : u[0]; o[1] = scaled_out ? sc[1] * u[1] : u[1]; o[2] = scaled_out ? sc[2] * u[2] : u[2];
+    }
+    return;
+  }
   double y0 = 0.0, y1 = 0.0, y2 = 0.0;
   for (uint32_t k = l; k < tk.len; k += G) {
     const size_t e = tk.ob + k;
@@ -272,7 +395,7 @@ __global__ void __launch_bounds__(256) k_ba_cam_pass(BaDev a, const double* __re
 // The preconditioner, the block diagonal of the Schur complement (Ceres' SCHUR_JACOBI), inverted per camera:
 //   M_k = S_k (sum_{e in k} H_e - H_e G_t H_e) S_k + D2_k,   G_t = S_t C~_t^-1 S_t;   the identity on inactive rows.
 __global__ void __launch_bounds__(256) k_ba_cam_precond(BaDev a, const double* __restrict__ S, const double* __restrict__ D2, const double* __restrict__ Gt,
-                                                         double* __restrict__ Minv) {
+                                                         const double* __restrict__ Cinv, const double* __restrict__ Cfix, double* __restrict__ Minv) {
   const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= a.n_cams) return;
   double* Mi = Minv + 9 * (size_t)row;
@@ -287,6 +410,29 @@ __global__ void __launch_bounds__(256) k_ba_cam_precond(BaDev a, const double* _
     ba_load_h(a.Hc, d, h);
     ba_load_h(Gt, a.ctrk[d], gt);
     const double H9[9] = {h[0], h[1], h[2], h[1], h[3], h[4], h[2], h[4], h[5]};
+    const size_t tt = a.ctrk[d];
+    if (Cfix[GSFM_BA_FIX_DOUBLES * tt + 9] != 0.0) {   // a flagged point: H - H S C~^-1 S H cancels to the damping's size; column by column through the pair
+      const size_t node = (size_t)a.n_cams + tt;
+      const double sc[3] = {S[3 * node], S[3 * node + 1], S[3 * node + 2]}, zl[3] = {0.0, 0.0, 0.0};
+      double X18[18], U[9];   // U = S C~^-1 S H
+      ba_pair(Cinv + 9 * tt, Cfix + GSFM_BA_FIX_DOUBLES * tt, X18);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double tc[3] = {sc[0] * H9[c], sc[1] * H9[3 + c], sc[2] * H9[6 + c]};
+        double x[3];
+        ba6_apply_inv_dd(X18, tc, zl, x);
+        U[c] = sc[0] * x[0]; U[3 + c] = sc[1] * x[1]; U[6 + c] = sc[2] * x[2];
+      }
+      const int rr[6] = {0, 0, 0, 1, 1, 2}, cc[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        double hi = H9[3 * rr[j] + cc[j]], lo = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ba6_dd_mac(-H9[3 * rr[j] + k], U[3 * k + cc[j]], hi, lo);
+        acc[j] += hi + lo;
+      }
+      continue;
+    }
     double W[9];   // W = G H
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -332,23 +478,42 @@ __global__ void k_ba_prep_nodes(size_t n_nodes, const uint8_t* __restrict__ acti
 // preconditioner and zneg_t = -S_t C~^-1 b_t for the reduced right-hand side; zeros on inactive points.
 __global__ void k_ba_prep_points(uint32_t n_cams, uint32_t n_tracks, const uint8_t* __restrict__ active, const double* __restrict__ Dg,
                                  const double* __restrict__ S, const double* __restrict__ D2, const double* __restrict__ b, double* __restrict__ Cinv,
-                                 double* __restrict__ Gt, double* __restrict__ zneg) {
+                                 double* __restrict__ Cfix, double* __restrict__ Gt, double* __restrict__ zneg) {
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= n_tracks) return;
   const size_t node = (size_t)n_cams + t;
-  double Ci[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, G6[6] = {0, 0, 0, 0, 0, 0}, zn[3] = {0, 0, 0};
+  double Ci[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, G6[6] = {0, 0, 0, 0, 0, 0}, zn[3] = {0, 0, 0}, fix[GSFM_BA_FIX_DOUBLES] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (active[node]) {
     const double* D = Dg + 6 * node;
     const double s0 = S[3 * node], s1 = S[3 * node + 1], s2 = S[3 * node + 2];
     const double M[6] = {s0 * D[0] * s0 + D2[3 * node], s0 * D[1] * s1, s0 * D[2] * s2, s1 * D[3] * s1 + D2[3 * node + 1], s1 * D[4] * s2,
                          s2 * D[5] * s2 + D2[3 * node + 2]};
     pos_inv3(M, Ci);
+    double mm = 0.0, mi = 0.0;
+    for (int c = 0; c < 6; ++c) mm = fmax(mm, fabs(M[c]));
+    for (int c = 0; c < 9; ++c) mi = fmax(mi, fabs(Ci[c]));
+    const bool flagged = !(mm * mi <= GSFM_BA_DD_COND);   // (a NaN is flagged too)
+    if (flagged) {
+      ba6_refine_inv3(M, Ci, nullptr);
+      ba6_refine_inv3(M, Ci, nullptr);
+      ba6_refine_inv3(M, Ci, fix);   // C~^-1 = Ci + fix[0..8] to about u^2
+      fix[9] = 1.0;
+    }
     G6[0] = s0 * Ci[0] * s0; G6[1] = s0 * Ci[1] * s1; G6[2] = s0 * Ci[2] * s2; G6[3] = s1 * Ci[4] * s1; G6[4] = s1 * Ci[5] * s2; G6[5] = s2 * Ci[8] * s2;
     const double b0 = b[3 * node], b1 = b[3 * node + 1], b2 = b[3 * node + 2];
-    zn[0] = -s0 * (Ci[0] * b0 + Ci[1] * b1 + Ci[2] * b2);
-    zn[1] = -s1 * (Ci[3] * b0 + Ci[4] * b1 + Ci[5] * b2);
-    zn[2] = -s2 * (Ci[6] * b0 + Ci[7] * b1 + Ci[8] * b2);
+    if (flagged) {
+      const double bh[3] = {b0, b1, b2}, bl[3] = {0.0, 0.0, 0.0};
+      double X18[18], w[3];
+      ba_pair(Ci, fix, X18);
+      ba6_apply_inv_dd(X18, bh, bl, w);
+      zn[0] = -s0 * w[0]; zn[1] = -s1 * w[1]; zn[2] = -s2 * w[2];
+    } else {
+      zn[0] = -s0 * (Ci[0] * b0 + Ci[1] * b1 + Ci[2] * b2);
+      zn[1] = -s1 * (Ci[3] * b0 + Ci[4] * b1 + Ci[5] * b2);
+      zn[2] = -s2 * (Ci[6] * b0 + Ci[7] * b1 + Ci[8] * b2);
+    }
   }
+  for (int c = 0; c < GSFM_BA_FIX_DOUBLES; ++c) Cfix[GSFM_BA_FIX_DOUBLES * t + c] = fix[c];
   for (int c = 0; c < 9; ++c) Cinv[9 * t + c] = Ci[c];
   for (int c = 0; c < 6; ++c) Gt[6 * t + c] = G6[c];
   for (int c = 0; c < 3; ++c) zneg[3 * t + c] = zn[c];

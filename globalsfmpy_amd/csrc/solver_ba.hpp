@@ -37,7 +37,7 @@ struct gsfm_ba_problem {
   // per camera
   double *rhs = nullptr, *r = nullptr, *z = nullptr, *p = nullptr, *q = nullptr, *Ap = nullptr, *Minv = nullptr;
   // per point
-  double *Cinv = nullptr, *Gt = nullptr, *zt = nullptr, *pt_scratch = nullptr;
+  double *Cinv = nullptr, *Cfix = nullptr, *Gt = nullptr, *zt = nullptr, *pt_scratch = nullptr;
   double *part = nullptr, *scal = nullptr;
   bool have_lin = false;
 };
@@ -112,12 +112,12 @@ void ba_norms(gsfm_ba_problem* P) {
 void ba_prep(gsfm_ba_problem* P, double radius, const gsfm_ba_options& o) {
   hipLaunchKernelGGL(k_ba_prep_nodes, ba_grid(P->n_nodes), dim3(256), 0, P->mem.s, P->n_nodes, P->active, P->Dg, P->g, P->S, radius, o.min_lm_diagonal,
                      o.max_lm_diagonal, P->D2, P->b);
-  hipLaunchKernelGGL(k_ba_prep_points, ba_grid(P->n_tracks), dim3(256), 0, P->mem.s, P->n_cams, P->n_tracks, P->active, P->Dg, P->S, P->D2, P->b, P->Cinv, P->Gt,
+  hipLaunchKernelGGL(k_ba_prep_points, ba_grid(P->n_tracks), dim3(256), 0, P->mem.s, P->n_cams, P->n_tracks, P->active, P->Dg, P->S, P->D2, P->b, P->Cinv, P->Cfix, P->Gt,
                      P->zt);
 }
 // out = Sc v on the cameras, v = pvec and q = S pvec given: the point pass, then the camera pass
 void ba_schur_product(gsfm_ba_problem* P, const double* qvec, const double* pvec, double* out) {
-  BA_TRACKS(P, k_ba_point_pass, qvec, (const double*)P->S, (const double*)P->Cinv, (const double*)nullptr, P->zt, 1);
+  BA_TRACKS(P, k_ba_point_pass, qvec, (const double*)P->S, (const double*)P->Cinv, (const double*)P->Cfix, (const double*)nullptr, P->zt, 1);
   hipLaunchKernelGGL(k_ba_cam_pass, ba_row_grid(P->n_cams), dim3(256), 0, P->mem.s, ba_dev(P), qvec, (const double*)P->zt, pvec, (const double*)P->S,
                      (const double*)P->D2, (const double*)nullptr, out, 1);
 }
@@ -130,7 +130,8 @@ int ba_pcg(gsfm_ba_problem* P, const gsfm_ba_options& o, int* iters, bool* stall
   HIPCHK(hipMemcpyAsync(P->scal + BS_RZA, P->scal + BS_RZ0, 8, hipMemcpyDeviceToDevice, P->mem.s));
   double rz0 = 0.0;
   if (int st = ba_read(P, &rz0, P->scal + BS_RZ0, 8, "pcg start")) return st;
-  if (!(rz0 > 0.0) || !std::isfinite(rz0)) return 0;   // rhs = 0: y = 0 is the solution (a NaN right-hand side: the step is refused later)
+  if (rz0 == 0.0) return 0;   // rhs = 0: y = 0 is the solution
+  if (!(rz0 > 0.0) || !std::isfinite(rz0)) { *stalled = true; *rel = rz0; return 0; }   // NaN (the step is refused later) or a preconditioner that is not positive definite: y = 0 is no solution -- say so
   const int check = std::max(1, o.cg_check_interval);
   double best = rz0; int best_it = 0;
   int cur = BS_RZA, nxt = BS_RZB;
@@ -148,6 +149,7 @@ int ba_pcg(gsfm_ba_problem* P, const gsfm_ba_options& o, int* iters, bool* stall
       if (int st = ba_read(P, &rz, P->scal + cur, 8, "pcg")) return st;
       *rel = std::sqrt(std::fmax(rz, 0.0) / rz0);
       if (!std::isfinite(rz)) { *rel = rz; break; }
+      if (rz < 0.0) { *rel = std::sqrt(-rz / rz0); break; }   // r.M^-1 r < 0: the system or its preconditioner is not positive definite as computed -- a breakdown, not a residual of zero
       if (*rel <= o.cg_relative_tolerance) { *iters = it; return 0; }
       if (rz <= 0.25 * best) { best = rz; best_it = it; }
       else if (o.cg_stall_iterations > 0 && it - best_it >= o.cg_stall_iterations) break;
@@ -169,12 +171,12 @@ int ba_step(gsfm_ba_problem* P, double radius, const gsfm_ba_options& o, BaStep*
   // reduced right-hand side b_c - E~ C~^-1 b_p (zt holds -S C~^-1 b_p), the Schur-Jacobi preconditioner, the PCG start
   hipLaunchKernelGGL(k_ba_cam_pass, ba_row_grid(N), dim3(256), 0, P->mem.s, ba_dev(P), (const double*)nullptr, (const double*)P->zt, (const double*)nullptr,
                      (const double*)P->S, (const double*)P->D2, (const double*)P->b, P->rhs, 0);
-  hipLaunchKernelGGL(k_ba_cam_precond, ba_row_grid(N), dim3(256), 0, P->mem.s, ba_dev(P), (const double*)P->S, (const double*)P->D2, (const double*)P->Gt, P->Minv);
+  hipLaunchKernelGGL(k_ba_cam_precond, ba_row_grid(N), dim3(256), 0, P->mem.s, ba_dev(P), (const double*)P->S, (const double*)P->D2, (const double*)P->Gt, (const double*)P->Cinv, (const double*)P->Cfix, P->Minv);
   hipLaunchKernelGGL(k_ba_pcg_init, ba_grid(N), dim3(256), 0, P->mem.s, N, P->active, P->rhs, P->Minv, P->S, P->y, P->r, P->z, P->p, P->q);
   if (int st = ba_pcg(P, o, &out->cg, &out->stalled, &out->cg_rel)) return st;
   // back-substitution y_p = C~^-1 (b_p - E~^T y_c), with q = S y_c
   hipLaunchKernelGGL(k_ba_scale, ba_grid(N), dim3(256), 0, P->mem.s, (size_t)N, P->active, P->S, P->y, 1.0, P->q);
-  if (T > 0) BA_TRACKS(P, k_ba_point_pass, (const double*)P->q, (const double*)P->S, (const double*)P->Cinv, (const double*)P->b, P->y + 3 * (size_t)N, 0);
+  if (T > 0) BA_TRACKS(P, k_ba_point_pass, (const double*)P->q, (const double*)P->S, (const double*)P->Cinv, (const double*)P->Cfix, (const double*)P->b, P->y + 3 * (size_t)N, 0);
   // the step, its gauge part removed, the trial point, and what the decision needs
   hipLaunchKernelGGL(k_ba_scale, ba_grid(NN), dim3(256), 0, P->mem.s, NN, P->active, P->S, P->y, -1.0, P->delta);
   if (o.remove_gauge && P->n_active > 0) {
@@ -342,7 +344,7 @@ FlatLayout ba_place(gsfm_ba_problem* P, char* slab, size_t* zeroed) {
   take(P->scal, BS_N); take(P->Dg, 6 * NN);
   for (double** v : {&P->x, &P->cand, &P->g, &P->S, &P->D2, &P->b, &P->y, &P->delta, &P->v}) take(*v, 3 * NN);
   for (double** v : {&P->rhs, &P->r, &P->z, &P->p, &P->q, &P->Ap}) take(*v, 3 * N);
-  take(P->zt, 3 * T); take(P->pt_scratch, T);
+  take(P->zt, 3 * T); take(P->pt_scratch, T); take(P->Cfix, GSFM_BA_FIX_DOUBLES * T);   // (no point is flagged before the first k_ba_prep_points)
   *zeroed = L.total;
   take(P->Minv, 9 * N); take(P->Cinv, 9 * T); take(P->Gt, 6 * T); take(P->part, GSFM_POS_PARTS);
   take(P->cams, GSFM_TRI_CAM_DOUBLES * N); take(P->Ht, 6 * O); take(P->At, 3 * O); take(P->Hc, 6 * U);
@@ -507,10 +509,10 @@ gsfm_status gsfm_ba_time_kernels(gsfm_ba_problem* P, const double* cam_pos, cons
   timed([&] { BA_TRACKS(P, k_ba_lin_tracks, (const double*)P->x, P->g, P->Dg); });
   timed([&] { hipLaunchKernelGGL(k_ba_cam_lin, ba_row_grid(N), dim3(256), 0, P->mem.s, ba_dev(P), P->g, P->Dg); });
   timed([&] { BA_TRACKS(P, k_ba_cost_tracks, (const double*)P->x, P->pt_scratch, (double*)nullptr, (double*)nullptr); });
-  timed([&] { BA_TRACKS(P, k_ba_point_pass, (const double*)P->q, (const double*)P->S, (const double*)P->Cinv, (const double*)nullptr, P->zt, 1); });
+  timed([&] { BA_TRACKS(P, k_ba_point_pass, (const double*)P->q, (const double*)P->S, (const double*)P->Cinv, (const double*)P->Cfix, (const double*)nullptr, P->zt, 1); });
   timed([&] { hipLaunchKernelGGL(k_ba_cam_pass, ba_row_grid(N), dim3(256), 0, P->mem.s, ba_dev(P), (const double*)P->q, (const double*)P->zt, (const double*)P->p,
                                  (const double*)P->S, (const double*)P->D2, (const double*)nullptr, P->Ap, 1); });
-  timed([&] { hipLaunchKernelGGL(k_ba_cam_precond, ba_row_grid(N), dim3(256), 0, P->mem.s, ba_dev(P), (const double*)P->S, (const double*)P->D2, (const double*)P->Gt, P->Minv); });
+  timed([&] { hipLaunchKernelGGL(k_ba_cam_precond, ba_row_grid(N), dim3(256), 0, P->mem.s, ba_dev(P), (const double*)P->S, (const double*)P->D2, (const double*)P->Gt, (const double*)P->Cinv, (const double*)P->Cfix, P->Minv); });
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return (gsfm_status)st;
 }
@@ -532,6 +534,8 @@ gsfm_status gsfm_ba_problem_create(uint32_t n_cams, const double* rot_aa, const 
 gsfm_status gsfm_ba_set_loss(gsfm_ba_problem* P, const gsfm_loss_node* prog, int32_t n) {
   if (!P || (n > 0 && !prog)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
   if (n < 0 || n > 1) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "the bundle adjustment takes a loss of one leaf (composite programs are not supported)");
+  // Every refusal below returns before P is read or written (the ABI tests hand in a handle that is no problem at all): keep the checks
+  // ahead of the first use of P.
   gsfm::DevLossNode leaf;
   std::memset(&leaf, 0, sizeof(leaf));
   leaf.kind = GSFM_LOSS_TRIVIAL;

@@ -123,7 +123,8 @@ int b6_pcg(gsfm_ba6_problem* P, const gsfm_ba_options& o, int* iters, bool* stal
   HIPCHK(hipMemcpyAsync(P->scal + B6_RZA, P->scal + B6_RZ0, 8, hipMemcpyDeviceToDevice, P->mem.s));
   double rz0 = 0.0;
   if (int st = b6_read(P, &rz0, P->scal + B6_RZ0, 8, "pcg start")) return st;
-  if (!(rz0 > 0.0) || !std::isfinite(rz0)) return 0;
+  if (rz0 == 0.0) return 0;                                   // rhs = 0: y = 0 is the solution
+  if (!(rz0 > 0.0) || !std::isfinite(rz0)) { *stalled = true; *rel = rz0; return 0; }   // NaN, or a preconditioner that is not positive definite: y = 0 is no solution -- say so
   const int check = std::max(1, o.cg_check_interval);
   double best = rz0; int best_it = 0;
   int cur = B6_RZA, nxt = B6_RZB;
@@ -141,6 +142,7 @@ int b6_pcg(gsfm_ba6_problem* P, const gsfm_ba_options& o, int* iters, bool* stal
       if (int st = b6_read(P, &rz, P->scal + cur, 8, "pcg")) return st;
       *rel = std::sqrt(std::fmax(rz, 0.0) / rz0);
       if (!std::isfinite(rz)) { *rel = rz; break; }
+      if (rz < 0.0) { *rel = std::sqrt(-rz / rz0); break; }   // r.M^-1 r < 0: the system or its preconditioner is not positive definite as computed -- a breakdown, not a residual of zero
       if (*rel <= o.cg_relative_tolerance) { *iters = it; return 0; }
       if (rz <= 0.25 * best) { best = rz; best_it = it; }
       else if (o.cg_stall_iterations > 0 && it - best_it >= o.cg_stall_iterations) break;
@@ -196,7 +198,7 @@ int b6_step(gsfm_ba6_problem* P, double radius, const gsfm_ba_options& o, BaStep
   // reduced right-hand side b_c - E~ C~^-1 b_p (zt holds -S C~^-1 b_p), the Schur-Jacobi preconditioner, the PCG start
   hipLaunchKernelGGL(k_ba6_cam_pass, ba_row_grid(N), dim3(256), 0, P->mem.s, b6_dev(P), (const double*)nullptr, (const double*)P->zt, -1.0, (const double*)nullptr,
                      (const double*)P->S, (const double*)P->D2, (const double*)P->b, P->rhs, 0);
-  hipLaunchKernelGGL(k_ba6_cam_precond, ba_row_grid(N), dim3(256), 0, P->mem.s, b6_dev(P), (const double*)P->S, (const double*)P->D2, (const double*)P->Gt, P->Minv);
+  hipLaunchKernelGGL(k_ba6_cam_precond, ba_row_grid(N), dim3(256), 0, P->mem.s, b6_dev(P), (const double*)P->S, (const double*)P->D2, (const double*)P->Gt, (const double*)P->Cinv, (const double*)P->Dg, (const double*)P->Bx, P->Minv);
   hipLaunchKernelGGL(k_ba6_pcg_init, ba_grid(N), dim3(256), 0, P->mem.s, N, P->active, P->rhs, P->Minv, P->S, P->y, P->r, P->z, P->p, P->q);
   if (int st = b6_pcg(P, o, &out->cg, &out->stalled, &out->cg_rel)) return st;
   // back-substitution y_p = C~^-1 (b_p - E~^T y_c), with q = S y_c
@@ -586,7 +588,7 @@ gsfm_status b6_time_kernels_impl(gsfm_ba6_problem* P, const double* rot_aa, cons
   timed([&] { B6_TRACKS(P, k_ba6_point_pass, (const double*)P->q, (const double*)P->S, (const double*)P->Cinv, (const double*)nullptr, 1.0, P->zt, 1); });
   timed([&] { hipLaunchKernelGGL(k_ba6_cam_pass, ba_row_grid(N), dim3(256), 0, P->mem.s, b6_dev(P), (const double*)P->q, (const double*)P->zt, 1.0, (const double*)P->p,
                                  (const double*)P->S, (const double*)P->D2, (const double*)nullptr, P->Ap, 1); });
-  timed([&] { hipLaunchKernelGGL(k_ba6_cam_precond, ba_row_grid(N), dim3(256), 0, P->mem.s, b6_dev(P), (const double*)P->S, (const double*)P->D2, (const double*)P->Gt, P->Minv); });
+  timed([&] { hipLaunchKernelGGL(k_ba6_cam_precond, ba_row_grid(N), dim3(256), 0, P->mem.s, b6_dev(P), (const double*)P->S, (const double*)P->D2, (const double*)P->Gt, (const double*)P->Cinv, (const double*)P->Dg, (const double*)P->Bx, P->Minv); });
   timed([&] { B6_TRACKS(P, k_ba6_quad_tracks, (const double*)P->delta, P->pt_scratch, (double*)nullptr); });
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return (gsfm_status)st;
@@ -620,6 +622,8 @@ gsfm_status gsfm_ba6_problem_create(uint32_t n_cams, const double* intrinsics, c
 gsfm_status gsfm_ba6_set_loss(gsfm_ba6_problem* P, const gsfm_loss_node* prog, int32_t n) {
   if (!P || (n > 0 && !prog)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
   if (n < 0 || n > 1) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "the full bundle adjustment takes a loss of one leaf (composite programs are not supported)");
+  // Every refusal below returns before P is read or written (the ABI tests hand in a handle that is no problem at all): keep the checks
+  // ahead of the first use of P.
   gsfm::DevLossNode leaf;
   std::memset(&leaf, 0, sizeof(leaf));
   leaf.kind = GSFM_LOSS_TRIVIAL;

@@ -446,7 +446,7 @@ def refine_relative_translations(n_cams, edge_i, edge_j, match_ptr, matches, int
 
 
 def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated=None, min_triangulation_angle_degrees=4.0,
-                       max_reprojection_error_pixels=15.0, refine=False, loss=None, max_num_iterations=100):
+                       max_reprojection_error_pixels=15.0, refine=False, loss=None, max_num_iterations=100, **refine_options):
     """gsfm_tracks_triangulate: every track triangulated by the midpoint method and gated on triangulation angle and reprojection error
     (Theia's TrackEstimator::EstimateTrack without the per-track refinement, under the definition of include/gsfm_tracks.h) on the device,
     a group of 4, 16 or 64 lanes per track.  rot_aa, cam_pos: N x 3; intrinsics: N x 3 (f u v); track_ptr: T + 1 offsets into obs_cam
@@ -456,8 +456,11 @@ def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, 
     refine=True: gsfm_tracks_triangulate_refine -- between the midpoint and the gate every track's point is refined by Levenberg-Marquardt
     with the cameras held (Theia's BundleAdjustTrack).  loss: None (Ceres' NULL loss), a list of (kind, p0, p1, p2) nodes or an object with
     .native_program(); one Trivial / Huber / SoftLOne / Tukey / GemanMcClure leaf.  The dict then also holds iterations, initial_cost,
-    final_cost, termination (per track, -1 = not refined), counts has 7 entries and status 6 is "refinement failed"."""
+    final_cost, termination (per track, -1 = not refined), counts has 7 entries and status 6 is "refinement failed".  refine_options: further
+    fields of gsfm_tracks_refine_options by name (function_tolerance, parameter_tolerance, ...)."""
     lib = _abi.load_library()
+    if refine_options and not refine:
+        raise TypeError("refinement options without refine=True: %s" % sorted(refine_options))
     rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(-1, 3)
     n = rot.shape[0]
     pos = np.ascontiguousarray(cam_pos, dtype=np.float64).reshape(-1, 3)
@@ -493,6 +496,10 @@ def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, 
         opt = _abi.TrackRefineOptions()
         lib.gsfm_tracks_refine_default_options(C.byref(opt))
         opt.refine, opt.max_num_iterations = 1, int(max_num_iterations)
+        for name, value in refine_options.items():
+            if name not in [f for f, _ in _abi.TrackRefineOptions._fields_]:
+                raise TypeError("gsfm_tracks_refine_options has no field %r" % name)
+            setattr(opt, name, value)
         err, counts = np.zeros(T), np.zeros(7, dtype=np.uint64)
         iters, term = np.zeros(T, dtype=np.int32), np.full(T, -1, dtype=np.int32)
         cost0, cost1 = np.zeros(T), np.zeros(T)

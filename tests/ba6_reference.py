@@ -16,7 +16,7 @@ from globalsfmpy_amd import synth
 
 import ba_reference as B
 import position_hp_reference as PH
-from ba_reference import DEFAULTS, LD, MARGIN, MP_DPS, TERM_NAMES, U, cached, decision_margin, loss_rho  # noqa: F401  (re-exported for the tests)
+from ba_reference import DEFAULTS, LD, MARGIN, MP_DPS, TERM_NAMES, U, cached, decision_margin, loss_rho, ratio  # noqa: F401  (re-exported for the tests)
 
 JL_SERIES_BELOW = 1e-3   # |w| below which the hp tier sums the series of J_l (20 terms: the remainder is below 1e-120)
 
@@ -49,7 +49,9 @@ def scene_c(noise_px=0.5, outlier_frac=0.03, seed=11):
 
 
 def scene(name):
-    """a, b, c: noisy; a0, b0, c0: noise-free"""
+    """a, b, c, t: noisy; a0, b0, c0: noise-free.  t is ba_reference.scene_t placed at THIS module's near start (the orientations are perturbed too)."""
+    if name == "t":
+        return cached(("scene6", name), lambda: B.scene_t(observe_np(B.scene("b"), near_start("b"))[0]))
     if name in ("c", "c0"):
         return cached(("scene6", name), (lambda: scene_c()) if name == "c" else (lambda: scene_c(0.0, 0.0)))
     return B.scene(name)
@@ -223,7 +225,7 @@ def damped(sc, lin, asm, S, radius, o=DEFAULTS):
     Cinv = np.array([B._inv3(m) for m in Ct]) if len(Ct) else Ct
     Cinv[~sc["pt_active"]] = 0
     E = S6[sc["obs_cam"], :, None] * np.einsum("eki,ekj->eij", lin["Jc"], lin["Jp"]) * S[2 * N + sc["track_of"], None, :]
-    return {"act": act, "D2": D2, "b": b, "Bt": Bt, "Ct": Ct, "Cinv": Cinv, "E": E, "S": S, "b6": np.concatenate([b[:N], b[N:2 * N]], 1)}
+    return B.add_cholesky(sc, {"act": act, "D2": D2, "b": b, "Bt": Bt, "Ct": Ct, "Cinv": Cinv, "E": E, "S": S, "b6": np.concatenate([b[:N], b[N:2 * N]], 1)})
 
 
 def cam_index(N, k):
@@ -264,7 +266,8 @@ def schur_system(sc, dm, absolute=False):
         es = np.arange(tp[t], tp[t + 1])[sc["used"][tp[t]:tp[t + 1]]]
         ks = sc["obs_cam"][es].astype(np.int64)
         Et = f(dm["E"][es])
-        EC = Et @ f(dm["Cinv"][t])
+        # (ba_reference.c_solve: the hp tier never multiplies by the rounded inverse)
+        EC = Et @ f(dm["Cinv"][t]) if absolute or "Cchol" not in dm else B.c_solve(dm, t, np.concatenate(Et, 0).T).T.reshape(Et.shape)
         np.add.at(rhs6, ks, sgn * (EC @ f(dm["b"][2 * N + t])))
         np.add.at(Mb, ks, sgn * np.einsum("aij,akj->aik", EC, Et))
         np.add.at(Sc4, (ks[:, None], ks[None, :]), sgn * np.einsum("aij,bkj->abik", EC, Et))
@@ -276,7 +279,7 @@ def back_substitute(sc, dm, yc):
     N = len(sc["cam_est"])
     acc = dm["b"][2 * N:].copy()
     np.add.at(acc, sc["track_of"], -np.einsum("eij,ei->ej", dm["E"], yc.reshape(N, 6)[sc["obs_cam"]]))
-    return np.einsum("tij,tj->ti", dm["Cinv"], acc)
+    return np.array([B.c_solve(dm, t, acc[t]) for t in range(len(acc))]).reshape(len(acc), 3)
 
 
 def cam6_to_nodes(y6):
@@ -507,6 +510,8 @@ LOSS = B.LOSS
 NEAR = (0.05, 1)   # sigma and seed of the start of the linearisation and step tests
 CASES = {   # name: (scene, sigma of the start's perturbation, seed); chosen on the CPU: tests/test_ba6_reference.py asserts the conditions
     "a_near": ("a", 0.05, 1), "a_far": ("a", 3.0, 1), "b_near": ("b", 0.05, 1), "b_far": ("b", 2.0, 5), "c_near": ("c", 0.05, 1), "c_far": ("c", 3.0, 16),
+    # a fourth entry is the case's loss (default LOSS); the near start, as in ba_reference.CASES (scene t's observations are placed at NEAR)
+    "t_near_tukey": ("t", 0.05, 1, B.TUKEY), "a_near_tukey": ("a", 0.05, 1, B.TUKEY), "a_near_geman": ("a", 0.05, 1, B.GEMAN),
 }
 
 
@@ -514,13 +519,17 @@ def near_start(sname):
     return nodes(*perturbed_start(scene(sname), *NEAR))
 
 
+def case_loss(name):
+    return CASES[name][3] if len(CASES[name]) > 3 else LOSS
+
+
 def case_start(name):
-    sname, sigma, seed = CASES[name]
+    sname, sigma, seed = CASES[name][:3]
     return nodes(*perturbed_start(scene(sname), sigma, seed))
 
 
 def case_solve(name, hp):
-    return cached(("solve6", name, hp), lambda: lm_solve(scene(CASES[name][0]), case_start(name), LOSS[0], LOSS[1], hp=hp))
+    return cached(("solve6", name, hp), lambda: lm_solve(scene(CASES[name][0]), case_start(name), *case_loss(name), hp=hp))
 
 
 def point_observation(sname, hp):

@@ -9,6 +9,8 @@ Two tiers over one text:
          rounding floor of the PCG residual.
 The tests bound the device by the fp64 tier's own deviation from the hp tier on the same quantity (see `MARGIN`).
 """
+import contextlib
+
 import mpmath
 import numpy as np
 
@@ -83,6 +85,34 @@ def scene_b(noise_px=0.5, seed=5):
     assert [rows[c] for c in (4, 1, 2, 3)] == [3, 63, 64, 65] and 280 <= rows[0] <= 320, rows[:5]
     assert rows.min() >= 3
     assert sorted(set(np.diff(track_ptr.astype(np.int64)))) == [2, 3, 8, 9, 64, 65, 70]
+    return sc
+
+
+T_CAMERA, T_TRACK = 4, 5   # scene t: the camera (3 rows) and the two-view track [30, 45] whose observations all lie beyond a Tukey cut of 10 px
+T_SINGLE = ((0, 7), (0, 40), (1, 0), (1, 33), (2, 17), (3, 4), (4, 2))   # (track, place in the track) of the single displaced observations
+T_AT_CUT = ((0, 20, 9.95), (1, 50, 10.05))   # (track, place, |r| at the near start): within 1 % of the cut, one on either side
+
+
+def scene_t(r=None, shift_px=50.0):
+    """Scene b's graph with observations that a Tukey loss of width 10 cuts at the near start (perturbation 0.05, seed 1): every observation
+    of camera T_CAMERA, both of track T_TRACK and the T_SINGLE ones in long tracks are displaced by shift_px ALONG their residual at that
+    start (so that the residual grows by that much whatever it was), and the T_AT_CUT ones are placed so that their residual there has the
+    given norm.  r: scene b's residuals (E x 2) at the start meant, default this module's near start (ba6_reference.py passes its own)."""
+    b = scene_b()
+    if r is None:
+        r = observe_np(b, *perturbed_start(b, 0.05, 0.05, 1))[0]
+    tp = b["track_ptr"].astype(np.int64)
+    es = set(np.flatnonzero(b["obs_cam"] == T_CAMERA)) | set(range(tp[T_TRACK], tp[T_TRACK + 1])) | {int(tp[t] + k) for t, k in T_SINGLE}
+    assert not es & {int(tp[t] + k) for t, k, _ in T_AT_CUT}
+    xy = b["obs_xy"].copy()
+    unit = r / np.sqrt((r * r).sum(1))[:, None]
+    for e in sorted(es):
+        xy[e] -= shift_px * unit[e]            # r = projection - xy
+    for t, k, norm in T_AT_CUT:
+        e = tp[t] + k
+        xy[e] += r[e] - norm * unit[e]
+    sc = dict(b)
+    sc["obs_xy"] = xy
     return sc
 
 
@@ -177,11 +207,23 @@ def observe_hp(sc, cam, pts):
 
 # ---- loss, Corrector, assembly (dtype of the inputs) -----------------------------------------------------------------------------
 def loss_rho(kind, a, s):
+    """(rho, rho', rho'') at s in the dtype of s.  a: the loss's width, or (width, sigma2) for Geman-McClure: the parameters of
+    loss_functions.GemanMcClureLoss in its order, sigma2 entering as it stands (tests/test_oracle_golden.py pins that class to the
+    reference project's vectors).  Tukey and Geman-McClure are Ceres' formulas as position_hp_reference.loss_rho states them."""
     one = s.dtype.type(1)
     if kind in (None, "trivial"):
         return s, np.ones_like(s), np.zeros_like(s)
-    a = s.dtype.type(a)
+    params = tuple(a) if isinstance(a, (tuple, list)) else (a,)
+    a = s.dtype.type(params[0])
     b = a * a
+    if kind == "tukey":
+        inside = s <= b
+        v = np.where(inside, one - s / b, 0)
+        return np.where(inside, b / 6 * (one - v * v * v), b / 6), np.where(inside, v * v / 2, 0), np.where(inside, -v / b, 0)
+    if kind == "geman_mcclure":
+        g2 = s.dtype.type(params[1])
+        t = s / b + g2
+        return b * g2 * s / (2 * (s + b * g2)), g2 * g2 / (2 * t * t), -(g2 * g2) / (b * t * t * t)
     with np.errstate(all="ignore"):
         if kind == "huber":
             rt = np.sqrt(s)
@@ -196,8 +238,39 @@ def loss_rho(kind, a, s):
     raise ValueError(kind)
 
 
+# One plausible defect each, of the kind a device kernel could carry: the CPU tests put the fp64 tier WITH the defect where the device's output goes
+# in the GPU tests' ratio and require it above 1 (the parity tests would notice).
+DEFECTS = {"geman_unsquared": ("geman_mcclure", (10.0, 0.5)), "tukey_without_half": ("tukey", 10.0), "tukey_cut_at_a": ("tukey", 10.0)}
+_sound_loss_rho = loss_rho
+
+
+@contextlib.contextmanager
+def defect(name):
+    """Within the block this module's loss_rho (which linearise, and through it ba6_reference.linearise, calls) carries the named defect."""
+    global loss_rho
+    kind = DEFECTS[name][0]
+
+    def bad(k, a, s):
+        r0, r1, r2 = _sound_loss_rho(k, a, s)
+        if k != kind:
+            return r0, r1, r2
+        if name == "geman_unsquared":        # sigma2 where sigma2^2 belongs
+            g2 = s.dtype.type(a[1])
+            return r0, r1 / g2, r2 / g2
+        if name == "tukey_without_half":     # rho' = v^2
+            return r0, 2 * r1, r2
+        beyond = s >= s.dtype.type(a)        # the cut at s < a in place of s <= a^2
+        return np.where(beyond, s.dtype.type(a) ** 2 / 6, r0), np.where(beyond, 0, r1), np.where(beyond, 0, r2)
+    loss_rho = bad
+    try:
+        yield
+    finally:
+        loss_rho = _sound_loss_rho
+
+
 def linearise(r, J, kind=None, a=None):
-    """dict(s, rho, H: E x 3 x 3, a: E x 3, cost, rt, Jt) of the corrected point Jacobian J~ and residual r~ (Ceres' Corrector)"""
+    """dict(s, rho, H: E x 3 x 3, a: E x 3, cost, rt, Jt) of the corrected point Jacobian J~ and residual r~ (Ceres' Corrector).  Beyond the
+    Tukey cut rho' = 0: the masked-out alpha divides by it (hence the errstate), and J~ and r~ are exactly zero."""
     s = (r * r).sum(1)
     rho0, rho1, rho2 = loss_rho(kind, a, s)
     sq = np.sqrt(rho1)
@@ -245,7 +318,7 @@ def damped(sc, lin, asm, S, radius, o=DEFAULTS):
     Cinv = np.array([_inv3(m) for m in Ct]) if len(Ct) else Ct
     Cinv[~sc["pt_active"]] = 0
     E = -S[sc["obs_cam"], :, None] * lin["H"] * S[N + sc["track_of"], None, :]
-    return {"act": act, "D2": D2, "b": b, "Bt": Bt, "Ct": Ct, "Cinv": Cinv, "E": E, "S": S}
+    return add_cholesky(sc, {"act": act, "D2": D2, "b": b, "Bt": Bt, "Ct": Ct, "Cinv": Cinv, "E": E, "S": S})
 
 
 def _inv3(m):
@@ -253,6 +326,40 @@ def _inv3(m):
                   [m[1, 2] * m[2, 0] - m[1, 0] * m[2, 2], m[0, 0] * m[2, 2] - m[0, 2] * m[2, 0], m[0, 2] * m[1, 0] - m[0, 0] * m[1, 2]],
                   [m[1, 0] * m[2, 1] - m[1, 1] * m[2, 0], m[0, 1] * m[2, 0] - m[0, 0] * m[2, 1], m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]]], dtype=m.dtype)
     return c / (m[0, 0] * c[0, 0] + m[0, 1] * c[1, 0] + m[0, 2] * c[2, 0])
+
+
+def _chol3(m):
+    L = np.zeros_like(m)
+    for j in range(3):
+        L[j, j] = np.sqrt(m[j, j] - (L[j, :j] * L[j, :j]).sum())
+        for i in range(j + 1, 3):
+            L[i, j] = (m[i, j] - (L[i, :j] * L[j, :j]).sum()) / L[j, j]
+    return L
+
+
+def c_solve(dm, t, X):
+    """C~_t^-1 X (X: 3 or 3 x k; zero for an inactive point).  fp64: the explicit inverse, as before.  hp: through the Cholesky factor of C~_t.  A
+    block that lost rank beyond the Tukey cut is held up by the damping alone and its inverse has entries of 1 / D^2, up to 1e16, next to
+    entries of order one: ROUNDED to long double that inverse is wrong by 1e-19 x 1e16 in every entry, while E~ C~^-1 E~^T needs the large part
+    (along the block's null vector, which E~ annihilates) to cancel.  The triangular solves keep each part to its own size."""
+    if "Cchol" not in dm:
+        return dm["Cinv"][t] @ X
+    L = dm["Cchol"][t]
+    if L[0, 0] == 0:
+        return np.zeros_like(X)
+    y = np.array(X, LD)
+    for i in range(3):
+        y[i] = (y[i] - sum(L[i, j] * y[j] for j in range(i))) / L[i, i]
+    for i in (2, 1, 0):
+        y[i] = (y[i] - sum(L[j, i] * y[j] for j in range(i + 1, 3))) / L[i, i]
+    return y
+
+
+def add_cholesky(sc, dm):
+    """damped()'s tail for the hp tier: the factors c_solve reads (zero for an inactive point)"""
+    if dm["S"].dtype == LD:
+        dm["Cchol"] = np.array([_chol3(m) if a else np.zeros((3, 3), LD) for m, a in zip(dm["Ct"], sc["pt_active"])]).reshape(-1, 3, 3)
+    return dm
 
 
 def full_system(sc, dm):
@@ -289,7 +396,7 @@ def schur_system(sc, dm, absolute=False):
         bp = f(dm["b"][N + t])
         for e in es:
             k = int(sc["obs_cam"][e])
-            EC = f(dm["E"][e]) @ Ci
+            EC = f(dm["E"][e]) @ Ci if absolute or "Cchol" not in dm else c_solve(dm, t, dm["E"][e].T).T   # (fp64 tier: the product it always formed)
             rhs[3 * k:3 * k + 3] += sgn * (EC @ bp)
             Mb[k] += sgn * (EC @ f(dm["E"][e]).T)
             for e2 in es:
@@ -303,7 +410,7 @@ def back_substitute(sc, dm, yc):
     N, T = len(sc["cam_est"]), len(sc["pt_est"])
     acc = dm["b"][N:].copy()
     np.add.at(acc, sc["track_of"], -np.einsum("eij,ei->ej", dm["E"], yc.reshape(N, 3)[sc["obs_cam"]]))
-    return np.einsum("tij,tj->ti", dm["Cinv"], acc)
+    return np.array([c_solve(dm, t, acc[t]) for t in range(T)]).reshape(T, 3)
 
 
 def solve_step(sc, lin, asm, S, radius, o=DEFAULTS, hp=False):
@@ -444,6 +551,14 @@ def lm_solve(sc, cam0, pts0, kind=None, a=None, hp=False, **opts):
         trace.append((last_ok, float(cost)))
 
 
+def ratio(dev, fp64, hp):
+    """max |dev - hp| / (MARGIN max(max |fp64 - hp|, u max |hp|)): the bound of the GPU tests (at most 1)"""
+    hp = np.asarray(hp, LD)
+    e_dev = float(np.abs(np.asarray(dev, LD) - hp).max())
+    e_ref = float(np.abs(np.asarray(fp64, LD) - hp).max())
+    return e_dev / (MARGIN * max(e_ref, U * float(np.abs(hp).max())))
+
+
 def decision_margin(decisions):
     """the smallest |value / threshold - 1| over the comparisons with a non-zero threshold (the model test: |value| itself must be > 0)"""
     m = np.inf
@@ -471,8 +586,11 @@ def pcg_residual_and_floor(sc, dm, yc_dev):
 
 # ---- the cases the CPU and the GPU tests share (computed once per process) ---------------------------------------------------------
 LOSS = ("huber", 10.0)   # the pipeline's loss
-CASES = {   # name: (scene, sigma of the start's perturbation, seed)
+TUKEY, GEMAN = ("tukey", 10.0), ("geman_mcclure", (10.0, 0.5))
+CASES = {   # name: (scene, sigma of the start's perturbation, seed[, loss: default LOSS])
     "a_near": ("a", 0.05, 1), "a_far": ("a", 3.0, 4), "b_near": ("b", 0.05, 1), "b_far": ("b", 2.0, 1),
+    # Tukey is not convex and the far starts are not the subject: the near start (seed 1 is scene t's own: its observations are placed at it)
+    "t_near_tukey": ("t", 0.05, 1, TUKEY), "a_near_tukey": ("a", 0.05, 1, TUKEY), "a_near_geman": ("a", 0.05, 1, GEMAN),
 }
 _CACHE = {}
 
@@ -484,20 +602,25 @@ def cached(key, make):
 
 
 def scene(name):
-    """a, b: noisy; a0, b0: noise-free"""
-    return cached(("scene", name), {"a": scene_a, "b": scene_b, "a0": lambda: scene_a(0.0, 0.0), "b0": lambda: scene_b(0.0)}[name])
+    """a, b, t: noisy; a0, b0: noise-free"""
+    return cached(("scene", name), {"a": scene_a, "b": scene_b, "t": scene_t, "a0": lambda: scene_a(0.0, 0.0), "b0": lambda: scene_b(0.0)}[name])
+
+
+def case_loss(name):
+    """(kind, a) of the case: the pipeline's loss unless the case names its own"""
+    return CASES[name][3] if len(CASES[name]) > 3 else LOSS
 
 
 def case_start(name):
-    sname, sigma, seed = CASES[name]
+    sname, sigma, seed = CASES[name][:3]
     return perturbed_start(scene(sname), sigma, sigma, seed)
 
 
 def case_solve(name, hp):
-    """lm_solve of a case with the pipeline's loss, fp64 or hp tier"""
+    """lm_solve of a case with its loss, fp64 or hp tier"""
     def make():
         c0, p0 = case_start(name)
-        return lm_solve(scene(CASES[name][0]), c0, p0, LOSS[0], LOSS[1], hp=hp)
+        return lm_solve(scene(CASES[name][0]), c0, p0, *case_loss(name), hp=hp)
     return cached(("solve", name, hp), make)
 
 

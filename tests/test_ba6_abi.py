@@ -81,6 +81,29 @@ def test_argument_checks_run_before_any_device_call():
     lib.gsfm_ba6_problem_destroy(None)
 
 
+def test_unsupported_loss_leaves_are_refused_before_the_handle_is_read():
+    """gsfm_ba6_set_loss answers status 1 for every leaf the kernels' loss_leaf_simple does not evaluate (it would fall through to `default:` -- no loss at
+    all), for a width that is not positive and for a parameter that is not finite.  The handle here is not a problem at all (a zeroed
+    buffer: no device is needed to have one): a refusal returns before anything is read from it.  Accepting Tukey and Geman-McClure writes
+    into the handle, so tests/test_gpu_ba6.py asserts that on a real problem."""
+    from globalsfmpy_amd import _abi
+    lib = _abi.load_library()
+    buf = C.create_string_buffer(1 << 16)
+    h = C.cast(buf, C.c_void_p)
+    nan, inf = float("nan"), float("inf")
+    refused = [(_abi.LOSS_CAUCHY, 10.0), (_abi.LOSS_ARCTAN, 10.0), (_abi.LOSS_TOLERANT, 10.0, 1.0), (_abi.LOSS_LONE_HALF, 10.0), (_abi.LOSS_LTWO, 10.0, 0.5),
+               (_abi.LOSS_MAGSAC, 0.02, 3, 0), (_abi.LOSS_MAGSAC + 1, 10.0), (99, 10.0), (-1, 10.0), (_abi.LOSS_OP_SCALE, 2.0),
+               (_abi.LOSS_TUKEY, 0.0), (_abi.LOSS_TUKEY, -10.0), (_abi.LOSS_TUKEY, nan), (_abi.LOSS_TUKEY, inf), (_abi.LOSS_TUKEY, 10.0, nan),
+               (_abi.LOSS_GEMAN_MCCLURE, 0.0, 0.5), (_abi.LOSS_GEMAN_MCCLURE, -1.0, 0.5), (_abi.LOSS_GEMAN_MCCLURE, 10.0, nan), (_abi.LOSS_GEMAN_MCCLURE, 10.0, inf),
+               (_abi.LOSS_GEMAN_MCCLURE, 10.0, 0.5, inf), (_abi.LOSS_HUBER, 0.0), (_abi.LOSS_SOFT_L1, -1.0)]
+    for node in refused:
+        prog, n = _abi.make_program([node])
+        assert lib.gsfm_ba6_set_loss(h, prog, n) == _abi.ERR_INVALID_ARG, node
+    prog, _ = _abi.make_program([(_abi.LOSS_TUKEY, 10.0), (_abi.LOSS_TUKEY, 10.0)])
+    assert lib.gsfm_ba6_set_loss(h, prog, 2) == _abi.ERR_INVALID_ARG and lib.gsfm_ba6_set_loss(h, prog, -1) == _abi.ERR_INVALID_ARG and lib.gsfm_ba6_set_loss(h, None, 1) == _abi.ERR_INVALID_ARG
+    assert not any(buf.raw)
+
+
 @pytest.mark.skipif(have_gpu(), reason="CPU-only behaviour")
 def test_fails_loudly_without_a_gpu():
     from globalsfmpy_amd.solver import FullBundleProblem, SolverError

@@ -136,3 +136,81 @@ def test_noise_free_scenes_end_at_the_generator_scene(sname):
     err = np.abs(got - want).max()
     print(sname, R.TERM_NAMES[out["termination"]], out["iterations"], "final cost %.3e" % out["final_cost"], "error %.3e" % err)
     assert out["termination"] in (0, 1, 2) and err <= 1e-6
+
+
+# ---- Tukey and Geman-McClure ---------------------------------------------------------------------------------------------------------
+def test_corrector_matches_the_robustified_cost_for_every_loss():
+    """J~^T r~ = rho' J^T r on the camera (6) and the point (3) side, for both Huber branches, SoftLOne, both Tukey branches and Geman-McClure."""
+    sc = R.scene("a")
+    r, Jp, Jr = R.point_observation("a", False)
+    for kind, a in (("huber", 10.0), ("softl1", 10.0), R.B.TUKEY, R.B.GEMAN):
+        with np.errstate(all="raise"):   # (finite where used: nothing the reference keeps divides by rho' = 0)
+            lin = R.linearise(r, Jp, Jr, kind, a)
+        _, rho1, _ = R.loss_rho(kind, a, lin["s"])
+        for got, J in ((np.einsum("eki,ek->ei", lin["Jc"], lin["rt"]), np.concatenate([Jr, -Jp], 2)), (np.einsum("eki,ek->ei", lin["Jp"], lin["rt"]), Jp)):
+            want = rho1[:, None] * np.einsum("eki,ek->ei", J, r)
+            assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max()
+    s = R.linearise(r, Jp, Jr, *R.B.TUKEY)["s"][sc["used"]]
+    assert (s > 100.0).any() and (s <= 100.0).any()
+
+
+@pytest.mark.parametrize("hp", [False, True])
+def test_scene_t_conditions_under_tukey(hp):
+    """What tests/test_gpu_ba6.py asserts as exact zeros holds on the reference's own lin / asm at the near start, in both tiers."""
+    sc = R.scene("t")
+    N = len(sc["cam_est"])
+    cam, trk = R.B.T_CAMERA, R.B.T_TRACK
+    lin, asm = R.point_linearisation("t", *R.B.TUKEY, hp)
+    tp = sc["track_ptr"].astype(np.int64)
+    s = lin["s"]
+    cam_rows, track_rows = np.flatnonzero(sc["obs_cam"] == cam), np.arange(tp[trk], tp[trk + 1])
+    assert len(cam_rows) == 3 and len(track_rows) == 2 and sc["used"].all()
+    assert np.all(s[cam_rows] > 100.0) and np.all(s[track_rows] > 100.0) and all(s[tp[t] + k] > 100.0 for t, k in R.B.T_SINGLE)
+    assert np.all(asm["B"][cam] == 0) and np.all(asm["C"][trk] == 0)                                  # exactly
+    assert np.all(asm["g"][[cam, N + cam, 2 * N + trk]] == 0)
+    assert np.all(lin["rho"][np.concatenate([cam_rows, track_rows])] == lin["rho"].dtype.type(100) / 6)
+    others = np.setdiff1d(np.arange(len(s)), np.concatenate([cam_rows, track_rows]))
+    assert (s[others] > 100.0).any() and (s[others] <= 100.0).any()                                   # both branches among the rest
+    n = np.sqrt(np.asarray(s, np.float64))
+    assert ((n > 9.9) & (n <= 10.0)).any() and ((n > 10.0) & (n < 10.1)).any()                        # within 1 % of the cut, on either side
+    for radius in (1e4, 1e10):
+        y, dm = R.solve_step(sc, lin, asm, R.jacobi_scale(asm), radius, hp=hp)
+        d2 = dm["S"].dtype.type(R.DEFAULTS["min_lm_diagonal"]) / dm["S"].dtype.type(radius)
+        assert np.all(dm["Bt"][cam] == d2 * np.eye(6)) and np.all(dm["Ct"][trk] == d2 * np.eye(3))    # the clamp alone, Jacobi scale 1 / (1 + 0)
+        Sc = R.schur_system(sc, dm)[0]
+        rows = slice(6 * cam, 6 * cam + 6)
+        assert np.all(Sc[rows, rows] == d2 * np.eye(6)) and np.count_nonzero(Sc[rows]) == 6           # S reduces to the damping there
+        plain = R.project_step(sc, dm, y, np.zeros_like(y), gauge=False)
+        assert np.all(plain[[cam, N + cam, 2 * N + trk]] == 0)                                        # the plain step leaves them where they are
+
+
+def test_cut_camera_and_track_of_scene_t_through_a_solve():
+    """tests/test_ba_reference.py's test of the same name: with the gauge projection camera 4 (orientation and centre) and track 5 move, without
+    it they keep their input bytes; their observations are beyond the cut at the end as at the start."""
+    sc = R.scene("t")
+    N = len(sc["cam_est"])
+    x0 = R.case_start("t_near_tukey")
+    idx = [R.B.T_CAMERA, N + R.B.T_CAMERA, 2 * N + R.B.T_TRACK]
+    for o, moved in ((R.case_solve("t_near_tukey", False), True), (R.lm_solve(sc, x0, *R.B.TUKEY, remove_gauge=0), False)):
+        asm = R.assemble(sc, R.linearise(*R.observe_np(sc, o["x"]), *R.B.TUKEY))
+        assert np.all(asm["B"][R.B.T_CAMERA] == 0) and np.all(asm["C"][R.B.T_TRACK] == 0)
+        assert o["termination"] in (0, 1, 2) and o["iterations"] >= 3
+        assert [o["x"][i].tobytes() != x0[i].tobytes() for i in idx] == [moved] * 3
+
+
+@pytest.mark.parametrize("name", sorted(R.B.DEFECTS))
+def test_a_defective_loss_exceeds_the_bound_of_the_gpu_tests(name):
+    """tests/test_ba_reference.py's test of the same name, on the full adjustment's linearisation (scene a, near start)."""
+    kind, a = R.B.DEFECTS[name]
+    sc = R.scene("a")
+    N = len(sc["cam_est"])
+    _, asm64 = R.point_linearisation("a", kind, a, False)
+    _, asmhp = R.point_linearisation("a", kind, a, True)
+    with R.B.defect(name):
+        bad = R.assemble(sc, R.linearise(*R.point_observation("a", False), kind, a))
+    worst = {"g_rot": R.ratio(bad["g"][:N], asm64["g"][:N], asmhp["g"][:N]), "g_pos": R.ratio(bad["g"][N:2 * N], asm64["g"][N:2 * N], asmhp["g"][N:2 * N]),
+             "g_point": R.ratio(bad["g"][2 * N:], asm64["g"][2 * N:], asmhp["g"][2 * N:]), "B": R.ratio(bad["B"], asm64["B"], asmhp["B"]),
+             "C": R.ratio(bad["C"], asm64["C"], asmhp["C"])}
+    print(name, worst)
+    assert min(worst.values()) > 1.0
+    assert R.ratio(asm64["g"], asm64["g"], asmhp["g"]) <= 1.0 / R.MARGIN     # (and the same arithmetic without the defect is inside it)

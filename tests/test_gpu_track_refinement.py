@@ -3,7 +3,11 @@
 are read from tests/golden/track_refinement_spread.json, which tests/test_track_refinement_reference.py recomputes and checks.
 
 The bound of test_points_and_costs_within_four_times_the_fp64_spread is 4 x spread_max = 3.0e-10; the test prints the device's worst
-deviations, which belong into the JSON's "device_measured" and DESIGN.md section 15 (not measured yet: no device was reachable)."""
+deviations, which the JSON's "device_measured" and DESIGN.md section 15 record.
+
+Tukey 10, Geman-McClure (10, 0.5) and SoftLOne 10 run on a sub-batch of 62 tracks (track_refinement_reference.make_sub_batch: the hand-placed
+tracks, per lane class the slowest and the fastest under Huber, and four tracks placed for Tukey's cut) against
+tests/golden/track_refinement_losses.json, each loss within 4 x its own spread_max."""
 import json
 import os
 
@@ -22,13 +26,15 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "track_refinement_spread.json")
 BASE = ("points", "status", "n_views", "mean_sq_err")
 OUTPUTS = BASE + ("iterations", "initial_cost", "final_cost", "termination")
 HUBER10, TRIVIAL = [(_abi.LOSS_HUBER, 10.0)], [(_abi.LOSS_TRIVIAL,)]
+GOLDEN_LOSSES = os.path.join(ROOT, "tests", "golden", "track_refinement_losses.json")
+SUB_NODES = {"tukey": [(_abi.LOSS_TUKEY, 10.0)], "geman": [(_abi.LOSS_GEMAN_MCCLURE, 10.0, 0.5)], "softl1": [(_abi.LOSS_SOFT_L1, 10.0)]}
 
 
-def run(b, refine=True, loss=HUBER10, max_num_iterations=100, **over):
+def run(b, refine=True, loss=HUBER10, max_num_iterations=100, options=None, **over):
     a = dict(b, **over)
     return solver.triangulate_tracks(a["rot_aa"], a["cam_pos"], a["intrinsics"], a["track_ptr"], a["obs_cam"], a["obs_xy"], cam_estimated=a["estimated"],
                                      min_triangulation_angle_degrees=tri.MIN_ANGLE_DEG, max_reprojection_error_pixels=tri.MAX_ERR_PX,
-                                     refine=refine, loss=loss, max_num_iterations=max_num_iterations)
+                                     refine=refine, loss=loss, max_num_iterations=max_num_iterations, **(options or {}))
 
 
 def permuted(b, perm):
@@ -185,3 +191,102 @@ def test_hand_placed_tracks(batch, device, unrefined):
     for L in (8, 9, 64, 65, 130):
         t = ref.hand_index(batch, "length_%d" % L)
         assert device["status"][t] == 0 and device["termination"][t] == ref.FUNCTION_TOLERANCE, L
+
+
+# ---- Tukey, Geman-McClure and SoftLOne on the sub-batch ----
+@pytest.fixture(scope="module")
+def gold_losses():
+    with open(GOLDEN_LOSSES) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope="module")
+def sub(batch, gold, gold_losses):
+    b = ref.make_sub_batch(batch, gold["cases"])
+    assert [int(t) for t in b["picks"]] == gold_losses["picks"] and gold_losses["hand_placed"] == list(ref.SUB_HAND_PLACED)
+    return b
+
+
+@pytest.fixture(scope="module")
+def sub_device(sub):
+    return {name: run(sub, loss=nodes) for name, nodes in SUB_NODES.items()}
+
+
+def _point(case):
+    return np.array([float.fromhex(x) for x in case["point"]])
+
+
+@pytest.mark.parametrize("name", sorted(SUB_NODES))
+def test_sub_batch_decisions_points_and_costs_per_loss(name, sub, gold_losses, sub_device):
+    doc, dev = gold_losses["losses"][name], sub_device[name]
+    cases = doc["cases"]
+    assert doc["loss"] == json.loads(json.dumps(ref.SUB_LOSSES[name])) and len(cases) == len(sub["track_ptr"]) - 1
+    flagged = [t for t, g in enumerate(cases) if g["near"]]
+    assert len(flagged) == doc["num_near"] and len(flagged) <= max(1, int(ref.MAX_FLAGGED_FRACTION * len(cases)))     # (one track: the full batch's cap)
+    wrong = [(t, g["length"], (int(dev["status"][t]), int(dev["termination"][t]), int(dev["iterations"][t])), (g["status"], g["termination"], g["iterations"]))
+             for t, g in enumerate(cases)
+             if t not in flagged and (dev["status"][t], dev["termination"][t], dev["iterations"][t]) != (g["status"], g["termination"], g["iterations"])]
+    assert not wrong, wrong
+    assert [int(x) for x in dev["n_views"]] == [g["n_views"] for g in cases]
+    bound = 4.0 * doc["spread_max"]
+    worst, worst_t, worst_c, worst_ct, n = 0.0, -1, 0.0, -1, 0
+    for t, ((oc, xy), g) in enumerate(zip(tri.track_slices(sub), cases)):
+        if g["near"] or g["status"] not in (0, 4, 5):
+            assert g["status"] in (0, 4, 5) or not dev["points"][t].any(), t
+            continue
+        d = tri.relative_deviation(dev["points"][t], _point(g), tri.origin_centroid(sub, oc))
+        n += 1
+        if d > worst:
+            worst, worst_t = d, t
+        if g["final_cost"] > 1e-12:
+            dc = ref.relative_cost_deviation(dev["final_cost"][t], g["final_cost"])
+            if dc > worst_c:
+                worst_c, worst_ct = dc, t
+        assert dev["final_cost"][t] <= dev["initial_cost"][t], t
+    print("%s: %d tracks left out, %d compared, points worst %.3e at track %d (length %d); final costs worst %.3e at track %d (length %d); bound %.3e = 4 x spread_max %.3e"
+          % (name, len(flagged), n, worst, worst_t, cases[worst_t]["length"], worst_c, worst_ct, cases[worst_ct]["length"], bound, doc["spread_max"]))
+    assert n >= 50
+    assert worst <= bound, (worst_t, worst, bound)
+    assert worst_c <= bound, (worst_ct, worst_c, bound)
+
+
+def test_tukey_on_the_tracks_placed_for_its_cut(sub, gold_losses, sub_device):
+    dev = sub_device["tukey"]
+    # every observation beyond the cut at the midpoint: g = 0, no iteration, the midpoint's bytes
+    t = ref.sub_index(sub, "all_beyond_the_tukey_cut")
+    mid = run(sub, refine=False)
+    assert dev["iterations"][t] == 0 and dev["termination"][t] == ref.GRADIENT_TOLERANCE and dev["final_cost"][t] == dev["initial_cost"][t] > 0
+    assert dev["points"][t].tobytes() == mid["points"][t].tobytes() and dev["status"][t] == mid["status"][t]
+    assert sub_device["geman"]["iterations"][t] > 0
+    # one observation 30 px off, exact inliers: it weighs nothing under Tukey.  Tukey's point is far from Huber's, and with both refinements
+    # run to their minimiser (SUB_CONVERGED; at the default tolerances they stop a step short of it) Tukey's point of the track WITH the
+    # outlier is the trivial loss's point of the track WITHOUT it within 4 x spread_max, each also that close to its 50-digit point
+    t = ref.sub_index(sub, "one_beyond_the_cut")
+    oc, xy = tri.track_slices(sub)[t]
+    huber = run(permuted(sub, np.array([t])), loss=HUBER10)
+    assert dev["status"][t] == 0 and huber["status"][0] == 0 and np.linalg.norm(dev["points"][t] - huber["points"][0]) > 1e-3
+    oc1, xy1 = ref.without_observation(oc, xy, ref.SUB_OUTLIER_PLACE)
+    alone = dict(sub, track_ptr=np.array([0, len(oc1)], dtype=np.uint64), obs_cam=np.ascontiguousarray(oc1), obs_xy=np.ascontiguousarray(xy1))
+    with_it = run(permuted(sub, np.array([t])), loss=SUB_NODES["tukey"], options=ref.SUB_CONVERGED)
+    without = run(alone, loss=TRIVIAL, options=ref.SUB_CONVERGED)
+    assert with_it["status"][0] == 0 and without["status"][0] == 0
+    bound = 4.0 * gold_losses["losses"]["tukey"]["spread_max"]
+    centroid = tri.origin_centroid(sub, oc)
+    want = {k: np.array([float.fromhex(x) for x in v]) for k, v in gold_losses["without_the_outlier"].items()}
+    devs = {"Tukey with / trivial without": tri.relative_deviation(with_it["points"][0], without["points"][0], centroid),
+            "Tukey with / its 50 digits": tri.relative_deviation(with_it["points"][0], want["tukey_with_it"], centroid),
+            "trivial without / its 50 digits": tri.relative_deviation(without["points"][0], want["trivial"], centroid)}
+    print("one_beyond_the_cut, converged: %s; bound %.3e; iterations %d / %d" % ("  ".join("%s %.3e" % kv for kv in devs.items()), bound,
+                                                                               with_it["iterations"][0], without["iterations"][0]))
+    assert max(devs.values()) <= bound, devs
+    assert dev["status"][ref.sub_index(sub, "at_the_cut")] == 0 and dev["status"][ref.sub_index(sub, "length_65_mixed")] == 0
+
+
+def test_tukey_two_calls_a_permutation_and_tracks_alone_return_the_same_bytes(sub, sub_device):
+    dev, nodes = sub_device["tukey"], SUB_NODES["tukey"]
+    assert same_bytes(run(sub, loss=nodes), dev)
+    perm = np.random.Generator(np.random.PCG64(6)).permutation(len(sub["track_ptr"]) - 1)
+    assert same_bytes(run(permuted(sub, perm), loss=nodes), dev, rows=perm)
+    picks = [ref.sub_index(sub, k) for k in ref.SUB_HAND_PLACED] + [int(np.argmax(dev["iterations"]))]
+    for t in picks:
+        assert same_bytes(run(permuted(sub, np.array([t])), loss=nodes), dev, rows=np.array([t])), t

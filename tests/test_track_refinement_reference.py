@@ -16,6 +16,7 @@ import triangulation_reference as tri
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "track_refinement_spread.json")
+GOLDEN_LOSSES = os.path.join(ROOT, "tests", "golden", "track_refinement_losses.json")
 COS, MAX_SQ = tri.cos_min_angle(), tri.MAX_ERR_PX ** 2
 
 
@@ -132,6 +133,195 @@ def test_golden_file_matches_a_recomputation(recomputed):
     assert 0.25 * recomputed["spread_max"] <= got["spread_max"] <= 4.0 * recomputed["spread_max"]   # rounding errors: another libm reorders them
 
 
+# ---- Tukey, Geman-McClure and SoftLOne on the sub-batch ----
+@pytest.fixture(scope="module")
+def sub(batch, recomputed):
+    return ref.make_sub_batch(batch, recomputed["cases"])
+
+
+@pytest.fixture(scope="module")
+def sub_recomputed(sub):
+    return ref.compute_sub_golden(sub)
+
+
+def _hexpoint(p):
+    return np.array([float.fromhex(x) for x in p])
+
+
+@pytest.mark.parametrize("ops", [ref._Fp64, ref._Mp])
+def test_loss_rows_against_the_loss_classes(ops):
+    """_rho on either number type against loss_functions' classes (pinned to the reference project's vectors by tests/test_oracle_golden.py) at
+    s = 0, inside, at the cut, beyond.  Bound: a few roundings of float64 -- for Tukey of each function's largest value (the class forms
+    v = 1 - s / a^2 and 1 - v^3 in float64, absolute errors of u that the 50-digit tier does not share), else of the value."""
+    import mpmath
+    from globalsfmpy_amd import loss_functions as LF
+    u = 2.0 ** -53
+    with mpmath.workdps(tri.MP_DPS):
+        for loss, cls, floor in ((ref.TUKEY10, LF.TukeyLoss(10.0), (100.0 / 6, 0.5, 0.01)), (ref.GEMAN10, LF.GemanMcClureLoss(10.0, 0.5), (0.0, 0.0, 0.0)),
+                                 (ref.SOFTL1_10, LF.SoftLOneLoss(10.0), (0.0, 0.0, 0.0)), (ref.HUBER10, LF.HuberLoss(10.0), (0.0, 0.0, 0.0))):
+            for s in (0.0, 1e-3, 37.0, 99.999, 100.0, 100.0 + 1e-9, 2500.0, 1e8):
+                want = [0.0, 0.0, 0.0]
+                cls.Evaluate(s, want)
+                got = ref._rho(loss, ops.num(s), ops)
+                for k in range(3):
+                    # (SoftLOne's rho = 2 b (sqrt(1 + s / b) - 1) cancels at small s in float64: an absolute 2 b u)
+                    tol = 8 * u * max(abs(want[k]), floor[k], 200.0 if (loss is ref.SOFTL1_10 and k == 0) else 0.0)
+                    assert abs(float(got[k]) - want[k]) <= tol, (loss, s, k, float(got[k]), want[k])
+        t = ref._rho(ref.TUKEY10, ops.num(100.0 + 1e-9), ops)
+        assert t[1] == 0 and t[2] == 0 and float(t[0]) == 100.0 / 6
+
+
+@pytest.mark.parametrize("ops", [ref._Fp64, ref._Mp])
+def test_corrected_gradient_is_the_gradient_of_the_robustified_cost(sub, ops):
+    """sum J~^T r~ = sum rho' J^T r on both number types, for every loss, at the midpoint of tracks that have observations on both sides of
+    the Tukey cut (J^T r and s per observation from the trivial-loss pass of a one-observation track)."""
+    import mpmath
+    sl = tri.track_slices(sub)
+    with mpmath.workdps(tri.MP_DPS), np.errstate(all="ignore"):
+        for name in ("one_beyond_the_cut", "length_65_mixed", "at_the_cut"):
+            oc, xy = sl[ref.sub_index(sub, name)]
+            X = [ops.num(v) for v in ref.refine_fp64(sub, oc, xy, COS, MAX_SQ, refine=False).point]
+            singles = [ref._Track(sub, oc[k:k + 1], xy[k:k + 1], ops).passes(X, ref.TRIVIAL, None) for k in range(len(oc))]
+            for loss in (ref.HUBER10, ref.SOFTL1_10, ref.TUKEY10, ref.GEMAN10):
+                got = ref._Track(sub, oc, xy, ops).passes(X, loss, None)
+                rho = [ref._rho(loss, 2 * one[9], ops) for one in singles]
+                if loss is ref.TUKEY10 and name != "at_the_cut":
+                    assert any(r[1] == 0 for r in rho) and any(r[1] > 0 for r in rho)
+                for c in range(3):
+                    want = sum(r[1] * one[6 + c] for r, one in zip(rho, singles))
+                    scale = sum(abs(r[1] * one[6 + c]) for r, one in zip(rho, singles))
+                    assert abs(float(got[6 + c] - want)) <= 1e-12 * float(scale), (name, loss, c)
+                assert abs(float(got[9] - sum(r[0] for r in rho) / 2)) <= 1e-12 * float(got[9])
+
+
+def test_sub_batch_holds_its_tracks_and_the_reference_flags_none(batch, sub, sub_recomputed):
+    lengths = np.diff(sub["track_ptr"].astype(np.int64))
+    assert len(lengths) == len(ref.HAND_PLACED) + 6 * ref.SUB_PER_CLASS + len(ref.SUB_HAND_PLACED) == 62
+    assert sub["picks"][:len(ref.HAND_PLACED)] == [ref.hand_index(batch, k) for k in ref.HAND_PLACED]
+    assert {tri.lane_class(n) for n in lengths[len(ref.HAND_PLACED):sub["n_picked"]]} == {4, 16, 64}
+    assert [int(lengths[ref.sub_index(sub, k)]) for k in ref.SUB_HAND_PLACED] == [6, 8, 8, 65]
+    for name, doc in sub_recomputed["losses"].items():
+        cases = doc["cases"]
+        print("%s: flagged %d of %d, spread_max %.3e, iterations max %d" % (name, doc["num_near"], len(cases), doc["spread_max"], max(cs["iterations"] for cs in cases)))
+        # the cap of the full batch -- at most MAX_FLAGGED_FRACTION, here one track -- holds, and the sub-batch was chosen so that none is flagged
+        assert doc["num_near"] == sum(cs["near"] for cs in cases) == 0 and doc["num_near"] <= ref.MAX_FLAGGED_FRACTION * len(cases) + 1
+        assert all(all(cs["fp64_agrees"]) for cs in cases)
+        assert 0 < doc["spread_max"] < 1e-9
+        sl = tri.track_slices(sub)
+        for t, cs in enumerate(cases):      # the header's order, which the 8 sequential orders do not sample
+            lane = ref.refine_fp64(sub, *sl[t], COS, MAX_SQ, loss=ref.SUB_LOSSES[name], order="lane")
+            assert (lane.status, lane.termination, lane.iterations) == (cs["status"], cs["termination"], cs["iterations"]), (name, t)
+        for cs in cases:
+            if cs["termination"] >= 0:
+                assert cs["final_cost"] <= cs["initial_cost"]
+
+
+def test_hand_placed_tracks_of_the_sub_batch(sub, sub_recomputed):
+    sl = tri.track_slices(sub)
+    tukey, cases = sub_recomputed["losses"]["tukey"]["cases"], None
+
+    def residual_norms(name, X):
+        oc, xy = sl[ref.sub_index(sub, name)]
+        return np.array([np.linalg.norm(tri._project(sub, c, X) - p) for c, p in zip(oc, xy)])
+    # every observation beyond the cut at the midpoint: rho' = 0 everywhere, g = 0, the refinement stops before its first iteration
+    t = ref.sub_index(sub, "all_beyond_the_tukey_cut")
+    mid = ref.refine_mp(sub, *sl[t], COS, MAX_SQ, refine=False)
+    assert residual_norms("all_beyond_the_tukey_cut", mid.point).min() > 12.0
+    cs = tukey[t]
+    assert (cs["iterations"], cs["termination"]) == (0, ref.GRADIENT_TOLERANCE) and cs["final_cost"] == cs["initial_cost"] == len(sl[t][0]) * 100.0 / 12
+    assert np.array_equal(_hexpoint(cs["point"]), mid.point) and cs["status"] == mid.status
+    assert sub_recomputed["losses"]["geman"]["cases"][t]["iterations"] > 0        # (a loss without a cut moves it)
+    # one observation 30 px off, exact inliers: beyond the cut at the refined point it weighs nothing, so Tukey's point is more than 1e-3 from
+    # Huber's and -- both run to their minimiser (SUB_CONVERGED) -- it IS the trivial loss's point of the track without that observation, within
+    # the spread: in 50 digits, and in fp64 in the track's and in the kernel's order.  (At the default tolerances the runs stop at a relative
+    # cost change of 1e-6, a step short of the minimiser: 2e-9 apart.)  A weight of 1e-4 leaking through the cut would move the point by 1e-6.
+    t = ref.sub_index(sub, "one_beyond_the_cut")
+    oc, xy = sl[t]
+    oc1, xy1 = ref.without_observation(oc, xy, ref.SUB_OUTLIER_PLACE)
+    centroid = tri.origin_centroid(sub, oc)
+    pt = _hexpoint(tukey[t]["point"])
+    norms = residual_norms("one_beyond_the_cut", pt)
+    assert norms[ref.SUB_OUTLIER_PLACE] > 12.0 and np.delete(norms, ref.SUB_OUTLIER_PLACE).max() < 1e-3
+    huber = ref.refine_mp(sub, oc, xy, COS, MAX_SQ, loss=ref.HUBER10).point
+    assert np.linalg.norm(pt - huber) > 1e-3
+    bound = 4.0 * sub_recomputed["losses"]["tukey"]["spread_max"]
+    with_it, without = (_hexpoint(sub_recomputed["without_the_outlier"][k]) for k in ("tukey_with_it", "trivial"))
+    worst = tri.relative_deviation(with_it, without, centroid)
+    for order in (None, "lane"):
+        a = ref.refine_fp64(sub, oc, xy, COS, MAX_SQ, ref.TUKEY10, ref.SUB_CONVERGED, order=order)
+        b = ref.refine_fp64(sub, oc1, xy1, COS, MAX_SQ, ref.TRIVIAL, ref.SUB_CONVERGED, order=order)
+        assert a.status == b.status == 0
+        worst = max(worst, tri.relative_deviation(a.point, b.point, centroid), tri.relative_deviation(a.point, with_it, centroid),
+                    tri.relative_deviation(b.point, without, centroid))
+    print("one_beyond_the_cut: Tukey with the outlier against the trivial loss without it, worst deviation %.3e (bound %.3e)" % (worst, bound))
+    assert worst <= bound
+    # one observation within 1 % of the cut at the refined point
+    t = ref.sub_index(sub, "at_the_cut")
+    norms = residual_norms("at_the_cut", _hexpoint(tukey[t]["point"]))
+    assert ((norms > 9.9) & (norms < 10.1)).sum() == 1 and tukey[t]["status"] == 0
+    # five of 65 beyond the cut, in the first pass of the lanes and in the second
+    t = ref.sub_index(sub, "length_65_mixed")
+    norms = residual_norms("length_65_mixed", _hexpoint(tukey[t]["point"]))
+    assert sorted(np.flatnonzero(norms > 10.0)) == list(ref.SUB_MIXED_PLACES) and tukey[t]["status"] == 0 and tukey[t]["iterations"] > 0
+
+
+def test_losses_golden_file_matches_a_recomputation(sub_recomputed):
+    with open(GOLDEN_LOSSES) as f:
+        got = json.load(f)
+    for k in ("sub_seed", "picks", "hand_placed"):          # ("device_measured" is what a device run printed: not compared)
+        assert got[k] == sub_recomputed[k], k
+    assert sorted(got["losses"]) == sorted(sub_recomputed["losses"])
+    for name in got["losses"]:
+        g, r = got["losses"][name], sub_recomputed["losses"][name]
+        for k in ("hand_seed", "batch_seed", "orders", "mp_dps", "loss", "min_angle_degrees", "max_error_pixels", "num_near"):
+            assert g[k] == r[k], (name, k)
+        assert len(g["cases"]) == len(r["cases"])
+        for t, (a, b) in enumerate(zip(g["cases"], r["cases"])):
+            for k in ("length", "status", "n_views", "iterations", "termination", "near"):
+                assert a[k] == b[k], (name, t, k, a[k], b[k])
+            pa, pb = _hexpoint(a["point"]), _hexpoint(b["point"])
+            assert np.max(np.abs(pa - pb)) <= 4 * 2.0 ** -53 * max(1.0, np.max(np.abs(pb))), (name, t)
+            assert abs(a["final_cost"] - b["final_cost"]) <= 4 * 2.0 ** -53 * abs(b["final_cost"]), (name, t)
+        assert g["spread_max"] == max(cs["spread"] for cs in g["cases"])
+        assert 0.25 * r["spread_max"] <= g["spread_max"] <= 4.0 * r["spread_max"]
+    for k, v in got["without_the_outlier"].items():
+        pa, pb = _hexpoint(v), _hexpoint(sub_recomputed["without_the_outlier"][k])
+        assert np.max(np.abs(pa - pb)) <= 4 * 2.0 ** -53 * max(1.0, np.max(np.abs(pb))), k
+
+
+@pytest.mark.parametrize("defect", ["geman_unsquared", "tukey_without_half", "tukey_cut_at_a"])
+def test_a_defective_loss_exceeds_the_bound_of_the_device_test(sub, sub_recomputed, defect, monkeypatch):
+    """The device test's bound notices each defect: the fp64 restatement WITH it, put where the device's output goes, takes other decisions
+    than the 50-digit tier or leaves 4 x spread_max on most of the sub-batch's refined tracks."""
+    sound = ref._rho
+    name = "geman" if defect.startswith("geman") else "tukey"
+
+    def bad(loss, s, ops):
+        r0, r1, r2 = sound(loss, s, ops)
+        if loss[0] == "geman_mcclure" and defect == "geman_unsquared":
+            return r0, r1 / ops.num(loss[1][1]), r2 / ops.num(loss[1][1])     # sigma2 where sigma2^2 belongs
+        if loss[0] == "tukey" and defect == "tukey_without_half":
+            return r0, 2 * r1, r2
+        if loss[0] == "tukey" and defect == "tukey_cut_at_a" and s >= ops.num(loss[1]):     # s < a in place of s <= a^2
+            return ops.num(loss[1]) ** 2 / 6, ops.num(0.0), ops.num(0.0)
+        return r0, r1, r2
+    monkeypatch.setattr(ref, "_rho", bad)
+    doc = sub_recomputed["losses"][name]
+    bound = 4.0 * doc["spread_max"]
+    caught = refined = 0
+    for (oc, xy), g in zip(tri.track_slices(sub), doc["cases"]):
+        if g["status"] not in (0, 4, 5) or g["iterations"] == 0:
+            continue
+        refined += 1
+        lo = ref.refine_fp64(sub, oc, xy, COS, MAX_SQ, ref.SUB_LOSSES[name], order="lane")
+        flipped = (lo.status, lo.termination, lo.iterations) != (g["status"], g["termination"], g["iterations"])
+        dev = tri.relative_deviation(lo.point, _hexpoint(g["point"]), tri.origin_centroid(sub, oc))
+        dc = ref.relative_cost_deviation(lo.final_cost, g["final_cost"])
+        caught += bool(flipped or dev > bound or dc > bound)
+    print(defect, "caught on %d of %d refined tracks" % (caught, refined))
+    assert refined >= 40 and caught >= 0.5 * refined
+
+
 # ---- the C entry point on a machine without a device ----
 def _call_args(b, options=None, loss=((_abi.LOSS_HUBER, 10.0),)):
     dp, u32, i32, u64 = C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
@@ -184,6 +374,19 @@ def test_invalid_arguments_are_rejected_before_any_device_call(batch):
         setattr(o, field, bad)
         args, _ = _call_args(batch, options=o)
         assert lib.gsfm_tracks_triangulate_refine(*args) == _abi.ERR_INVALID_ARG, field
+    # every leaf the kernel's loss_leaf_simple does not evaluate (it would run as no loss at all), a width that is not positive, a parameter
+    # that is not finite: refused; Tukey and Geman-McClure with a positive width pass the checks (what comes back is the device's answer)
+    nan, inf = float("nan"), float("inf")
+    for node in ((_abi.LOSS_CAUCHY, 10.0), (_abi.LOSS_ARCTAN, 10.0), (_abi.LOSS_TOLERANT, 10.0, 1.0), (_abi.LOSS_LONE_HALF, 10.0), (_abi.LOSS_LTWO, 10.0, 0.5),
+                 (_abi.LOSS_MAGSAC, 0.02, 9, 0), (_abi.LOSS_MAGSAC + 1, 10.0), (-1, 10.0), (_abi.LOSS_OP_COMPOSE, 10.0),
+                 (_abi.LOSS_TUKEY, 0.0), (_abi.LOSS_TUKEY, -10.0), (_abi.LOSS_TUKEY, nan), (_abi.LOSS_TUKEY, inf), (_abi.LOSS_TUKEY, 10.0, nan),
+                 (_abi.LOSS_GEMAN_MCCLURE, 0.0, 0.5), (_abi.LOSS_GEMAN_MCCLURE, -1.0, 0.5), (_abi.LOSS_GEMAN_MCCLURE, 10.0, nan), (_abi.LOSS_GEMAN_MCCLURE, 10.0, inf),
+                 (_abi.LOSS_SOFT_L1, 0.0)):
+        args, _ = _call_args(batch, loss=(node,))
+        assert lib.gsfm_tracks_triangulate_refine(*args) == _abi.ERR_INVALID_ARG, node
+    for node in ((_abi.LOSS_TUKEY, 10.0), (_abi.LOSS_GEMAN_MCCLURE, 10.0, 0.5), (_abi.LOSS_SOFT_L1, 10.0), (_abi.LOSS_TRIVIAL,)):
+        args, _ = _call_args(batch, loss=(node,))
+        assert lib.gsfm_tracks_triangulate_refine(*args) in (_abi.OK, _abi.ERR_NO_DEVICE), node
     cam = batch["obs_cam"].copy()
     cam[17] = batch["n_cams"]
     args = list(good)

@@ -6,6 +6,7 @@ may hinge on rounding.  The fp64 version takes a summation order: None (the trac
 or "lane" -- the header's order (lane stride G, then the xor butterfly).  Also here: the parity batch, triangulation_reference.make_batch()
 plus hand-placed tracks, and the golden file's content."""
 import collections
+import json
 import math
 
 import mpmath
@@ -18,6 +19,7 @@ FUNCTION_TOLERANCE, GRADIENT_TOLERANCE, PARAMETER_TOLERANCE, NO_CONVERGENCE, FAI
 OPTIONS = {"max_num_iterations": 100, "function_tolerance": 1e-6, "gradient_tolerance": 1e-10, "parameter_tolerance": 1e-8,
            "min_relative_decrease": 1e-3, "initial_radius": 1e4, "max_radius": 1e12, "min_radius": 1e-32}
 TRIVIAL, HUBER10 = ("trivial", 0.0), ("huber", 10.0)     # Theia's TRIVIAL and the reference YAML's HUBER with its width
+SOFTL1_10, TUKEY10, GEMAN10 = ("softl1", 10.0), ("tukey", 10.0), ("geman_mcclure", (10.0, 0.5))     # the other leaves the entry takes
 NEAR_REL = 1e-9
 DBL_MIN = 2.2250738585072014e-308
 
@@ -111,18 +113,35 @@ def _cholesky_solve(M, q, ops):
 
 
 def _rho(loss, s, ops):
+    """(rho, rho', rho'') at s: Ceres' formulas as position_hp_reference.loss_rho states them; Geman-McClure's second parameter is
+    loss_functions.GemanMcClureLoss's sigma2 and enters as it stands"""
     kind, a = loss
     one, zero = ops.num(1.0), ops.num(0.0)
+    if kind == "trivial":
+        return s, one, zero
+    params = tuple(a) if isinstance(a, (tuple, list)) else (a,)
+    a = ops.num(params[0])
+    b = a * a
     if kind == "huber":
-        a = ops.num(a)
-        b = a * a
         if s > b:
             r = ops.sqrt(s)
             r1 = max(a / r, ops.num(DBL_MIN))
             return 2 * a * r - b, r1, -r1 / (2 * s)
-    else:
-        assert kind == "trivial"
-    return s, one, zero
+        return s, one, zero
+    if kind == "softl1":
+        sm = 1 + s / b
+        tmp = ops.sqrt(sm)
+        r1 = max(1 / tmp, ops.num(DBL_MIN))
+        return 2 * b * (tmp - 1), r1, -(r1 / b) / (2 * sm)
+    if kind == "tukey":
+        if s <= b:
+            v = 1 - s / b
+            return b / 6 * (1 - v * v * v), v * v / 2, -v / b
+        return b / 6, zero, zero
+    assert kind == "geman_mcclure"
+    g2 = ops.num(params[1])
+    t = s / b + g2
+    return b * g2 * s / (2 * (s + b * g2)), g2 * g2 / (2 * t * t), -(g2 * g2) / (b * t * t * t)
 
 
 class _Track:
@@ -385,6 +404,117 @@ def hand_index(batch, name):
     return batch["n_base"] + HAND_PLACED.index(name)
 
 
+# ---------------------------------- the sub-batch of the other losses ----
+SUB_SEED = 9108
+SUB_PER_CLASS = 8          # per lane class (4, 16, 64): the base tracks with the most and with the fewest iterations under Huber
+SUB_HAND_PLACED = ("all_beyond_the_tukey_cut", "one_beyond_the_cut", "at_the_cut", "length_65_mixed")
+SUB_LOSSES = {"tukey": TUKEY10, "geman": GEMAN10, "softl1": SOFTL1_10}
+SUB_OUTLIER_PLACE = 3      # one_beyond_the_cut: the observation 30 px off
+# options at which a refinement runs to its minimiser instead of stopping at a relative cost change of 1e-6: it ends on the gradient, on a step
+# of 1e-14 |x|, or at the iteration cap with steps at rounding level
+SUB_CONVERGED = {"function_tolerance": 0.0, "parameter_tolerance": 1e-14}
+SUB_MIXED_PLACES = (0, 13, 31, 47, 64)     # length_65_mixed: the observations 30 px off, spread over the 64 lanes and the second pass
+
+
+def _append_tracks(b, tracks):
+    out = dict(b)
+    out["obs_cam"] = np.concatenate([b["obs_cam"], np.array([c for t in tracks for c, _ in t], dtype=np.uint32)])
+    out["obs_xy"] = np.vstack([b["obs_xy"], np.array([xy for t in tracks for _, xy in t])])
+    out["track_ptr"] = np.concatenate([b["track_ptr"], b["track_ptr"][-1] + np.cumsum([len(t) for t in tracks]).astype(np.uint64)]).astype(np.uint64)
+    return out
+
+
+def sub_batch_picks(batch, huber_cases):
+    """the tracks of the batch that the sub-batch keeps: HAND_PLACED, and per lane class the SUB_PER_CLASS base tracks with the most and the
+    fewest iterations in the Huber golden (ties by index; a track that is not refined there -- status 1, 2, 3 -- does not count)"""
+    lengths = np.diff(batch["track_ptr"].astype(np.int64))
+    picks = [hand_index(batch, k) for k in HAND_PLACED]
+    for G in (4, 16, 64):
+        of_class = sorted((huber_cases[t]["iterations"], t) for t in range(batch["n_base"])
+                          if tri.lane_class(lengths[t]) == G and huber_cases[t]["termination"] >= 0 and not huber_cases[t]["near"])
+        assert len(of_class) >= 2 * SUB_PER_CLASS, (G, len(of_class))
+        picks += [t for _, t in of_class[:SUB_PER_CLASS]] + [t for _, t in of_class[-SUB_PER_CLASS:]]
+    return picks
+
+
+def make_sub_batch(batch, huber_cases):
+    """About sixty tracks for the losses of SUB_LOSSES: sub_batch_picks() of the batch, then the tracks of SUB_HAND_PLACED.  "picks" are the
+    indices in the batch, "n_picked" their count."""
+    picks = sub_batch_picks(batch, huber_cases)
+    ptr = batch["track_ptr"].astype(np.int64)
+    rows = np.concatenate([np.arange(ptr[t], ptr[t + 1], dtype=np.int64) for t in picks])
+    sub = dict(batch, track_ptr=np.concatenate([[0], np.cumsum(np.diff(ptr)[picks])]).astype(np.uint64), obs_cam=batch["obs_cam"][rows],
+               obs_xy=batch["obs_xy"][rows])
+    rng = np.random.Generator(np.random.PCG64(SUB_SEED))
+
+    def seen(cam_list, X, noise):
+        return [(c, tri._project(batch, c, X) + noise * rng.standard_normal(2)) for c in cam_list]
+    P = np.array([0.4, -0.3, 0.6])
+    cams_p = _estimated_in_front(batch, P)
+    tracks = []
+    # every observation 40 px off in one image direction: cameras that look at P from different sides disagree about it, and the midpoint
+    # leaves every one of them beyond a cut of 10 px (tests/test_track_refinement_reference.py checks that)
+    tracks.append([(c, xy + np.array([40.0, 0.0])) for c, xy in seen(cams_p[:6], P, 0.5)])
+    # make_batch()'s outlier construction with EXACT inliers: then the trivial loss without the outlier and Tukey with it (the outlier beyond
+    # the cut, the inliers' weights (1 - s / a^2)^2 / 2 equal to 1e-20) have one minimiser, P, and at SUB_CONVERGED's tolerances both runs reach it
+    one = seen(cams_p[:8], P, 0.0)
+    one[SUB_OUTLIER_PLACE] = (one[SUB_OUTLIER_PLACE][0], one[SUB_OUTLIER_PLACE][1] + np.array([30.0, 0.0]))
+    tracks.append(one)
+    # one observation whose residual AT THE REFINED POINT (Tukey 10) is 9.95 px: placed by a secant iteration on its offset (the
+    # observation weighs next to nothing there, so the refined point hardly follows it)
+    at = seen(cams_p[10:18], P, 0.5)
+    c, max_sq = tri.cos_min_angle(), tri.MAX_ERR_PX ** 2
+    base_xy, k_at = at[2][1].copy(), 2
+
+    def residual_norm(off):
+        at[k_at] = (at[k_at][0], base_xy + np.array([off, 0.0]))
+        oc, xy = np.array([cc for cc, _ in at], dtype=np.uint32), np.array([v for _, v in at])
+        X = refine_fp64(batch, oc, xy, c, max_sq, TUKEY10).point
+        return float(np.linalg.norm(tri._project(batch, at[k_at][0], X) - at[k_at][1]))
+    o0, o1 = 9.0, 10.0
+    f0, f1 = residual_norm(o0) - 9.95, residual_norm(o1) - 9.95
+    for _ in range(20):
+        if abs(f1) < 1e-3:
+            break
+        o0, o1, f0 = o1, o1 - f1 * (o1 - o0) / (f1 - f0), f1
+        f1 = residual_norm(o1) - 9.95
+    assert abs(f1) < 1e-3, f1
+    tracks.append(list(at))
+    X = rng.uniform(-1.5, 1.5, 3)
+    ok = _estimated_in_front(batch, X)
+    mixed = seen([ok[k % len(ok)] for k in range(65)], X, 0.5)
+    for k in SUB_MIXED_PLACES:
+        mixed[k] = (mixed[k][0], mixed[k][1] + np.array([0.0, 30.0]))
+    tracks.append(mixed)
+    assert len(tracks) == len(SUB_HAND_PLACED)
+    out = _append_tracks(sub, tracks)
+    out["picks"], out["n_picked"] = picks, len(picks)
+    return out
+
+
+def sub_index(sub, name):
+    return sub["n_picked"] + SUB_HAND_PLACED.index(name)
+
+
+def without_observation(oc, xy, place):
+    keep = [k for k in range(len(oc)) if k != place]
+    return oc[keep], xy[keep]
+
+
+def compute_sub_golden(sub):
+    """compute_golden() of the sub-batch per loss of SUB_LOSSES, and the 50-digit point of one_beyond_the_cut WITHOUT its outlier under the
+    trivial loss and of the track WITH it under Tukey, both at SUB_CONVERGED's tolerances (what Tukey has to reproduce: the observation beyond the
+    cut weighs nothing)"""
+    doc = {"sub_seed": SUB_SEED, "picks": [int(t) for t in sub["picks"]], "hand_placed": list(SUB_HAND_PLACED),
+           "losses": {name: compute_golden(sub, loss) for name, loss in SUB_LOSSES.items()}}
+    oc, xy = without_observation(*tri.track_slices(sub)[sub_index(sub, "one_beyond_the_cut")], SUB_OUTLIER_PLACE)
+    c, max_sq = tri.cos_min_angle(), tri.MAX_ERR_PX ** 2
+    full = tri.track_slices(sub)[sub_index(sub, "one_beyond_the_cut")]
+    doc["without_the_outlier"] = {"trivial": [float(x).hex() for x in refine_mp(sub, oc, xy, c, max_sq, TRIVIAL, SUB_CONVERGED).point],
+                                  "tukey_with_it": [float(x).hex() for x in refine_mp(sub, *full, c, max_sq, TUKEY10, SUB_CONVERGED).point]}
+    return doc
+
+
 # ------------------------------------------------------ the golden file ----
 ORDERS = 8
 
@@ -416,6 +546,6 @@ def compute_golden(batch=None, loss=HUBER10):
                 if float(hp.final_cost) > 1e-12:          # below: the cost is the rounding of the pixels, not a quantity to agree on
                     case["spread"] = max(case["spread"], relative_cost_deviation(lo.final_cost, hp.final_cost))
         cases.append(case)
-    return {"hand_seed": HAND_SEED, "batch_seed": tri.BATCH_SEED, "orders": ORDERS, "mp_dps": tri.MP_DPS, "loss": list(loss),
+    return {"hand_seed": HAND_SEED, "batch_seed": tri.BATCH_SEED, "orders": ORDERS, "mp_dps": tri.MP_DPS, "loss": json.loads(json.dumps(loss)),
             "min_angle_degrees": tri.MIN_ANGLE_DEG, "max_error_pixels": tri.MAX_ERR_PX, "num_near": sum(cs["near"] for cs in cases),
             "spread_max": max(cs["spread"] for cs in cases), "cases": cases}
