@@ -21,6 +21,17 @@ struct FlatLayout {
   }
 };
 
+// A problem's slab (solver_pos.hpp, solver_ba.hpp, solver_ba6.hpp): take(ptr, count) lays the array out and, given the committed slab,
+// points ptr into it; the same list of takes serves both passes
+struct SlabTake {
+  FlatLayout L;
+  char* slab;
+  template <typename E> void operator()(E*& ptr, size_t count) {
+    const Slot<E> slot = L.take<E>(count);
+    if (slab) ptr = (E*)(slab + slot.off);
+  }
+};
+
 }  // namespace
 
 #ifdef __HIPCC__

@@ -1,6 +1,5 @@
-// Host side of camera-position estimation (include/gsfm_pos.h): problem assembly, the Levenberg-Marquardt loop with Ceres 1.14's
-// TrustRegionMinimizer + LevenbergMarquardtStrategy rules (restated from oracle/ref_solver.cpp::lm_solve for Euclidean parameters; the radius
-// rule is trust_region.hpp's), exact steps by the dense tiled Cholesky (solver_dense.hpp, enqueue_chol_solve) or block-Jacobi PCG.  The
+// Host side of camera-position estimation (include/gsfm_pos.h): problem assembly, the operations that lm_loop.hpp's Levenberg-Marquardt loop
+// and PCG driver run (PosLm, pos_pcg), exact steps by the dense tiled Cholesky (solver_dense.hpp, enqueue_chol_solve) or block-Jacobi PCG.  The
 // kernels are in pos_kernels.hpp; the host sequences launches and reads a few scalars per LM iteration (and one per cg_check_interval PCG
 // iterations).
 // Memory: every array a problem always has lies in one slab laid out by FlatLayout and owned, with the problem's private non-blocking
@@ -10,7 +9,8 @@
 #include "host_common.hpp"
 #include "flat_call.hpp"
 #include "pos_structure.hpp"
-#include "trust_region.hpp"
+#include "lm_loop.hpp"
+#include "dev_scalars.hpp"
 #include "solver_launch.hpp"
 #include "solver_dense.hpp"
 #include "pos_kernels.hpp"
@@ -41,14 +41,18 @@ struct gsfm_pos_problem {
   DevBuf<double> rho_ext, s_dev;           // (first callback loss)
   std::vector<double> h_s, h_rho;
   bool have_lin = false;                   // a linearisation from gsfm_pos_linearize / gsfm_pos_step_check is on the device
+  DevScalars vec() const { return {mem.s, part, scal}; }
 };
 
 namespace {
 
 using gsfm::PosDev;
 
-enum { PS_RZ0 = 0, PS_RZA = 1, PS_RZB = 2, PS_PAP = 3, PS_DV = 4, PS_VV = 5, PS_STEP2 = 6, PS_DG = 7, PS_DLD = 8, PS_COST = 9, PS_GMAX = 10,
+enum { PS_RZ0 = PCG_RZ0, PS_RZA = PCG_RZA, PS_RZB = PCG_RZB, PS_PAP = 3, PS_DV = 4, PS_VV = 5, PS_STEP2 = 6, PS_DG = 7, PS_DLD = 8, PS_COST = 9, PS_GMAX = 10,
        PS_XNORM2 = 11, PS_N = 12 };
+static_assert(LM_TERM_FUNCTION_TOLERANCE == GSFM_TERM_FUNCTION_TOLERANCE && LM_TERM_GRADIENT_TOLERANCE == GSFM_TERM_GRADIENT_TOLERANCE &&
+              LM_TERM_PARAMETER_TOLERANCE == GSFM_TERM_PARAMETER_TOLERANCE && LM_TERM_NO_CONVERGENCE == GSFM_TERM_NO_CONVERGENCE &&
+              LM_TERM_FAILURE == GSFM_TERM_FAILURE, "lm_loop.hpp restates the termination codes");
 
 PosDev pos_dev(gsfm_pos_problem* P) {
   PosDev a{};
@@ -68,22 +72,10 @@ auto pos_lin_kernel(const gsfm_pos_problem* P) {
   return P->lm == LM_SIMPLE ? k_pos_lin<LM_SIMPLE> : k_pos_lin<LM_PROGRAM>;
 }
 
-// bytes from the device, waited for
-int pos_read(gsfm_pos_problem* P, void* dst, const void* src_dev, size_t bytes, const char* what) {
-  HIPCHK(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, P->mem.s));
-  return sync_stream(P->mem.s, what);
-}
-
-// scal[slot] = a . b (mask: per camera), in a fixed order
-void pos_dot(gsfm_pos_problem* P, const double* a, const double* b, const uint8_t* mask, int slot) {
-  hipLaunchKernelGGL(k_pos_dot, dim3(GSFM_POS_PARTS), dim3(256), 0, P->mem.s, a, b, mask, 3 * (size_t)P->n_cams, P->part);
-  hipLaunchKernelGGL(k_pos_reduce, dim3(1), dim3(256), 0, P->mem.s, P->part, P->scal + slot, 0);
-}
-
 // host-callback loss: s of every edge at pos, rho from the callback (in edge order), the triples uploaded for the linearisation; returns the cost
 int pos_callback_rho(gsfm_pos_problem* P, const double* pos, double* cost) {
   hipLaunchKernelGGL(k_pos_resid, pos_grid(P->n_edges), dim3(256), 0, P->mem.s, pos_dev(P), pos, (double*)nullptr, P->s_dev.p, (double*)nullptr, 0);
-  if (int st = pos_read(P, P->h_s.data(), P->s_dev.p, 8 * P->n_edges, "callback residuals")) return st;
+  if (int st = P->vec().read(P->h_s.data(), P->s_dev.p, 8 * P->n_edges, "callback residuals")) return st;
   double c = 0.0;
   for (size_t e = 0; e < P->n_edges; ++e) { P->cb(P->cb_user, P->h_s[e], &P->h_rho[3 * e]); c += 0.5 * P->h_rho[3 * e]; }
   *cost = c;
@@ -94,7 +86,7 @@ int pos_callback_rho(gsfm_pos_problem* P, const double* pos, double* cost) {
 int pos_cost(gsfm_pos_problem* P, const double* pos, double* cost) {
   if (P->cb) return pos_callback_rho(P, pos, cost);
   hipLaunchKernelGGL(pos_cost_kernel(P), dim3(GSFM_POS_PARTS), dim3(256), 0, P->mem.s, pos_dev(P), pos, P->part);
-  hipLaunchKernelGGL(k_pos_reduce, dim3(1), dim3(256), 0, P->mem.s, P->part, P->scal + PS_COST, 0);
+  P->vec().reduce(PS_COST);
   return 0;
 }
 
@@ -113,11 +105,7 @@ int pos_start(gsfm_pos_problem* P, double* cb_cost) {
 }
 
 // gradient max norm and |x| over the free parameters into scal[PS_GMAX], scal[PS_XNORM2]
-void pos_norms(gsfm_pos_problem* P) {
-  hipLaunchKernelGGL(k_pos_absmax, dim3(GSFM_POS_PARTS), dim3(256), 0, P->mem.s, P->g, P->active, 3 * (size_t)P->n_cams, P->part);
-  hipLaunchKernelGGL(k_pos_reduce, dim3(1), dim3(256), 0, P->mem.s, P->part, P->scal + PS_GMAX, 1);
-  pos_dot(P, P->x, P->x, P->active, PS_XNORM2);
-}
+void pos_norms(gsfm_pos_problem* P) { P->vec().norms(P->g, P->x, P->active, P->n_cams, PS_GMAX, PS_XNORM2); }
 
 // Exact step by the dense tiled Cholesky; *ok = false: not used (size, memory; *info = -1) or the factorisation met a non-positive pivot
 // (*info > 0).  K_tiles (may be NULL): a host copy of the assembled tiles, taken before the factorisation overwrites them.
@@ -139,53 +127,32 @@ int pos_dense_step(gsfm_pos_problem* P, bool* ok, int* info_out, std::vector<dou
   hipLaunchKernelGGL(k_pos_dense_assemble, dim3(P->n_cams), dim3(256), 0, P->mem.s, pos_dev(P), P->S, P->Mblk, P->b, P->denseA.p, n, T);
   if (K_tiles) {
     K_tiles->resize(elems);
-    if (int st = pos_read(P, K_tiles->data(), P->denseA.p, 8 * elems, "dense assembly")) return st;
+    if (int st = P->vec().read(K_tiles->data(), P->denseA.p, 8 * elems, "dense assembly")) return st;
   }
   enqueue_chol_solve(P->denseA.p, P->denseL.p, P->dense_x.p, n, T, P->dense_info.p, P->mem.s, false);
   HIPCHK(hipMemcpyAsync(P->y, P->dense_x.p, 8 * (size_t)n, hipMemcpyDeviceToDevice, P->mem.s));
   int info = 0;
-  if (int st = pos_read(P, &info, P->dense_info.p, sizeof(int), "dense step")) return st;
+  if (int st = P->vec().read(&info, P->dense_info.p, sizeof(int), "dense step")) return st;
   *info_out = info;
   *ok = info == 0;
   return 0;
 }
 
-// PCG on (S L S + D^2) y = b from y = 0 (k_pos_prep set r, z, p, q); returns its iterations, *stalled: ended above the tolerance,
-// *rel: the last relative residual read back, sqrt(r.M^-1 r / b.M^-1 b) of the recursion (0 when b = 0)
+// PCG on (S L S + D^2) y = b from y = 0 (k_pos_prep set r, z, p, q): lm_loop.hpp's driver, without the breakdown rule
 int pos_pcg(gsfm_pos_problem* P, const gsfm_pos_options& o, int* iters, bool* stalled, double* rel) {
-  *iters = 0; *stalled = false; *rel = 0.0;
   const PosDev a = pos_dev(P);
+  const DevScalars V = P->vec();
   const uint32_t N = P->n_cams;
-  pos_dot(P, P->r, P->z, nullptr, PS_RZ0);
+  V.dot(P->r, P->z, nullptr, N, PS_RZ0);
   HIPCHK(hipMemcpyAsync(P->scal + PS_RZA, P->scal + PS_RZ0, 8, hipMemcpyDeviceToDevice, P->mem.s));
-  double rz0 = 0.0;
-  if (int st = pos_read(P, &rz0, P->scal + PS_RZ0, 8, "pcg start")) return st;
-  if (!(rz0 > 0.0) || !std::isfinite(rz0)) return 0;   // b = 0: y = 0 is the solution (a NaN right-hand side: the step is refused later)
-  const int check = std::max(1, o.cg_check_interval);
-  double best = rz0; int best_it = 0;
-  int cur = PS_RZA, nxt = PS_RZB;
-  int it = 0;
-  while (it < o.max_cg_iterations) {
+  auto iterate = [&](int cur, int nxt) {
     hipLaunchKernelGGL(k_pos_matvec<true>, pos_row_grid(N), dim3(256), 0, P->mem.s, a, P->q, P->p, P->S, P->D2, P->Ap);
-    pos_dot(P, P->p, P->Ap, nullptr, PS_PAP);
+    V.dot(P->p, P->Ap, nullptr, N, PS_PAP);
     hipLaunchKernelGGL(k_pos_pcg_update, pos_grid(N), dim3(256), 0, P->mem.s, N, P->scal, cur, PS_PAP, P->p, P->Ap, P->y, P->r, P->z, P->Minv);
-    pos_dot(P, P->r, P->z, nullptr, nxt);
+    V.dot(P->r, P->z, nullptr, N, nxt);
     hipLaunchKernelGGL(k_pos_pcg_dir, pos_grid(N), dim3(256), 0, P->mem.s, N, P->scal, nxt, cur, P->active, P->S, P->z, P->p, P->q);
-    std::swap(cur, nxt);
-    ++it;
-    if (it % check == 0 || it == o.max_cg_iterations) {
-      double rz = 0.0;
-      if (int st = pos_read(P, &rz, P->scal + cur, 8, "pcg")) return st;
-      *rel = std::sqrt(std::fmax(rz, 0.0) / rz0);
-      if (!std::isfinite(rz)) { *rel = rz; break; }
-      if (*rel <= o.cg_relative_tolerance) { *iters = it; return 0; }
-      if (rz <= 0.25 * best) { best = rz; best_it = it; }   // the relative residual sqrt(rz / rz0) halved
-      else if (o.cg_stall_iterations > 0 && it - best_it >= o.cg_stall_iterations) break;
-    }
-  }
-  *iters = it;
-  *stalled = true;
-  return 0;
+  };
+  return pcg_loop(o, false, iterate, V.pcg_reader(), iters, stalled, rel);
 }
 
 // One LM step's linear algebra at P->x, after its linearisation and with the Jacobi scale S in place -- shared by the solve and by
@@ -197,6 +164,7 @@ struct PosStep { bool dense = false; int info = -1; int cg = 0; bool stalled = f
 int pos_step(gsfm_pos_problem* P, int32_t fixed, double radius, const gsfm_pos_options& o, PosStep* out, std::vector<double>* K_tiles) {
   const uint32_t N = P->n_cams;
   const PosDev a = pos_dev(P);
+  const DevScalars V = P->vec();
   *out = PosStep();
   auto prep = [&] {
     hipLaunchKernelGGL(k_pos_prep, pos_grid(N), dim3(256), 0, P->mem.s, N, P->active, P->Dg, P->g, P->S, radius, o.min_lm_diagonal, o.max_lm_diagonal,
@@ -213,109 +181,59 @@ int pos_step(gsfm_pos_problem* P, int32_t fixed, double radius, const gsfm_pos_o
     if (int st = pos_pcg(P, o, &out->cg, &out->stalled, &out->cg_rel)) return st;
   // the step, its scale-gauge part removed, the trial point, and what the decision needs
   hipLaunchKernelGGL(k_pos_step, pos_grid(N), dim3(256), 0, P->mem.s, N, P->active, P->S, P->y, P->x, fixed, o.remove_scale_gauge, P->delta, P->v);
-  pos_dot(P, P->delta, P->v, nullptr, PS_DV);
-  pos_dot(P, P->v, P->v, nullptr, PS_VV);
+  V.dot(P->delta, P->v, nullptr, N, PS_DV);
+  V.dot(P->v, P->v, nullptr, N, PS_VV);
   hipLaunchKernelGGL(k_pos_project, pos_grid(N), dim3(256), 0, P->mem.s, N, P->scal, PS_DV, PS_VV, P->v, P->delta, P->x, P->cand);
-  pos_dot(P, P->delta, P->delta, nullptr, PS_STEP2);
-  pos_dot(P, P->delta, P->g, nullptr, PS_DG);
+  V.dot(P->delta, P->delta, nullptr, N, PS_STEP2);
+  V.dot(P->delta, P->g, nullptr, N, PS_DG);
   hipLaunchKernelGGL(k_pos_matvec<false>, pos_row_grid(N), dim3(256), 0, P->mem.s, a, P->delta, P->delta, P->S, P->D2, P->Ap);
-  pos_dot(P, P->delta, P->Ap, nullptr, PS_DLD);
+  V.dot(P->delta, P->Ap, nullptr, N, PS_DLD);
   return 0;
 }
 
-int pos_lm_solve(gsfm_pos_problem* P, int32_t fixed, const gsfm_pos_options& o, gsfm_pos_summary* sum) {
-  const uint32_t N = P->n_cams;
-  TrustRegion tr;
-  tr.radius = o.initial_trust_region_radius;
-  int iteration = 0;
-  double x_cost = 0.0, x_norm = 0.0, gmax = 0.0;
+// What lm_loop runs for the position problem.  hs: the host copy of the device scalars.
+struct PosLm {
+  gsfm_pos_problem* P;
+  int32_t fixed;
+  const gsfm_pos_options& o;
+  gsfm_pos_summary* sum;
   double hs[PS_N];
-  sum->max_radius = tr.radius;
-
-  auto read_scal = [&](const char* what) { return pos_read(P, hs, P->scal, sizeof(hs), what); };
-  auto finish = [&](int term) {
-    sum->termination = term; sum->num_iterations = iteration; sum->final_cost = x_cost;
-    sum->final_gradient_max_norm = gmax; sum->final_radius = tr.radius;
-    if (!std::isfinite(x_cost)) sum->nonfinite = 1;
+  int read_scal(const char* what) { return P->vec().read(hs, P->scal, sizeof(hs), what); }
+  int start(LmPoint* at) {
+    const uint32_t N = P->n_cams;
+    double cb_cost = 0.0;
+    if (int st = pos_start(P, &cb_cost)) return st;
+    hipLaunchKernelGGL(k_pos_scale, pos_grid(N), dim3(256), 0, P->mem.s, N, P->Dg, P->S, o.jacobi_scaling);
+    pos_norms(P);
+    if (int st = read_scal("start point")) return st;
+    *at = {P->cb ? cb_cost : hs[PS_COST], hs[PS_GMAX], hs[PS_XNORM2]};
     return 0;
-  };
-  auto log = [&](double cost_change, double step_norm, double rel_dec, int cg) {
-    if (o.verbose) fprintf(stderr, "[gsfm pos] it %3d cost %.12e dcost %.3e |g| %.3e |dx| %.3e rho %.3e radius %.3e cg %d\n",
-                           iteration, x_cost, cost_change, gmax, step_norm, rel_dec, tr.radius, cg);
-  };
-
-  // iteration 0: cost, linearisation (with the Jacobi scale of the start point), gradient norm
-  double cb_cost = 0.0;
-  if (int st = pos_start(P, &cb_cost)) return st;
-  hipLaunchKernelGGL(k_pos_scale, pos_grid(N), dim3(256), 0, P->mem.s, N, P->Dg, P->S, o.jacobi_scaling);
-  pos_norms(P);
-  if (int st = read_scal("start point")) return st;
-  x_cost = P->cb ? cb_cost : hs[PS_COST];
-  gmax = hs[PS_GMAX]; x_norm = std::sqrt(hs[PS_XNORM2]);
-  sum->num_residual_sweeps++; sum->num_linearizations++;
-  sum->initial_cost = x_cost;
-  log(0, 0, 0, 0);
-  if (!std::isfinite(x_cost)) return finish(GSFM_TERM_FAILURE);
-  if (gmax <= o.gradient_tolerance) return finish(GSFM_TERM_GRADIENT_TOLERANCE);
-  bool last_successful = false;
-  while (true) {
-    if (iteration >= o.max_num_iterations) return finish(GSFM_TERM_NO_CONVERGENCE);
-    if (last_successful && gmax <= o.gradient_tolerance) return finish(GSFM_TERM_GRADIENT_TOLERANCE);
-    if (tr.radius <= o.min_trust_region_radius) return finish(GSFM_TERM_FAILURE);
-    ++iteration;
-    last_successful = false;
+  }
+  int step(double radius, LmStep* out) {
     PosStep step;
-    if (int st = pos_step(P, fixed, tr.radius, o, &step, nullptr)) return st;
-    const int cg = step.cg;
+    if (int st = pos_step(P, fixed, radius, o, &step, nullptr)) return st;
     if (step.dense) sum->num_dense_solves++;
     else {
-      sum->num_cg_iterations += cg;
+      sum->num_cg_iterations += step.cg;
       if (step.stalled) sum->num_pcg_stalled_steps++;
     }
     if (int st = read_scal("step")) return st;
-    const double step2 = hs[PS_STEP2];
-    bool valid = std::isfinite(step2) && std::isfinite(hs[PS_DG]) && std::isfinite(hs[PS_DLD]);
-    // model cost change -(J delta)^T (r + J delta / 2) = -delta.g - delta^T L delta / 2
-    const double model_cost_change = -hs[PS_DG] - 0.5 * hs[PS_DLD];
-    if (valid && !(model_cost_change > 0.0)) valid = false;
-    if (!valid) {   // HandleInvalidStep
-      if (tr.invalid_step()) return finish(GSFM_TERM_FAILURE);
-      sum->num_unsuccessful_steps++;
-      log(0, 0, 0, cg);
-      continue;
-    }
-    tr.num_invalid = 0;
-    double cand_cost = 0.0;
-    if (int st = pos_cost(P, P->cand, &cand_cost)) return st;
-    if (!P->cb) {
-      if (int st = pos_read(P, &cand_cost, P->scal + PS_COST, 8, "trial cost")) return st;
-    }
-    sum->num_residual_sweeps++;
-    if (!std::isfinite(cand_cost)) { cand_cost = std::numeric_limits<double>::max(); sum->nonfinite = 1; }
-    const double step_norm = std::sqrt(step2);
-    const double cost_change = x_cost - cand_cost;
-    const double rel_dec = cost_change / model_cost_change;
-    if (step_norm <= o.parameter_tolerance * (x_norm + o.parameter_tolerance)) { log(cost_change, step_norm, rel_dec, cg); return finish(GSFM_TERM_PARAMETER_TOLERANCE); }
-    if (std::fabs(cost_change) <= o.function_tolerance * x_cost) { log(cost_change, step_norm, rel_dec, cg); return finish(GSFM_TERM_FUNCTION_TOLERANCE); }
-    if (rel_dec > o.min_relative_decrease) {   // HandleSuccessfulStep
-      HIPCHK(hipMemcpyAsync(P->x, P->cand, 24 * (size_t)N, hipMemcpyDeviceToDevice, P->mem.s));
-      x_cost = cand_cost;
-      if (int st = pos_linearize(P)) return st;
-      pos_norms(P);
-      if (int st = read_scal("linearisation")) return st;
-      gmax = hs[PS_GMAX]; x_norm = std::sqrt(hs[PS_XNORM2]);
-      sum->num_linearizations++;
-      tr.accepted(rel_dec, o.max_trust_region_radius);
-      sum->num_successful_steps++;
-      last_successful = true;
-    } else {   // HandleUnsuccessfulStep
-      tr.rejected();
-      sum->num_unsuccessful_steps++;
-    }
-    sum->max_radius = std::fmax(sum->max_radius, tr.radius);
-    log(cost_change, step_norm, rel_dec, cg);
+    *out = {hs[PS_STEP2], hs[PS_DG], hs[PS_DLD], step.cg};
+    return 0;
   }
-}
+  int trial_cost(double* cost) {
+    if (int st = pos_cost(P, P->cand, cost)) return st;
+    return P->cb ? 0 : P->vec().read_slot(PS_COST, cost, "trial cost");
+  }
+  int accept(LmPoint* at) {
+    HIPCHK(hipMemcpyAsync(P->x, P->cand, 24 * (size_t)P->n_cams, hipMemcpyDeviceToDevice, P->mem.s));
+    if (int st = pos_linearize(P)) return st;
+    pos_norms(P);
+    if (int st = read_scal("linearisation")) return st;
+    at->gmax = hs[PS_GMAX]; at->xnorm2 = hs[PS_XNORM2];
+    return 0;
+  }
+};
 
 // fixed_cam is -1 or a camera that appears in an edge
 int pos_check_fixed(const gsfm_pos_problem* P, int32_t fixed_cam) {
@@ -363,20 +281,15 @@ int pos_check_create(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, 
 // first, side by side (*zeroed bytes): one memset clears them.
 FlatLayout pos_place(gsfm_pos_problem* P, char* slab, size_t* zeroed) {
   const size_t N = P->n_cams, E = P->n_edges, ND = 2 * E;
-  FlatLayout L;
-  auto take = [&](auto*& ptr, size_t count) {
-    using T = std::remove_reference_t<decltype(*ptr)>;
-    const Slot<T> slot = L.take<T>(count);
-    if (slab) ptr = (T*)(slab + slot.off);
-  };
+  SlabTake take{FlatLayout(), slab};
   take(P->active, N); take(P->scal, PS_N); take(P->Dg, 6 * N);
   take(P->d_loss, 1);   // (all zeros: Ceres' NULL loss, the default; the estimator layer sets the reference's HuberLoss(0.1))
   for (double** v : {&P->x, &P->cand, &P->g, &P->S, &P->D2, &P->b, &P->r, &P->z, &P->p, &P->q, &P->y, &P->Ap, &P->delta, &P->v}) take(*v, 3 * N);
-  *zeroed = L.total;
+  *zeroed = take.L.total;
   take(P->row_ptr, N + 1); take(P->nbr, ND); take(P->eid, ND); take(P->ei, E); take(P->ej, E);
   take(P->dir_k, 3 * ND); take(P->dir_e, 3 * E); take(P->H, 6 * ND);
   take(P->Mblk, 6 * N); take(P->Minv, 9 * N); take(P->part, GSFM_POS_PARTS);
-  return L;
+  return take.L;
 }
 
 // k_pos_directions' inputs that the problem does not keep: one allocation of create's, gone when it returns
@@ -495,7 +408,8 @@ gsfm_status gsfm_pos_solve(gsfm_pos_problem* P, double* pos, int32_t fixed_cam, 
   summary->num_edges_used = P->n_edges;
   const double t0 = now_ms();
   if (int st = pos_upload_point(P, pos, fixed_cam)) return (gsfm_status)st;
-  if (int st = pos_lm_solve(P, fixed_cam, o, summary)) return (gsfm_status)st;
+  PosLm ops{P, fixed_cam, o, summary, {}};
+  if (int st = lm_loop(ops, o, summary, "pos")) return (gsfm_status)st;
   HIPCHK_S(hipMemcpyAsync(pos, P->x, 24 * (size_t)P->n_cams, hipMemcpyDeviceToHost, P->mem.s));
   if (int st = sync_stream(P->mem.s, "download positions")) return (gsfm_status)st;
   summary->t_total_ms = now_ms() - t0;

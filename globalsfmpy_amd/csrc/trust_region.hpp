@@ -1,5 +1,5 @@
 // The trust-region radius rule of Ceres 1.14's LevenbergMarquardtStrategy (StepAccepted / StepRejected) and TrustRegionMinimizer's count of
-// consecutive invalid steps, as the host loops apply it: LmSolve (solver_lm.hpp) and pos_lm_solve (solver_pos.hpp).  Plain arithmetic, no
+// consecutive invalid steps, as the host loops apply it: LmSolve (solver_lm.hpp) and lm_loop (lm_loop.hpp: the position and bundle solvers).  Plain arithmetic, no
 // HIP: tests/cpp/trust_region_test.cpp builds it with the host compiler alone and replays an oracle trace through it bit for bit.
 // The cube is std::pow(t, 3), the oracle's very call.  The device-side rules cube otherwise and differ in the last bit by design:
 // k_lm_decide through lm_cube (correctly rounded), the per-track / per-edge / covariance kernels and host/evaluation.cpp by t * t * t.

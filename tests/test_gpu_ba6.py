@@ -289,3 +289,21 @@ def test_fixed_orientation_solve_keeps_the_bytes_of_the_commit_before_this_solve
     assert c1.tobytes() == gold["cam_pos"].tobytes() and p1.tobytes() == gold["points"].tobytes()
     assert s["final_cost"] == gold["final_cost"][0]
     assert [s["termination"], s["num_iterations"], s["num_successful_steps"], s["num_unsuccessful_steps"], s["num_cg_iterations"]] == list(gold["counts"])
+
+
+@pytest.mark.parametrize("name", ["b_near", "a_far"])
+def test_full_solve_keeps_the_bytes_of_the_commit_before_the_shared_host_loop(name):
+    """gsfm_ba6_solve under Huber 10 from case_start(name): the bytes and counts recorded on an MI355X from a library built from the commit
+    before the solvers' host loops moved to csrc/lm_loop.hpp (tools/make_lm_loop_golden.py, tests/golden/ba6_solve_parent_bytes.npz).  The
+    far start takes rejected steps."""
+    gold = np.load(os.path.join(os.path.dirname(GOLDEN), "ba6_solve_parent_bytes.npz"))
+    sc = R.scene(R.CASES[name][0])
+    w0, c0, p0 = R.split(sc, R.case_start(name))
+    w1, c1, p1, s = _problem(sc, LOSSES["huber"][0]).solve(w0, c0, p0)
+    counts = [s["termination"], s["num_iterations"], s["num_successful_steps"], s["num_unsuccessful_steps"], s["num_cg_iterations"]]
+    print(name, counts, "final cost %.17g" % s["final_cost"])
+    if name == "a_far":
+        assert gold["a_far_counts"][3] > 0
+    assert w1.tobytes() == gold[name + "_rot"].tobytes() and c1.tobytes() == gold[name + "_cam"].tobytes() and p1.tobytes() == gold[name + "_points"].tobytes()
+    assert s["final_cost"] == gold[name + "_final_cost"][0]
+    assert counts == list(gold[name + "_counts"])

@@ -1,5 +1,7 @@
 """Camera-position estimation on the device (include/gsfm_pos.h) against the numpy reference (tests/position_reference.py).
 Everything runs in the pytest process.  Positions are compared after removing translation and scale (synth.gauge_normalize)."""
+import os
+
 import numpy as np
 import pytest
 
@@ -253,3 +255,19 @@ def test_ply_writes_estimated_positions(tmp_path):
     got = sorted(map(tuple, verts[:, :3]))
     np.testing.assert_allclose(np.array(got), np.array(sorted(map(tuple, want))), rtol=1e-5, atol=1e-5 * np.abs(want).max())
     assert np.abs(want).max() > 0.1   # the cameras are no longer all at the origin
+
+
+@pytest.mark.parametrize("tag,options", [("dense", {}), ("pcg", {"dense_max_cams": 0})])
+def test_solve_keeps_the_bytes_of_the_commit_before_the_shared_host_loop(tag, options):
+    """gsfm_pos_solve under Huber 0.1 from the fixture's start array, by Cholesky steps and by PCG steps: the bytes and counts recorded on an
+    MI355X from a library built from the commit before the solvers' host loops moved to csrc/lm_loop.hpp (tools/make_lm_loop_golden.py,
+    tests/golden/pos_solve_parent_bytes.npz)."""
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pos_solve_parent_bytes.npz"))
+    g = synth.make_position_graph(60, 500, seed=11, outlier_frac=0.3, noise=0.01)
+    x, s = _problem(g, lf.HuberLoss(0.1)).solve(gold["start"], fixed_cam=0, **options)
+    counts = [s[k] for k in ("termination", "num_iterations", "num_successful_steps", "num_unsuccessful_steps", "num_cg_iterations", "num_dense_solves")]
+    print(tag, counts, "final cost %.17g" % s["final_cost"])
+    assert (s["num_dense_solves"] > 0) == (tag == "dense") and (s["num_cg_iterations"] > 0) == (tag == "pcg")
+    assert x.tobytes() == gold[tag + "_pos"].tobytes()
+    assert s["final_cost"] == gold[tag + "_final_cost"][0]
+    assert counts == list(gold[tag + "_counts"])

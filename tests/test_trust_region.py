@@ -1,4 +1,4 @@
-"""CPU check of the host trust-region rule (csrc/trust_region.hpp, used by LmSolve and pos_lm_solve): the host compiler builds
+"""CPU check of the host trust-region rule (csrc/trust_region.hpp, used by LmSolve and lm_loop.hpp): the host compiler builds
 tests/cpp/trust_region_test.cpp against the header.  The program's own checks cover five consecutive invalid steps (the radius shrinks by
 2, 4, 8, 16, the fifth ends the solve); the replay feeds it the steps of a CPU-oracle solve and wants the oracle's radius column bit for bit."""
 import os
