@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from .solver import _dp, _raise_if_failed
+from .solver import _p, _raise_if_failed
 
 
 def _call(fn, match_ptr, matches, intrinsics, rot, trans, max_iterations, with_ms):
@@ -18,8 +18,8 @@ def _call(fn, match_ptr, matches, intrinsics, rot, trans, max_iterations, with_m
     cov = np.zeros((E, 3, 3)); ro = np.zeros((E, 3)); to = np.zeros((E, 3))
     st = np.zeros(E, dtype=np.int32); it = np.zeros(E, dtype=np.int32)
     ms = C.c_double(0)
-    args = [C.c_uint64(E), mp.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(m), _dp(K), _dp(r), _dp(t), int(max_iterations), _dp(cov), _dp(ro), _dp(to),
-            st.ctypes.data_as(C.POINTER(C.c_int32)), it.ctypes.data_as(C.POINTER(C.c_int32))]
+    args = [C.c_uint64(E), _p(mp), _p(m), _p(K), _p(r), _p(t), int(max_iterations), _p(cov), _p(ro), _p(to),
+            _p(st), _p(it)]
     if with_ms:
         args.append(C.byref(ms))
     code = fn(*args)

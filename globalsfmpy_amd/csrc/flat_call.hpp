@@ -1,5 +1,6 @@
 // The scratch owner of the one-shot device calls (host arrays in, a few launches, host arrays out): edge_norms.hpp, spanning_tree.hpp,
-// trans_filter.hpp, trans_refine.hpp, triangulate.hpp, outlier_tracks.hpp, dense_check.hpp, cov_estimate.hpp.  FlatLayout lays the call's arrays out in one
+// trans_filter.hpp, trans_refine.hpp, dense_check.hpp, cov_estimate.hpp, and through track_scene.hpp's TrackScene (the slots every call
+// over cameras and tracks takes) triangulate.hpp and outlier_tracks.hpp.  FlatLayout lays the call's arrays out in one
 // slab (plain arithmetic, no HIP: tests/cpp/flat_layout_test.cpp builds it with the host compiler alone).  FlatCall::commit then checks the
 // free memory and creates a private non-blocking stream, the timing events and the slab; the destructor frees them on every path.  Nothing
 // is kept between calls, nothing touches the default stream or synchronises the device: a flat call never stalls a problem's stream.

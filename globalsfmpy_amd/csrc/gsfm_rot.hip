@@ -396,9 +396,8 @@ gsfm_status gsfm_tracks_outlier_tracks(uint32_t n_cams, const double* rot_aa, co
 gsfm_status gsfm_tracks_launch_order(uint64_t n_tracks, const uint64_t* track_ptr, uint32_t* order_out, uint64_t* class_begin_out) {
   return guarded("the launch order", [&] {   // (the messages' strings, stable_sort's buffer)
     if (!class_begin_out || (n_tracks > 0 && (!track_ptr || !order_out))) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
-    if (n_tracks >= (1ull << 31)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "problem too large (2^31 tracks)");
-    for (uint64_t t = 0; t < n_tracks; ++t)
-      if (track_ptr[t + 1] < track_ptr[t]) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "track_ptr decreases at track " + std::to_string(t));
+    std::string why;   // (track_ptr[0] is not looked at: only the lengths matter here)
+    if (!track_ptr_ok(n_tracks, track_ptr, TrackLimit::tracks, 0, false, nullptr, &why)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, why);
     tri_bucket(n_tracks, track_ptr, order_out, class_begin_out);
     return GSFM_OK;
   });

@@ -1,8 +1,9 @@
 // Host side of the bundle adjustment of camera positions and points (include/gsfm_ba.h), and what it shares with the full bundle adjustment
 // (solver_ba6.hpp): the problem's common part (BaProblem: sizes, host structure of ba_structure.hpp, structure arrays, the vectors of the
-// step), the operations that lm_loop.hpp's Levenberg-Marquardt loop runs (BaLm), argument checks, the one-leaf loss, solve, residuals and
-// kernel timing.  Its own: the Schur-complement PCG (ba_pcg, on lm_loop.hpp's driver) and the step.  The kernels are in ba_kernels.hpp; the
-// vector kernels of the PCG and the reductions are the position problem's (pos_kernels.hpp, dev_scalars.hpp), which work on any n x 3 array.
+// step), the operations that lm_loop.hpp's Levenberg-Marquardt loop runs (BaLm), argument checks, set_loss, solve, residuals and kernel
+// timing; the checks of the track arrays, the lane classes with their launcher and the one-leaf loss are track_scene.hpp's.  Its own: the
+// Schur-complement PCG (ba_pcg, on lm_loop.hpp's driver) and the step.  The kernels are in ba_kernels.hpp; the vector kernels of the PCG
+// and the reductions are the position problem's (pos_kernels.hpp, dev_scalars.hpp), which work on any n x 3 array.
 // Memory: one slab laid out by FlatLayout and owned, with the problem's private non-blocking stream, by a FlatCall member (flat_call.hpp).
 // Every copy and memset is ordered on that stream.  The unknowns are one array of (n_cams + n_tracks) x 3, cameras first.
 #pragma once
@@ -11,7 +12,7 @@
 #include "ba_structure.hpp"
 #include "lm_loop.hpp"
 #include "dev_scalars.hpp"
-#include "triangulate.hpp"
+#include "track_scene.hpp"
 #include "ba_kernels.hpp"
 #include "../../include/gsfm_ba.h"
 
@@ -89,17 +90,13 @@ BaDev ba_dev(const gsfm_ba_problem* P) {
 inline dim3 ba_grid(size_t n) { return dim3((unsigned)std::max<size_t>(1, (n + 255) / 256)); }
 inline dim3 ba_row_grid(uint32_t n_cams) { return dim3(std::max(1u, (n_cams + 3) / 4)); }
 
-// a point-side kernel over every track: one launch per lane class, the long tracks first (the order of triangulate.hpp).  a: BaDev or Ba6Dev
-template <typename Dev, typename K4, typename K16, typename K64, typename... Args>
-void ba_tracks(const BaProblem* P, const Dev& a, K4 k4, K16 k16, K64 k64, Args... args) {
-  auto go = [&](int c, auto kernel, unsigned groups_per_block, unsigned block) {
-    const BaSlots sl{P->cb[c + 1] - P->cb[c], P->order + P->cb[c]};
-    if (sl.n_slots == 0) return;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((sl.n_slots + groups_per_block - 1) / groups_per_block)), dim3(block), 0, P->mem.s, a, sl, args...);
-  };
-  go(2, k64, 1, 64);
-  go(1, k16, GSFM_TRI_BLOCK / 16, GSFM_TRI_BLOCK);
-  go(0, k4, GSFM_TRI_BLOCK / 4, GSFM_TRI_BLOCK);
+// a point-side kernel over every track: one launch per lane class, the long tracks first (track_scene.hpp's launcher).  a: BaDev or Ba6Dev
+template <typename Dev, typename K, typename... Args>
+void ba_tracks(const BaProblem* P, const Dev& a, K k4, K k16, K k64, Args... args) {
+  for_lane_classes(P->cb, [&](auto G, uint64_t n_slots, uint64_t offset, dim3 grid, dim3 block) {
+    const BaSlots sl{n_slots, P->order + offset};
+    hipLaunchKernelGGL(G() == 64 ? k64 : G() == 16 ? k16 : k4, grid, block, 0, P->mem.s, a, sl, args...);
+  });
 }
 #define BA_TRACKS(P, K, ...) ba_tracks(P, ba_dev(P), K<4>, K<16>, K<64>, __VA_ARGS__)
 
@@ -260,18 +257,11 @@ bool ba_needs_points(const gsfm_ba_problem* P, const double* cam_pos, const doub
 }
 
 // ---- problem creation ----
-// The checks of the track arrays, on the host before any device call.  nodes_per_cam: 1, or 2 for the full bundle adjustment.
+// The checks of the track arrays (track_scene.hpp), on the host before any device call.  nodes_per_cam: 1, or 2 for the full bundle adjustment.
 int ba_check_tracks(uint32_t n_cams, int nodes_per_cam, uint64_t n_tracks, const uint64_t* track_ptr, const uint32_t* obs_cam, const double* obs_xy,
                     const char* entry) {
-  if (!track_ptr) return fail(GSFM_ERR_INVALID_ARG, "NULL argument (track_ptr holds n_tracks + 1 entries)");
-  if (track_ptr[0] != 0) return fail(GSFM_ERR_INVALID_ARG, "track_ptr[0] must be 0");
-  for (uint64_t t = 0; t < n_tracks; ++t)
-    if (track_ptr[t + 1] < track_ptr[t]) return fail(GSFM_ERR_INVALID_ARG, "track_ptr decreases at track " + std::to_string(t));
-  const uint64_t O = track_ptr[n_tracks];
-  if (O >= (1ull << 31) || (uint64_t)nodes_per_cam * n_cams + n_tracks >= (1ull << 31)) return fail(GSFM_ERR_INVALID_ARG, "problem too large (2^31 observations or nodes)");
-  if (O > 0 && (!obs_cam || !obs_xy)) return fail(GSFM_ERR_INVALID_ARG, "NULL argument");
-  for (uint64_t k = 0; k < O; ++k)
-    if (obs_cam[k] >= n_cams) return fail(GSFM_ERR_INVALID_ARG, "observation " + std::to_string(k) + " has an out-of-range camera index");
+  if (int st = track_arrays_check(n_cams, n_tracks, track_ptr, obs_cam, obs_xy, TrackLimit::observations_and_nodes, (uint64_t)nodes_per_cam * n_cams,
+                                  "NULL argument (track_ptr holds n_tracks + 1 entries)")) return st;
   if (const char* why = no_device_reason(entry)) return fail(GSFM_ERR_NO_DEVICE, why);
   return 0;
 }
@@ -435,24 +425,14 @@ gsfm_status ba_residuals_impl(gsfm_ba_problem* P, const double* cam_pos, const d
   return ba_residuals(P, [&] { return ba_upload_point(P, cam_pos, points); }, r_out, rho_out);
 }
 
-// The one-leaf loss of a bundle adjustment, validated without a problem (the ABI tests hand in a handle that is no problem at all: the
-// callers store *leaf after every refusal).  who: "bundle adjustment" or "full bundle adjustment"
-int ba_leaf_loss(const gsfm_loss_node* prog, int32_t n, const std::string& who, gsfm::DevLossNode* leaf) {
-  if (n < 0 || n > 1) return fail(GSFM_ERR_INVALID_ARG, "the " + who + " takes a loss of one leaf (composite programs are not supported)");
-  std::memset(leaf, 0, sizeof(*leaf));
-  leaf->kind = GSFM_LOSS_TRIVIAL;
-  if (n == 1) {
-    const int k = prog[0].kind;
-    if (!(k == GSFM_LOSS_TRIVIAL || k == GSFM_LOSS_HUBER || k == GSFM_LOSS_SOFT_L1 || k == GSFM_LOSS_TUKEY || k == GSFM_LOSS_GEMAN_MCCLURE))
-      return fail(GSFM_ERR_INVALID_ARG, "the " + who + " takes the losses Trivial, Huber, SoftLOne, Tukey and GemanMcClure (MAGSAC and the other leaves are not supported)");
-    for (int j = 0; j < 3; ++j) {
-      if (!std::isfinite(prog[0].p[j])) return fail(GSFM_ERR_INVALID_ARG, "loss parameter is not finite");
-      leaf->p[j] = prog[0].p[j];
-    }
-    if (k != GSFM_LOSS_TRIVIAL && !(prog[0].p[0] > 0.0)) return fail(GSFM_ERR_INVALID_ARG, "the loss width must be positive");
-    leaf->kind = k;
-  }
-  return 0;
+// set_loss of either bundle adjustment (who: its name in the messages); nothing is read of P before the last refusal
+gsfm_status ba_set_loss(BaProblem* P, const gsfm_loss_node* prog, int32_t n, const char* who) {
+  if (!P || (n > 0 && !prog)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
+  gsfm::DevLossNode leaf;
+  if (int st = one_leaf_loss(prog, n, who, &leaf)) return (gsfm_status)st;
+  P->leaf = leaf;   // (passed to the kernels by value)
+  P->have_lin = false;
+  return GSFM_OK;
 }
 
 // Device time of single launches for the *_time_kernels entries: timer(launch) runs launch once to warm, then reps times between two events,
@@ -536,14 +516,7 @@ gsfm_status gsfm_ba_problem_create(uint32_t n_cams, const double* rot_aa, const 
                  point_estimated, out);
 }
 
-gsfm_status gsfm_ba_set_loss(gsfm_ba_problem* P, const gsfm_loss_node* prog, int32_t n) {
-  if (!P || (n > 0 && !prog)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
-  gsfm::DevLossNode leaf;
-  if (int st = ba_leaf_loss(prog, n, "bundle adjustment", &leaf)) return (gsfm_status)st;
-  P->leaf = leaf;   // (passed to the kernels by value)
-  P->have_lin = false;
-  return GSFM_OK;
-}
+gsfm_status gsfm_ba_set_loss(gsfm_ba_problem* P, const gsfm_loss_node* prog, int32_t n) { return ba_set_loss(P, prog, n, "bundle adjustment"); }
 
 gsfm_status gsfm_ba_solve(gsfm_ba_problem* P, double* cam_pos, double* points, const gsfm_ba_options* opt, gsfm_ba_summary* summary) {
   return guarded("the bundle adjustment", ba_solve_impl, P, cam_pos, points, opt, summary);

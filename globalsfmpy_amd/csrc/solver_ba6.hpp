@@ -370,14 +370,7 @@ gsfm_status gsfm_ba6_problem_create(uint32_t n_cams, const double* intrinsics, c
                  point_estimated, out);
 }
 
-gsfm_status gsfm_ba6_set_loss(gsfm_ba6_problem* P, const gsfm_loss_node* prog, int32_t n) {
-  if (!P || (n > 0 && !prog)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
-  gsfm::DevLossNode leaf;
-  if (int st = ba_leaf_loss(prog, n, "full bundle adjustment", &leaf)) return (gsfm_status)st;
-  P->leaf = leaf;   // (passed to the kernels by value)
-  P->have_lin = false;
-  return GSFM_OK;
-}
+gsfm_status gsfm_ba6_set_loss(gsfm_ba6_problem* P, const gsfm_loss_node* prog, int32_t n) { return ba_set_loss(P, prog, n, "full bundle adjustment"); }
 
 gsfm_status gsfm_ba6_solve(gsfm_ba6_problem* P, double* rot_aa, double* cam_pos, double* points, const gsfm_ba_options* opt, gsfm_ba_summary* summary) {
   return guarded("the full bundle adjustment", b6_solve_impl, P, rot_aa, cam_pos, points, opt, summary);

@@ -1,5 +1,6 @@
-// Host side of gsfm_tracks_triangulate_refine (include/gsfm_tracks.h): the checks of the options and of the loss, the loss leaf the kernel
-// takes, and the call of tri_impl (triangulate.hpp) with the refinement hook -- its validation, slab and launch order serve both entries.
+// Host side of gsfm_tracks_triangulate_refine (include/gsfm_tracks.h): the checks of the options, the loss leaf the kernel takes
+// (track_scene.hpp's one_leaf_loss), and the call of tri_impl (triangulate.hpp) with the refinement hook -- its validation, slab and launch
+// order serve both entries.
 // Part of libgsfm_rot.so's one translation unit.
 #pragma once
 #include "triangulate.hpp"
@@ -17,45 +18,28 @@ gsfm_status tri_refine_impl(uint32_t n_cams, const double* rot_aa, const double*
   gsfm_tracks_refine_options o;
   gsfm_tracks_refine_default_options(&o);
   if (options) o = *options;
-  // the loss: nothing (Ceres' NULL loss) or ONE leaf the kernel's loss_leaf_simple evaluates
-  if (n_loss_nodes < 0 || n_loss_nodes > 1) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "the track refinement takes a loss of one leaf (composite programs are not supported)");
-  if (n_loss_nodes == 1 && !loss) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "NULL argument");
   TriRefineHook rf{};
-  rf.proto.leaf.kind = GSFM_LOSS_TRIVIAL;
-  if (n_loss_nodes == 1) {
-    const int k = loss[0].kind;
-    if (!(k == GSFM_LOSS_TRIVIAL || k == GSFM_LOSS_HUBER || k == GSFM_LOSS_SOFT_L1 || k == GSFM_LOSS_TUKEY || k == GSFM_LOSS_GEMAN_MCCLURE))
-      return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "the track refinement takes the losses Trivial, Huber, SoftLOne, Tukey and GemanMcClure (MAGSAC and the other leaves are not supported)");
-    for (int j = 0; j < 3; ++j) {
-      if (!std::isfinite(loss[0].p[j])) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "loss parameter is not finite");
-      rf.proto.leaf.p[j] = loss[0].p[j];
-    }
-    if (k != GSFM_LOSS_TRIVIAL && !(loss[0].p[0] > 0.0)) return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "the loss width must be positive");
-    rf.proto.leaf.kind = k;
-  }
+  if (int st = one_leaf_loss(loss, n_loss_nodes, "track refinement", &rf.proto.leaf)) return (gsfm_status)st;   // (its node count before a NULL program)
   auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
   if (!(o.function_tolerance >= 0.0) || !(o.gradient_tolerance >= 0.0) || !(o.parameter_tolerance >= 0.0) || !std::isfinite(o.function_tolerance) ||
       !std::isfinite(o.gradient_tolerance) || !std::isfinite(o.parameter_tolerance) || !std::isfinite(o.min_relative_decrease))
     return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "the refinement's tolerances must be finite and not negative");
   if (!positive(o.initial_trust_region_radius) || !positive(o.max_trust_region_radius) || !(o.min_trust_region_radius >= 0.0) || !std::isfinite(o.min_trust_region_radius))
     return (gsfm_status)fail(GSFM_ERR_INVALID_ARG, "the refinement's trust-region radii must be finite and positive");
-  if (!o.refine) {  // the entry without the refinement, k_tri_tracks and its bytes; a status 6 cannot occur
+  if (!o.refine)   // the entry without the refinement (no hook below): k_tri_tracks and its bytes; a status 6 cannot occur
     for (uint64_t t = 0; t < n_tracks; ++t) {
       if (iterations_out) iterations_out[t] = 0;
       if (termination_out) termination_out[t] = -1;
       if (initial_cost_out) initial_cost_out[t] = 0.0;
       if (final_cost_out) final_cost_out[t] = 0.0;
     }
-    return tri_impl(n_cams, rot_aa, cam_pos, intrinsics, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy, min_triangulation_angle_degrees,
-                    max_reprojection_error_pixels, point_out, status_out, n_views_out, mean_sq_err_out, counts_out, kernel_ms, nullptr);
-  }
   rf.proto.max_num_iterations = std::min(std::max(o.max_num_iterations, 0), GSFM_TRR_MAX_ITERATIONS);
   rf.proto.function_tolerance = o.function_tolerance; rf.proto.gradient_tolerance = o.gradient_tolerance;
   rf.proto.parameter_tolerance = o.parameter_tolerance; rf.proto.min_relative_decrease = o.min_relative_decrease;
   rf.proto.initial_radius = o.initial_trust_region_radius; rf.proto.max_radius = o.max_trust_region_radius; rf.proto.min_radius = o.min_trust_region_radius;
   rf.iterations_out = iterations_out; rf.termination_out = termination_out; rf.initial_cost_out = initial_cost_out; rf.final_cost_out = final_cost_out;
   return tri_impl(n_cams, rot_aa, cam_pos, intrinsics, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy, min_triangulation_angle_degrees,
-                  max_reprojection_error_pixels, point_out, status_out, n_views_out, mean_sq_err_out, counts_out, kernel_ms, &rf);
+                  max_reprojection_error_pixels, point_out, status_out, n_views_out, mean_sq_err_out, counts_out, kernel_ms, o.refine ? &rf : nullptr);
 }
 
 }  // namespace

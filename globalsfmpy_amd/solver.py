@@ -9,12 +9,16 @@ import numpy as np
 from . import _abi
 
 
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+_CTYPES = {np.dtype(t): c for t, c in ((np.float64, C.c_double), (np.uint8, C.c_uint8), (np.int32, C.c_int32), (np.uint32, C.c_uint32),
+                                      (np.int64, C.c_int64), (np.uint64, C.c_uint64))}
 
 
-def _u32p(a):
-    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+def _p(a):
+    """The ctypes pointer to a contiguous array's data, typed by the array's dtype; None passes through as NULL."""
+    return None if a is None else a.ctypes.data_as(C.POINTER(_CTYPES[a.dtype]))
+
+
+_dp = _u32p = _p   # the older names, which oracle/pyoracle.py imports
 
 
 class SolverError(RuntimeError):
@@ -27,7 +31,52 @@ def _raise_if_failed(lib, name, st):
         raise SolverError("%s failed with status %d: %s" % (name, st, lib.gsfm_last_error().decode("utf-8", "replace")))
 
 
-class ProblemBase(object):
+def _loss_nodes(loss, who, callback_ok=False):
+    """A loss argument as a list of (kind, p0, p1, p2) nodes: None (Ceres' NULL loss), such a list, or an object with .native_program().
+    callback_ok: an object that has only .Evaluate gives None (the caller takes the host callback path); otherwise `who` needs a native loss."""
+    if loss is None:
+        return []
+    if isinstance(loss, (list, tuple)):
+        return list(loss)
+    if hasattr(loss, "native_program") and loss.native_program() is not None:
+        return loss.native_program()
+    if not callback_ok:
+        raise TypeError("the %s needs a loss with a native descriptor, got %r" % (who, loss))
+    if hasattr(loss, "Evaluate"):
+        return None
+    raise TypeError("unsupported loss object %r" % (loss,))
+
+
+class _Handle(object):
+    """The lifetime of a problem handle (self._lib, self._h, destroyed by the entry self._prefix + "problem_destroy") and the options of a
+    solve by name (the subclass's default_options())."""
+    _prefix = None
+    _h = None
+
+    def _fn(self, name):
+        return getattr(self._lib, self._prefix + name)
+
+    def close(self):
+        if self._h is not None:
+            self._fn("problem_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _options(self, kw):
+        o = self.default_options()
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise TypeError("unknown solver option %r" % k)
+            setattr(o, k, v)
+        return o
+
+
+class ProblemBase(_Handle):
     """Shared call sequence for anything exporting the gsfm_rot_* argument lists.
     (The CPU oracle under oracle/ mirrors them with an orc_ prefix for the parity tests.)"""
 
@@ -41,9 +90,6 @@ class ProblemBase(object):
         self.error_type = int(error_type)
         self.residual_dim = int(residual_dim)
         self._keep = []
-
-    def _fn(self, name):
-        return getattr(self._lib, self._prefix + name)
 
     def _check(self, st, what):
         # every C call may have run the host-callback loss: an exception parked by the trampoline surfaces HERE, from the call that caused
@@ -61,32 +107,14 @@ class ProblemBase(object):
     def _last_error(self):
         return ""
 
-    def close(self):
-        if self._h is not None:
-            self._fn("problem_destroy")(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # -- loss ---------------------------------------------------------------
     def set_loss(self, loss):
         """loss: None (Ceres NULL loss), a list of (kind, p0, p1, p2) nodes, or an object with
         .native_program() (globalsfmpy_amd.loss_functions classes); any other object with
         .Evaluate(s, out) is used through the host callback path."""
-        if loss is None:
-            nodes = []
-        elif isinstance(loss, (list, tuple)):
-            nodes = list(loss)
-        elif hasattr(loss, "native_program") and loss.native_program() is not None:
-            nodes = loss.native_program()
-        elif hasattr(loss, "Evaluate"):
+        nodes = _loss_nodes(loss, None, callback_ok=True)
+        if nodes is None:
             return self.set_loss_callback(loss.Evaluate)
-        else:
-            raise TypeError("unsupported loss object %r" % (loss,))
         arr, n = _abi.make_program(nodes)
         self._check(self._fn("set_loss")(self._h, arr, n), "set_loss")
 
@@ -116,7 +144,7 @@ class ProblemBase(object):
     def set_edge_weights(self, w):
         w = np.ascontiguousarray(w, dtype=np.float64)
         assert w.shape == (self.n_edges,)
-        self._check(self._fn("set_edge_weights")(self._h, _dp(w)), "set_edge_weights")
+        self._check(self._fn("set_edge_weights")(self._h, _p(w)), "set_edge_weights")
 
     # -- evaluation ---------------------------------------------------------
     def residuals(self, rot_aa, want_residuals=False):
@@ -125,7 +153,7 @@ class ProblemBase(object):
         rho = np.empty((self.n_edges, 3))
         r = np.empty((self.n_edges, self.residual_dim)) if want_residuals else None
         cost = C.c_double(0)
-        st = self._fn("residuals")(self._h, _dp(rot), _dp(s), _dp(rho), _dp(r), C.byref(cost))
+        st = self._fn("residuals")(self._h, _p(rot), _p(s), _p(rho), _p(r), C.byref(cost))
         self._check(st, "residuals")
         return {"s": s, "rho": rho, "residuals": r, "cost": cost.value}
 
@@ -134,13 +162,13 @@ class ProblemBase(object):
         g = np.empty((self.n_cams, 3))
         d = np.empty((self.n_cams, 3, 3))
         cost = C.c_double(0)
-        self._check(self._fn("linearize")(self._h, _dp(rot), _dp(g), _dp(d), C.byref(cost)), "linearize")
+        self._check(self._fn("linearize")(self._h, _p(rot), _p(g), _p(d), C.byref(cost)), "linearize")
         return {"gradient": g, "diag_blocks": d, "cost": cost.value}
 
     def normal_matvec(self, v):
         v = np.ascontiguousarray(v, dtype=np.float64).reshape(self.n_cams, 3)
         y = np.empty_like(v)
-        self._check(self._fn("normal_matvec")(self._h, _dp(v), _dp(y)), "normal_matvec")
+        self._check(self._fn("normal_matvec")(self._h, _p(v), _p(y)), "normal_matvec")
         return y
 
     # -- solve --------------------------------------------------------------
@@ -149,19 +177,11 @@ class ProblemBase(object):
         self._options_default(o)
         return o
 
-    def _options(self, kw):
-        o = self.default_options()
-        for k, v in kw.items():
-            if not hasattr(o, k):
-                raise TypeError("unknown solver option %r" % k)
-            setattr(o, k, v)
-        return o
-
     def solve(self, rot_aa, **options):
         rot = np.array(rot_aa, dtype=np.float64, order="C").reshape(self.n_cams, 3)
         o = self._options(options)
         s = _abi.Summary()
-        st = self._fn("solve")(self._h, _dp(rot), C.byref(o), C.byref(s))
+        st = self._fn("solve")(self._h, _p(rot), C.byref(o), C.byref(s))
         self._check(st, "solve")
         return rot, s.as_dict()
 
@@ -169,7 +189,7 @@ class ProblemBase(object):
         rot = np.array(rot_aa, dtype=np.float64, order="C").reshape(self.n_cams, 3)
         o = self._options(options)
         s = _abi.Summary()
-        st = self._fn("solve_sigma_consensus")(self._h, _dp(rot), int(iters_num), float(sigma_max), C.byref(o), C.byref(s))
+        st = self._fn("solve_sigma_consensus")(self._h, _p(rot), int(iters_num), float(sigma_max), C.byref(o), C.byref(s))
         self._check(st, "solve_sigma_consensus")
         return rot, s.as_dict()
 
@@ -177,7 +197,7 @@ class ProblemBase(object):
         rows = self._fn("get_trace")(self._h, None, 0)
         out = np.zeros((max(rows, 0), 8))
         if rows > 0:
-            self._fn("get_trace")(self._h, _dp(out), rows)
+            self._fn("get_trace")(self._h, _p(out), rows)
         return out
 
 
@@ -217,8 +237,8 @@ class RotationProblem(ProblemBase):
         lib = _abi.load_library()
         ei, ej, rel, c6, iw, n_edges = _prep_edges(n_cams, edge_i, edge_j, rel_aa, cov6, inlier_weight)
         h = C.c_void_p()
-        st = lib.gsfm_rot_problem_create(int(n_cams), int(n_edges), _u32p(ei), _u32p(ej), _dp(rel), int(error_type),
-                                         _dp(c6), _dp(iw), C.byref(shard) if shard is not None else None, C.byref(h))
+        st = lib.gsfm_rot_problem_create(int(n_cams), int(n_edges), _p(ei), _p(ej), _p(rel), int(error_type),
+                                         _p(c6), _p(iw), C.byref(shard) if shard is not None else None, C.byref(h))
         _raise_if_failed(lib, "gsfm_rot_problem_create", st)
         ProblemBase.__init__(self, lib, h, n_cams, n_edges, error_type, lib.gsfm_rot_residual_dim(int(error_type)))
         self._shard = shard
@@ -256,8 +276,8 @@ class RotationProblem(ProblemBase):
         eta, delta, lam, xs, xt = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, pd)), np.zeros((n, pd))
         eta_l, delta_l = np.zeros((n, 3)), np.zeros((n, 3))
         info = _abi.StepInfo()
-        st = self._lib.gsfm_rot_step_check(self._h, _dp(rot), float(radius), float(loose_tau), C.byref(o), _dp(eta), _dp(delta), _dp(xs), _dp(xt), _dp(lam),
-                                           _dp(eta_l), _dp(delta_l), C.byref(info))
+        st = self._lib.gsfm_rot_step_check(self._h, _p(rot), float(radius), float(loose_tau), C.byref(o), _p(eta), _p(delta), _p(xs), _p(xt), _p(lam),
+                                           _p(eta_l), _p(delta_l), C.byref(info))
         self._check(st, "step_check")
         out = {name: getattr(info, name) for name, _ in info._fields_}
         out["step_sums"] = np.array(list(info.step_sums))
@@ -270,14 +290,14 @@ class RotationProblem(ProblemBase):
     def time_sweep(self, rot_aa, reps=20):
         rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(self.n_cams, 3)
         ms = C.c_double(0)
-        self._check(self._lib.gsfm_rot_time_sweep(self._h, _dp(rot), int(reps), C.byref(ms)), "time_sweep")
+        self._check(self._lib.gsfm_rot_time_sweep(self._h, _p(rot), int(reps), C.byref(ms)), "time_sweep")
         return ms.value
 
     def time_kernels(self, rot_aa, reps=10):
         """Mean HIP-event time (ms) of k_cost, the linearisation and one mat-vec (row-major or column-sorted forms, incl. their finish kernels)."""
         rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(self.n_cams, 3)
         out = np.zeros(4)
-        self._check(self._lib.gsfm_rot_time_kernels(self._h, _dp(rot), int(reps), _dp(out)), "time_kernels")
+        self._check(self._lib.gsfm_rot_time_kernels(self._h, _p(rot), int(reps), _p(out)), "time_kernels")
         return {"k_cost": out[0], "k_lin": out[1], "k_matvec": out[2]}
 
     def matvec_bytes(self):
@@ -297,7 +317,7 @@ class RotationProblem(ProblemBase):
         s = np.ascontiguousarray(s, dtype=np.float64).ravel()
         rho3, val = np.empty((s.size, 3)), np.empty(s.size)
         fast = np.empty(s.size) if with_fast_rho1 else None
-        self._check(self._lib.gsfm_rot_loss_eval(self._h, _dp(s), s.size, _dp(rho3), _dp(val), _dp(fast)), "loss_eval")
+        self._check(self._lib.gsfm_rot_loss_eval(self._h, _p(s), s.size, _p(rho3), _p(val), _p(fast)), "loss_eval")
         return (rho3, val, fast) if with_fast_rho1 else (rho3, val)
 
     def edge_order(self):
@@ -305,7 +325,7 @@ class RotationProblem(ProblemBase):
         n = self._lib.gsfm_rot_edge_order(self._h, None, 0)
         out = np.empty(max(n, 0), dtype=np.uint32)
         if n > 0:
-            self._lib.gsfm_rot_edge_order(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n)
+            self._lib.gsfm_rot_edge_order(self._h, _p(out), n)
         return out
 
     def time_sweep_variants(self, rot_aa, reps=10):
@@ -313,7 +333,7 @@ class RotationProblem(ProblemBase):
         forms of K1 / K2 against their plain forms (zeros unless the problem is an ANGLE_AXIS one carrying scalar weights)."""
         rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(self.n_cams, 3)
         out = np.zeros(8)
-        self._check(self._lib.gsfm_rot_time_sweep_variants(self._h, _dp(rot), int(reps), _dp(out)), "time_sweep_variants")
+        self._check(self._lib.gsfm_rot_time_sweep_variants(self._h, _p(rot), int(reps), _p(out)), "time_sweep_variants")
         return {"trial_cost": out[0], "full_reweight": out[1], "s_only": out[2], "rho1_only": out[3],
                 "k1_sigma_fused": out[4], "k1_sigma_plain": out[5], "k2_sigma_fused": out[6], "k2_sigma_plain": out[7]}
 
@@ -327,7 +347,7 @@ def magsac_table(nu):
     lib = _abi.load_library()
     n = lib.gsfm_magsac_table(int(nu), None, 0)
     out = np.empty(n)
-    lib.gsfm_magsac_table(int(nu), _dp(out), n)
+    lib.gsfm_magsac_table(int(nu), _p(out), n)
     return out
 
 
@@ -346,9 +366,9 @@ def edge_sq_norms(n_cams, edge_i, edge_j, rel_aa, rot_aa, cov6=None, max_sq_norm
     s = np.empty(n_edges)
     keep = np.empty(n_edges, dtype=np.uint8) if max_sq_norm is not None else None
     kept, ms = C.c_uint64(0), C.c_double(0)
-    st = lib.gsfm_rot_edge_sq_norms(int(n_cams), int(n_edges), _u32p(ei), _u32p(ej), _dp(rel), _dp(c6), _dp(rot),
-                                    float(max_sq_norm if max_sq_norm is not None else -1.0), _dp(s),
-                                    keep.ctypes.data_as(C.POINTER(C.c_uint8)) if keep is not None else None, C.byref(kept), C.byref(ms))
+    st = lib.gsfm_rot_edge_sq_norms(int(n_cams), int(n_edges), _p(ei), _p(ej), _p(rel), _p(c6), _p(rot),
+                                    float(max_sq_norm if max_sq_norm is not None else -1.0), _p(s),
+                                    _p(keep), C.byref(kept), C.byref(ms))
     _raise_if_failed(lib, "gsfm_rot_edge_sq_norms", st)
     return {"s": s, "keep": None if keep is None else keep.astype(bool), "n_kept": int(kept.value), "kernel_ms": ms.value}
 
@@ -370,9 +390,9 @@ def orientations_from_maximum_spanning_tree(n_cams, edge_i, edge_j, rel_aa, weig
     rot = np.empty((n, 3))
     parent = np.empty(n, dtype=np.int64)
     root, n_tree, depth, ms = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_double(0)
-    st = lib.gsfm_rot_init_spanning_tree(n, int(n_edges), _u32p(ei), _u32p(ej), _dp(rel),
-                                         None if wt is None else wt.ctypes.data_as(C.POINTER(C.c_int32)), _dp(rot),
-                                         parent.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(root), C.byref(n_tree), C.byref(depth), C.byref(ms))
+    st = lib.gsfm_rot_init_spanning_tree(n, int(n_edges), _p(ei), _p(ej), _p(rel),
+                                         _p(wt), _p(rot),
+                                         _p(parent), C.byref(root), C.byref(n_tree), C.byref(depth), C.byref(ms))
     _raise_if_failed(lib, "gsfm_rot_init_spanning_tree", st)
     return {"rot_aa": rot, "parent_edge": parent, "root": int(root.value), "n_tree_cams": int(n_tree.value), "depth": int(depth.value),
             "kernel_ms": ms.value}
@@ -405,9 +425,9 @@ def filter_relative_translations(n_cams, edge_i, edge_j, rel_t, rot_aa, num_iter
     proj = np.empty((E, Kc)) if want_projections else None
     passes, picks = np.zeros(Kc, dtype=np.uint32), np.zeros(Kc, dtype=np.uint32)
     kept, ms = C.c_uint64(0), C.c_double(0)
-    st = lib.gsfm_pos_filter_relative_translations(n, E, _u32p(ei), _u32p(ej), _dp(rel), _dp(rot), K, _dp(ax), int(seed), float(tolerance),
-                                                   _dp(bad), keep.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(kept), _dp(stats), _dp(axes_out),
-                                                   _dp(proj), _u32p(passes), _u32p(picks), C.byref(ms))
+    st = lib.gsfm_pos_filter_relative_translations(n, E, _p(ei), _p(ej), _p(rel), _p(rot), K, _p(ax), int(seed), float(tolerance),
+                                                   _p(bad), _p(keep), C.byref(kept), _p(stats), _p(axes_out),
+                                                   _p(proj), _p(passes), _p(picks), C.byref(ms))
     _raise_if_failed(lib, "gsfm_pos_filter_relative_translations", st)
     return keep.astype(bool), {"bad_weight": bad, "n_kept": int(kept.value), "mean": stats[:3].copy(), "variance": stats[3:].copy(), "axes": axes_out,
                                "projections": proj, "num_passes": passes, "num_picks": picks, "kernel_ms": ms.value}
@@ -437,12 +457,40 @@ def refine_relative_translations(n_cams, edge_i, edge_j, match_ptr, matches, int
     status, iters = np.zeros(E, dtype=np.int32), np.zeros(E, dtype=np.int32)
     cost = np.zeros(E)
     ms = C.c_double(0)
-    i32p = C.POINTER(C.c_int32)
-    st = lib.gsfm_pos_refine_relative_translations(n, E, _u32p(ei), _u32p(ej), mp.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(m), _dp(K), _dp(rot),
-                                                   _dp(rel), _dp(out), status.ctypes.data_as(i32p), iters.ctypes.data_as(i32p), _dp(cost),
+    st = lib.gsfm_pos_refine_relative_translations(n, E, _p(ei), _p(ej), _p(mp), _p(m), _p(K), _p(rot), _p(rel), _p(out), _p(status), _p(iters), _p(cost),
                                                    C.byref(ms))
     _raise_if_failed(lib, "gsfm_pos_refine_relative_translations", st)
     return out, {"status": status, "iterations": iters, "cost": cost, "kernel_ms": ms.value}
+
+
+def _track_arrays(cameras, track_ptr, obs_cam, obs_xy, cam_estimated=None, point_estimated=None, points=None, per=("camera", "track")):
+    """What every entry over cameras and a track CSR takes, as contiguous arrays with the shapes checked.  cameras: (name, N x 3 array) pairs
+    that must agree in N; points: T x 3 or None; per: the nouns in the messages of the flag arrays.
+    Returns (camera arrays, track_ptr, obs_cam, obs_xy, camera flags or None, point flags or None, points or None)."""
+    cams = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 3) for _, a in cameras]
+    tp = np.ascontiguousarray(track_ptr, dtype=np.uint64).reshape(-1)
+    oc = np.ascontiguousarray(obs_cam, dtype=np.uint32).reshape(-1)
+    xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
+    pts = None if points is None else np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    if any(c.shape[0] != cams[0].shape[0] for c in cams):
+        names = [name for name, _ in cameras]
+        raise ValueError("%s and %s must describe the same cameras" % (", ".join(names[:-1]), names[-1]))
+    if tp.shape[0] < 1 or xy.shape[0] != oc.shape[0]:
+        raise ValueError("track_ptr needs n_tracks + 1 entries, and obs_cam and obs_xy one row per observation")
+    if int(tp.max()) > oc.shape[0]:
+        raise ValueError("track_ptr points past the end of the observations")
+    T = tp.shape[0] - 1
+    if pts is not None and pts.shape[0] != T:
+        raise ValueError("points needs one row per track")
+
+    def flags(a, count, what, noun):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8).reshape(-1)
+        if a.shape[0] != count:
+            raise ValueError("%s needs one flag per %s" % (what, noun))
+        return a
+    return cams, tp, oc, xy, flags(cam_estimated, cams[0].shape[0], "cam_estimated", per[0]), flags(point_estimated, T, "point_estimated", per[1]), pts
 
 
 def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated=None, min_triangulation_angle_degrees=4.0,
@@ -461,38 +509,17 @@ def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, 
     lib = _abi.load_library()
     if refine_options and not refine:
         raise TypeError("refinement options without refine=True: %s" % sorted(refine_options))
-    rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(-1, 3)
-    n = rot.shape[0]
-    pos = np.ascontiguousarray(cam_pos, dtype=np.float64).reshape(-1, 3)
-    K = np.ascontiguousarray(intrinsics, dtype=np.float64).reshape(-1, 3)
-    tp = np.ascontiguousarray(track_ptr, dtype=np.uint64).reshape(-1)
-    oc = np.ascontiguousarray(obs_cam, dtype=np.uint32).reshape(-1)
-    xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
-    if pos.shape[0] != n or K.shape[0] != n:
-        raise ValueError("rot_aa, cam_pos and intrinsics must describe the same cameras")
-    if tp.shape[0] < 1 or xy.shape[0] != oc.shape[0]:
-        raise ValueError("track_ptr needs n_tracks + 1 entries, and obs_cam and obs_xy one row per observation")
+    (rot, pos, K), tp, oc, xy, est, _, _ = _track_arrays((("rot_aa", rot_aa), ("cam_pos", cam_pos), ("intrinsics", intrinsics)), track_ptr, obs_cam, obs_xy,
+                                                         cam_estimated)
     T = tp.shape[0] - 1
-    if int(tp.max()) > oc.shape[0]:
-        raise ValueError("track_ptr points past the end of the observations")
-    est = None
-    if cam_estimated is not None:
-        est = np.ascontiguousarray(np.asarray(cam_estimated) != 0, dtype=np.uint8).reshape(-1)
-        if est.shape[0] != n:
-            raise ValueError("cam_estimated needs one flag per camera")
-    points, status, n_views = np.zeros((T, 3)), np.zeros(T, dtype=np.int32), np.zeros(T, dtype=np.int32)
-    ms = C.c_double(0)
-    i32p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    points, status, n_views, err = np.zeros((T, 3)), np.zeros(T, dtype=np.int32), np.zeros(T, dtype=np.int32), np.zeros(T)
+    counts, ms = np.zeros(7 if refine else 6, dtype=np.uint64), C.c_double(0)
+    scene = (rot.shape[0], _p(rot), _p(pos), _p(K), _p(est), T, _p(tp), _p(oc), _p(xy), float(min_triangulation_angle_degrees),
+             float(max_reprojection_error_pixels))
+    out = (_p(points), _p(status), _p(n_views), _p(err))
+    more = {}
     if refine:
-        if loss is None:
-            nodes = []
-        elif isinstance(loss, (list, tuple)):
-            nodes = list(loss)
-        elif hasattr(loss, "native_program") and loss.native_program() is not None:
-            nodes = loss.native_program()
-        else:
-            raise TypeError("the track refinement needs a loss with a native descriptor, got %r" % (loss,))
-        prog, n_nodes = _abi.make_program(nodes)
+        prog, n_nodes = _abi.make_program(_loss_nodes(loss, "track refinement"))
         opt = _abi.TrackRefineOptions()
         lib.gsfm_tracks_refine_default_options(C.byref(opt))
         opt.refine, opt.max_num_iterations = 1, int(max_num_iterations)
@@ -500,24 +527,13 @@ def triangulate_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, 
             if name not in [f for f, _ in _abi.TrackRefineOptions._fields_]:
                 raise TypeError("gsfm_tracks_refine_options has no field %r" % name)
             setattr(opt, name, value)
-        err, counts = np.zeros(T), np.zeros(7, dtype=np.uint64)
-        iters, term = np.zeros(T, dtype=np.int32), np.full(T, -1, dtype=np.int32)
-        cost0, cost1 = np.zeros(T), np.zeros(T)
-        st = lib.gsfm_tracks_triangulate_refine(n, _dp(rot), _dp(pos), _dp(K), None if est is None else est.ctypes.data_as(C.POINTER(C.c_uint8)), T,
-                                                tp.ctypes.data_as(u64p), _u32p(oc), _dp(xy), float(min_triangulation_angle_degrees),
-                                                float(max_reprojection_error_pixels), C.byref(opt), prog, n_nodes, _dp(points),
-                                                status.ctypes.data_as(i32p), n_views.ctypes.data_as(i32p), _dp(err), iters.ctypes.data_as(i32p),
-                                                _dp(cost0), _dp(cost1), term.ctypes.data_as(i32p), counts.ctypes.data_as(u64p), C.byref(ms))
+        iters, term, cost0, cost1 = np.zeros(T, dtype=np.int32), np.full(T, -1, dtype=np.int32), np.zeros(T), np.zeros(T)
+        st = lib.gsfm_tracks_triangulate_refine(*scene, C.byref(opt), prog, n_nodes, *out, _p(iters), _p(cost0), _p(cost1), _p(term), _p(counts), C.byref(ms))
         _raise_if_failed(lib, "gsfm_tracks_triangulate_refine", st)
-        return {"points": points, "status": status, "n_views": n_views, "mean_sq_err": err, "counts": counts, "kernel_ms": ms.value,
-                "iterations": iters, "initial_cost": cost0, "final_cost": cost1, "termination": term}
-    err, counts = np.zeros(T), np.zeros(6, dtype=np.uint64)
-    st = lib.gsfm_tracks_triangulate(n, _dp(rot), _dp(pos), _dp(K), None if est is None else est.ctypes.data_as(C.POINTER(C.c_uint8)), T,
-                                     tp.ctypes.data_as(u64p), _u32p(oc), _dp(xy), float(min_triangulation_angle_degrees),
-                                     float(max_reprojection_error_pixels), _dp(points), status.ctypes.data_as(i32p), n_views.ctypes.data_as(i32p),
-                                     _dp(err), counts.ctypes.data_as(u64p), C.byref(ms))
-    _raise_if_failed(lib, "gsfm_tracks_triangulate", st)
-    return {"points": points, "status": status, "n_views": n_views, "mean_sq_err": err, "counts": counts, "kernel_ms": ms.value}
+        more = {"iterations": iters, "initial_cost": cost0, "final_cost": cost1, "termination": term}
+    else:
+        _raise_if_failed(lib, "gsfm_tracks_triangulate", lib.gsfm_tracks_triangulate(*scene, *out, _p(counts), C.byref(ms)))
+    return dict({"points": points, "status": status, "n_views": n_views, "mean_sq_err": err, "counts": counts, "kernel_ms": ms.value}, **more)
 
 
 def outlier_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, points, cam_estimated=None, point_estimated=None,
@@ -529,41 +545,15 @@ def outlier_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, poin
     Returns dict(status (0 kept, 1 not estimated on input, 2 behind a camera, 3 reprojection error, 4 insufficient viewing angle), n_views,
     mean_sq_err, counts (5), kernel_ms)."""
     lib = _abi.load_library()
-    rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(-1, 3)
-    n = rot.shape[0]
-    pos = np.ascontiguousarray(cam_pos, dtype=np.float64).reshape(-1, 3)
-    K = np.ascontiguousarray(intrinsics, dtype=np.float64).reshape(-1, 3)
-    tp = np.ascontiguousarray(track_ptr, dtype=np.uint64).reshape(-1)
-    oc = np.ascontiguousarray(obs_cam, dtype=np.uint32).reshape(-1)
-    xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
-    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
-    if pos.shape[0] != n or K.shape[0] != n:
-        raise ValueError("rot_aa, cam_pos and intrinsics must describe the same cameras")
-    if tp.shape[0] < 1 or xy.shape[0] != oc.shape[0]:
-        raise ValueError("track_ptr needs n_tracks + 1 entries, and obs_cam and obs_xy one row per observation")
+    (rot, pos, K), tp, oc, xy, est, pest, pts = _track_arrays((("rot_aa", rot_aa), ("cam_pos", cam_pos), ("intrinsics", intrinsics)), track_ptr, obs_cam,
+                                                              obs_xy, cam_estimated, point_estimated, points=points)
     T = tp.shape[0] - 1
-    if int(tp.max()) > oc.shape[0]:
-        raise ValueError("track_ptr points past the end of the observations")
-    if pts.shape[0] != T:
-        raise ValueError("points needs one row per track")
-    u8p = C.POINTER(C.c_uint8)
-    est = pest = None
-    if cam_estimated is not None:
-        est = np.ascontiguousarray(np.asarray(cam_estimated) != 0, dtype=np.uint8).reshape(-1)
-        if est.shape[0] != n:
-            raise ValueError("cam_estimated needs one flag per camera")
-    if point_estimated is not None:
-        pest = np.ascontiguousarray(np.asarray(point_estimated) != 0, dtype=np.uint8).reshape(-1)
-        if pest.shape[0] != T:
-            raise ValueError("point_estimated needs one flag per track")
     status, n_views = np.zeros(T, dtype=np.int32), np.zeros(T, dtype=np.int32)
     err, counts = np.zeros(T), np.zeros(5, dtype=np.uint64)
     ms = C.c_double(0)
-    i32p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
-    st = lib.gsfm_tracks_outlier_tracks(n, _dp(rot), _dp(pos), _dp(K), None if est is None else est.ctypes.data_as(u8p), T, tp.ctypes.data_as(u64p),
-                                        _u32p(oc), _dp(xy), _dp(pts), None if pest is None else pest.ctypes.data_as(u8p),
-                                        float(max_reprojection_error_pixels), float(min_triangulation_angle_degrees), status.ctypes.data_as(i32p),
-                                        n_views.ctypes.data_as(i32p), _dp(err), counts.ctypes.data_as(u64p), C.byref(ms))
+    st = lib.gsfm_tracks_outlier_tracks(rot.shape[0], _p(rot), _p(pos), _p(K), _p(est), T, _p(tp), _p(oc), _p(xy), _p(pts), _p(pest),
+                                        float(max_reprojection_error_pixels), float(min_triangulation_angle_degrees), _p(status), _p(n_views), _p(err),
+                                        _p(counts), C.byref(ms))
     _raise_if_failed(lib, "gsfm_tracks_outlier_tracks", st)
     return {"status": status, "n_views": n_views, "mean_sq_err": err, "counts": counts, "kernel_ms": ms.value}
 
@@ -571,11 +561,10 @@ def outlier_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, poin
 def track_launch_order(track_ptr):
     """gsfm_tracks_launch_order (host code): (order, class_begin) -- the tracks by lane class 4, 16, 64, longest first inside a class."""
     lib = _abi.load_library()
-    tp = np.ascontiguousarray(track_ptr, dtype=np.uint64).reshape(-1)
+    tp = np.ascontiguousarray(track_ptr, dtype=np.uint64).reshape(-1)   # (no observations here: _track_arrays does not fit)
     T = tp.shape[0] - 1
     order, begin = np.zeros(T, dtype=np.uint32), np.zeros(4, dtype=np.uint64)
-    u64p = C.POINTER(C.c_uint64)
-    st = lib.gsfm_tracks_launch_order(T, tp.ctypes.data_as(u64p), _u32p(order), begin.ctypes.data_as(u64p))
+    st = lib.gsfm_tracks_launch_order(T, _p(tp), _p(order), _p(begin))
     _raise_if_failed(lib, "gsfm_tracks_launch_order", st)
     return order, begin
 
@@ -596,7 +585,7 @@ class PositionProblem(ProblemBase):
         if not (ei.shape == ej.shape == (rel.shape[0],)):
             raise ValueError("edge_i, edge_j and rel_t must describe the same edges")
         h = C.c_void_p()
-        st = lib.gsfm_pos_problem_create(int(n_cams), ei.size, _u32p(ei), _u32p(ej), _dp(rel), _dp(rot), C.byref(h))
+        st = lib.gsfm_pos_problem_create(int(n_cams), ei.size, _p(ei), _p(ej), _p(rel), _p(rot), C.byref(h))
         _raise_if_failed(lib, "gsfm_pos_problem_create", st)
         ProblemBase.__init__(self, lib, h, n_cams, ei.size, -1, 3)
 
@@ -614,7 +603,7 @@ class PositionProblem(ProblemBase):
         pos = np.zeros((self.n_cams, 3)) if init is None else np.array(init, dtype=np.float64, order="C").reshape(self.n_cams, 3)
         o = self._options(options)
         s = _abi.PosSummary()
-        st = self._lib.gsfm_pos_solve(self._h, _dp(pos), int(fixed_cam), C.byref(o), C.byref(s))
+        st = self._lib.gsfm_pos_solve(self._h, _p(pos), int(fixed_cam), C.byref(o), C.byref(s))
         self._check(st, "solve")
         return pos, s.as_dict()
 
@@ -623,7 +612,7 @@ class PositionProblem(ProblemBase):
         pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(self.n_cams, 3)
         r = np.empty((self.n_edges, 3))
         rho = np.empty(self.n_edges)
-        st = self._lib.gsfm_pos_residuals(self._h, _dp(pos), _dp(r), _dp(rho))
+        st = self._lib.gsfm_pos_residuals(self._h, _p(pos), _p(r), _p(rho))
         self._check(st, "residuals")
         return r, rho
 
@@ -640,8 +629,8 @@ class PositionProblem(ProblemBase):
         b, y, delta = np.empty((self.n_cams, 3)), np.empty((self.n_cams, 3)), np.empty((self.n_cams, 3))
         scal = np.empty(4)
         info = np.zeros(3, dtype=np.int32)
-        st = self._lib.gsfm_pos_step_check(self._h, _dp(pos), int(fixed_cam), float(radius), C.byref(o), None if K is None else _dp(K),
-                                           _dp(b), _dp(y), _dp(delta), _dp(scal), info.ctypes.data_as(C.POINTER(C.c_int32)))
+        st = self._lib.gsfm_pos_step_check(self._h, _p(pos), int(fixed_cam), float(radius), C.byref(o), None if K is None else _p(K),
+                                           _p(b), _p(y), _p(delta), _p(scal), _p(info))
         self._check(st, "step_check")
         return {"K": K if info[1] >= 0 else None, "b": b, "y": y, "delta": delta,
                 "model_cost_change": scal[0], "dg": scal[1], "dld": scal[2], "cg_rel": scal[3], "path": int(info[0]),
@@ -651,80 +640,29 @@ class PositionProblem(ProblemBase):
         raise NotImplementedError("position residuals have weight 1 (the reference's BASELINE error)")
 
 
-class _BundleProblemBase(object):
-    """What BundleProblem and FullBundleProblem share: the handle, the loss, the options, the argument arrays.  A subclass sets _PREFIX (the
-    C prefix of its entry points), creates the problem in __init__ and ends it with self._adopt(lib, handle, n_cams, n_tracks, n_obs)."""
-    _PREFIX = None
-    _h = None
+_PER_ENTRY = ("entry", "entry")   # the bundle classes' wording for both flag arrays
 
+
+class _BundleProblemBase(_Handle):
+    """What BundleProblem and FullBundleProblem share: the handle, the loss, the options, the argument arrays.  A subclass sets _prefix (the
+    C prefix of its entry points), creates the problem in __init__ and ends it with self._adopt(lib, handle, n_cams, n_tracks, n_obs)."""
     def _adopt(self, lib, handle, n_cams, n_tracks, n_obs):
         self._lib, self._h = lib, handle
         self.n_cams, self.n_tracks, self.n_obs = n_cams, n_tracks, n_obs
-
-    def _fn(self, name):
-        return getattr(self._lib, self._PREFIX + name)
-
-    @staticmethod
-    def _track_arrays(intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated):
-        """(K, track_ptr, obs_cam, obs_xy, cam flags or None, point flags or None) as contiguous arrays, shapes checked"""
-        K = np.ascontiguousarray(intrinsics, dtype=np.float64).reshape(-1, 3)
-        tp = np.ascontiguousarray(track_ptr, dtype=np.uint64).reshape(-1)
-        oc = np.ascontiguousarray(obs_cam, dtype=np.uint32).reshape(-1)
-        xy = np.ascontiguousarray(obs_xy, dtype=np.float64).reshape(-1, 2)
-        if tp.shape[0] < 1 or xy.shape[0] != oc.shape[0]:
-            raise ValueError("track_ptr needs n_tracks + 1 entries, and obs_cam and obs_xy one row per observation")
-        if int(tp.max()) > oc.shape[0]:
-            raise ValueError("track_ptr points past the end of the observations")
-
-        def flags(a, count, what):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8).reshape(-1)
-            if a.shape[0] != count:
-                raise ValueError("%s needs one flag per entry" % what)
-            return a
-        return K, tp, oc, xy, flags(cam_estimated, K.shape[0], "cam_estimated"), flags(point_estimated, tp.shape[0] - 1, "point_estimated")
 
     def _check(self, st, what):
         if st != 0:
             raise SolverError("%s failed with status %d: %s" % (what, st, self._lib.gsfm_last_error().decode("utf-8", "replace")))
 
-    def close(self):
-        if self._h is not None:
-            self._fn("problem_destroy")(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_loss(self, loss):
         """loss: None (Ceres' NULL loss), a list of (kind, p0, p1, p2) nodes or an object with .native_program(); one Trivial / Huber /
         SoftLOne / Tukey / GemanMcClure leaf."""
-        if loss is None:
-            nodes = []
-        elif isinstance(loss, (list, tuple)):
-            nodes = list(loss)
-        elif hasattr(loss, "native_program") and loss.native_program() is not None:
-            nodes = loss.native_program()
-        else:
-            raise TypeError("the bundle adjustment needs a loss with a native descriptor, got %r" % (loss,))
-        arr, n = _abi.make_program(nodes)
+        arr, n = _abi.make_program(_loss_nodes(loss, "bundle adjustment"))
         self._check(self._fn("set_loss")(self._h, arr, n), "set_loss")
 
     def default_options(self):
         o = _abi.BaOptions()
         self._fn("options_default")(C.byref(o))
-        return o
-
-    def _options(self, kw):
-        o = self.default_options()
-        for k, v in kw.items():
-            if not hasattr(o, k):
-                raise TypeError("unknown solver option %r" % k)
-            setattr(o, k, v)
         return o
 
     def _point(self, cam_pos, points):
@@ -737,20 +675,17 @@ class BundleProblem(_BundleProblemBase):
     BundleAdjustCameraPositionsAndPoints on the device, the points eliminated and the reduced camera system solved by PCG.
     rot_aa: N x 3, intrinsics: N x 3 (f u v); track_ptr / obs_cam / obs_xy: the track CSR of triangulate_tracks; cam_estimated (N) and
     point_estimated (T): flags or None (all estimated).  A new problem has Ceres' NULL loss."""
-    _PREFIX = "gsfm_ba_"
+    _prefix = "gsfm_ba_"
 
     def __init__(self, rot_aa, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated=None, point_estimated=None):
         lib = _abi.load_library()
         rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(-1, 3)
-        K, tp, oc, xy, ce, pe = self._track_arrays(intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated)
+        (K,), tp, oc, xy, ce, pe, _ = _track_arrays((("intrinsics", intrinsics),), track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated, per=_PER_ENTRY)
         n, T = rot.shape[0], tp.shape[0] - 1
-        if K.shape[0] != n:
+        if K.shape[0] != n:   # (after the track arrays, as ever)
             raise ValueError("rot_aa and intrinsics must describe the same cameras")
-        u8p = C.POINTER(C.c_uint8)
         h = C.c_void_p()
-        st = lib.gsfm_ba_problem_create(n, _dp(rot), _dp(K), None if ce is None else ce.ctypes.data_as(u8p), T,
-                                        tp.ctypes.data_as(C.POINTER(C.c_uint64)), _u32p(oc), _dp(xy),
-                                        None if pe is None else pe.ctypes.data_as(u8p), C.byref(h))
+        st = lib.gsfm_ba_problem_create(n, _p(rot), _p(K), _p(ce), T, _p(tp), _p(oc), _p(xy), _p(pe), C.byref(h))
         _raise_if_failed(lib, "gsfm_ba_problem_create", st)
         self._adopt(lib, h, n, T, int(oc.shape[0]))
 
@@ -758,14 +693,14 @@ class BundleProblem(_BundleProblemBase):
         """Returns (camera positions N x 3, points T x 3, summary dict); inactive and unestimated rows are returned as given."""
         c, p = self._point(cam_pos, points)
         o, s = self._options(options), _abi.BaSummary()
-        self._check(self._lib.gsfm_ba_solve(self._h, _dp(c), _dp(p), C.byref(o), C.byref(s)), "solve")
+        self._check(self._lib.gsfm_ba_solve(self._h, _p(c), _p(p), C.byref(o), C.byref(s)), "solve")
         return c, p, s.as_dict()
 
     def residuals(self, cam_pos, points):
         """(r: n_obs x 2, rho: n_obs); zeros for an unused observation"""
         c, p = self._point(cam_pos, points)
         r, rho = np.zeros((self.n_obs, 2)), np.zeros(self.n_obs)
-        self._check(self._lib.gsfm_ba_residuals(self._h, _dp(c), _dp(p), _dp(r), _dp(rho)), "residuals")
+        self._check(self._lib.gsfm_ba_residuals(self._h, _p(c), _p(p), _p(r), _p(rho)), "residuals")
         return r, rho
 
     def linearize(self, cam_pos, points):
@@ -774,7 +709,7 @@ class BundleProblem(_BundleProblemBase):
         cost = np.zeros(1)
         gc, gp = np.zeros((self.n_cams, 3)), np.zeros((self.n_tracks, 3))
         dc, dp = np.zeros((self.n_cams, 3, 3)), np.zeros((self.n_tracks, 3, 3))
-        self._check(self._lib.gsfm_ba_linearize(self._h, _dp(c), _dp(p), _dp(cost), _dp(gc), _dp(gp), _dp(dc), _dp(dp)), "linearize")
+        self._check(self._lib.gsfm_ba_linearize(self._h, _p(c), _p(p), _p(cost), _p(gc), _p(gp), _p(dc), _p(dp)), "linearize")
         return {"cost": float(cost[0]), "grad_cam": gc, "grad_point": gp, "diag_cam": dc, "diag_point": dp}
 
     def schur_matvec(self, v, radius=1e4, **options):
@@ -782,7 +717,7 @@ class BundleProblem(_BundleProblemBase):
         v = np.ascontiguousarray(v, dtype=np.float64).reshape(self.n_cams, 3)
         y = np.zeros((self.n_cams, 3))
         o = self._options(options)
-        self._check(self._lib.gsfm_ba_schur_matvec(self._h, _dp(v), float(radius), C.byref(o), _dp(y)), "schur_matvec")
+        self._check(self._lib.gsfm_ba_schur_matvec(self._h, _p(v), float(radius), C.byref(o), _p(y)), "schur_matvec")
         return y
 
     def step_check(self, cam_pos, points, radius=1e4, **options):
@@ -792,8 +727,8 @@ class BundleProblem(_BundleProblemBase):
         N, T = self.n_cams, self.n_tracks
         rhs, yc, yp, dc, dp = np.zeros((N, 3)), np.zeros((N, 3)), np.zeros((T, 3)), np.zeros((N, 3)), np.zeros((T, 3))
         scal, info = np.zeros(4), np.zeros(2, dtype=np.int32)
-        st = self._lib.gsfm_ba_step_check(self._h, _dp(c), _dp(p), float(radius), C.byref(o), _dp(rhs), _dp(yc), _dp(yp), _dp(dc), _dp(dp), _dp(scal),
-                                          info.ctypes.data_as(C.POINTER(C.c_int32)))
+        st = self._lib.gsfm_ba_step_check(self._h, _p(c), _p(p), float(radius), C.byref(o), _p(rhs), _p(yc), _p(yp), _p(dc), _p(dp), _p(scal),
+                                          _p(info))
         self._check(st, "step_check")
         return {"rhs": rhs, "y_cam": yc, "y_point": yp, "delta_cam": dc, "delta_point": dp, "model_cost_change": scal[0], "dg": scal[1],
                 "dld": scal[2], "cg_rel": scal[3], "cg_iterations": int(info[0]), "stalled": bool(info[1])}
@@ -803,7 +738,7 @@ class BundleProblem(_BundleProblemBase):
         """mean device microseconds of the kernels of one linearisation and one Schur product (gsfm_ba_time_kernels)"""
         c, p = self._point(cam_pos, points)
         out = np.zeros(6)
-        self._check(self._lib.gsfm_ba_time_kernels(self._h, _dp(c), _dp(p), float(radius), int(reps), _dp(out)), "time_kernels")
+        self._check(self._lib.gsfm_ba_time_kernels(self._h, _p(c), _p(p), float(radius), int(reps), _p(out)), "time_kernels")
         return dict(zip(("lin_tracks", "lin_cameras", "cost", "point_pass", "camera_pass", "preconditioner"), out))
 
 
@@ -822,16 +757,14 @@ class FullBundleProblem(_BundleProblemBase):
     """The full bundle adjustment (include/gsfm_ba6.h): Theia's GlobalReconstructionEstimator::BundleAdjustment on the device, camera
     orientations, camera positions and points moving together (intrinsics held), the points eliminated and the reduced 6 x 6-block camera
     system solved by PCG.  The arguments are BundleProblem's without rot_aa: the orientations are a start value of solve()."""
-    _PREFIX = "gsfm_ba6_"
+    _prefix = "gsfm_ba6_"
 
     def __init__(self, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated=None, point_estimated=None):
         lib = _abi.load_library()
-        K, tp, oc, xy, ce, pe = self._track_arrays(intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated)
+        (K,), tp, oc, xy, ce, pe, _ = _track_arrays((("intrinsics", intrinsics),), track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated, per=_PER_ENTRY)
         n, T = K.shape[0], tp.shape[0] - 1
-        u8p = C.POINTER(C.c_uint8)
         h = C.c_void_p()
-        st = lib.gsfm_ba6_problem_create(n, _dp(K), None if ce is None else ce.ctypes.data_as(u8p), T, tp.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                         _u32p(oc), _dp(xy), None if pe is None else pe.ctypes.data_as(u8p), C.byref(h))
+        st = lib.gsfm_ba6_problem_create(n, _p(K), _p(ce), T, _p(tp), _p(oc), _p(xy), _p(pe), C.byref(h))
         _raise_if_failed(lib, "gsfm_ba6_problem_create", st)
         self._adopt(lib, h, n, T, int(oc.shape[0]))
 
@@ -842,14 +775,14 @@ class FullBundleProblem(_BundleProblemBase):
         """Returns (orientations N x 3, camera positions N x 3, points T x 3, summary dict); inactive and unestimated rows are returned as given."""
         w, c, p = self._point6(rot_aa, cam_pos, points)
         o, s = self._options(options), _abi.BaSummary()
-        self._check(self._lib.gsfm_ba6_solve(self._h, _dp(w), _dp(c), _dp(p), C.byref(o), C.byref(s)), "solve")
+        self._check(self._lib.gsfm_ba6_solve(self._h, _p(w), _p(c), _p(p), C.byref(o), C.byref(s)), "solve")
         return w, c, p, s.as_dict()
 
     def residuals(self, rot_aa, cam_pos, points):
         """(r: n_obs x 2, rho: n_obs); zeros for an unused observation"""
         w, c, p = self._point6(rot_aa, cam_pos, points)
         r, rho = np.zeros((self.n_obs, 2)), np.zeros(self.n_obs)
-        self._check(self._lib.gsfm_ba6_residuals(self._h, _dp(w), _dp(c), _dp(p), _dp(r), _dp(rho)), "residuals")
+        self._check(self._lib.gsfm_ba6_residuals(self._h, _p(w), _p(c), _p(p), _p(r), _p(rho)), "residuals")
         return r, rho
 
     def linearize(self, rot_aa, cam_pos, points):
@@ -858,7 +791,7 @@ class FullBundleProblem(_BundleProblemBase):
         cost = np.zeros(1)
         gr, gc, gp = np.zeros((self.n_cams, 3)), np.zeros((self.n_cams, 3)), np.zeros((self.n_tracks, 3))
         dc, dp = np.zeros((self.n_cams, 6, 6)), np.zeros((self.n_tracks, 3, 3))
-        self._check(self._lib.gsfm_ba6_linearize(self._h, _dp(w), _dp(c), _dp(p), _dp(cost), _dp(gr), _dp(gc), _dp(gp), _dp(dc), _dp(dp)), "linearize")
+        self._check(self._lib.gsfm_ba6_linearize(self._h, _p(w), _p(c), _p(p), _p(cost), _p(gr), _p(gc), _p(gp), _p(dc), _p(dp)), "linearize")
         return {"cost": float(cost[0]), "grad_rot": gr, "grad_pos": gc, "grad_point": gp, "diag_cam": dc, "diag_point": dp}
 
     def schur_matvec(self, v, radius=1e4, **options):
@@ -866,7 +799,7 @@ class FullBundleProblem(_BundleProblemBase):
         v = np.ascontiguousarray(v, dtype=np.float64).reshape(self.n_cams, 6)
         y = np.zeros((self.n_cams, 6))
         o = self._options(options)
-        self._check(self._lib.gsfm_ba6_schur_matvec(self._h, _dp(v), float(radius), C.byref(o), _dp(y)), "schur_matvec")
+        self._check(self._lib.gsfm_ba6_schur_matvec(self._h, _p(v), float(radius), C.byref(o), _p(y)), "schur_matvec")
         return y
 
     def step_check(self, rot_aa, cam_pos, points, radius=1e4, **options):
@@ -878,8 +811,8 @@ class FullBundleProblem(_BundleProblemBase):
         rhs, yc, yp = np.zeros((N, 6)), np.zeros((N, 6)), np.zeros((T, 3))
         dr, dc, dp, jd = np.zeros((N, 3)), np.zeros((N, 3)), np.zeros((T, 3)), np.zeros((self.n_obs, 2))
         scal, info = np.zeros(4), np.zeros(2, dtype=np.int32)
-        st = self._lib.gsfm_ba6_step_check(self._h, _dp(w), _dp(c), _dp(p), float(radius), C.byref(o), _dp(rhs), _dp(yc), _dp(yp), _dp(dr), _dp(dc), _dp(dp),
-                                           _dp(jd), _dp(scal), info.ctypes.data_as(C.POINTER(C.c_int32)))
+        st = self._lib.gsfm_ba6_step_check(self._h, _p(w), _p(c), _p(p), float(radius), C.byref(o), _p(rhs), _p(yc), _p(yp), _p(dr), _p(dc), _p(dp),
+                                           _p(jd), _p(scal), _p(info))
         self._check(st, "step_check")
         return {"rhs": rhs, "y_cam": yc, "y_point": yp, "delta_rot": dr, "delta_pos": dc, "delta_point": dp, "j_delta": jd, "model_cost_change": scal[0],
                 "dg": scal[1], "jd2": scal[2], "cg_rel": scal[3], "cg_iterations": int(info[0]), "stalled": bool(info[1])}
@@ -888,7 +821,7 @@ class FullBundleProblem(_BundleProblemBase):
         """mean device microseconds of the kernels of one linearisation and one Schur product (gsfm_ba6_time_kernels)"""
         w, c, p = self._point6(rot_aa, cam_pos, points)
         out = np.zeros(8)
-        self._check(self._lib.gsfm_ba6_time_kernels(self._h, _dp(w), _dp(c), _dp(p), float(radius), int(reps), _dp(out)), "time_kernels")
+        self._check(self._lib.gsfm_ba6_time_kernels(self._h, _p(w), _p(c), _p(p), float(radius), int(reps), _p(out)), "time_kernels")
         return dict(zip(("camera_records", "lin_tracks", "lin_cameras", "cost", "point_pass", "camera_pass", "preconditioner", "quadratic_form"), out))
 
 

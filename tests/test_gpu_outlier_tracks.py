@@ -1,7 +1,8 @@
 """The outlier rule on the device (gsfm_tracks_outlier_tracks, include/gsfm_tracks.h) against the 50-digit restatement
 (tests/outlier_reference.py).  The mpmath results of the parity batch are read from tests/golden/outlier_tracks.json, which
 tests/test_outlier_reference.py recomputes and checks.  Also here: gsfm_tracks_triangulate and gsfm_tracks_triangulate_refine still return, byte for
-byte, what the commit before the angle sweep was factored out of tri_front returned on an MI355X (tests/golden/triangulation_parent_bytes.npz)."""
+byte, what the commit before the angle sweep was factored out of tri_front returned on an MI355X (tests/golden/triangulation_parent_bytes.npz),
+and gsfm_tracks_outlier_tracks what the commit before csrc/track_scene.hpp returned there (tests/golden/outlier_parent_bytes.npz)."""
 import json
 import math
 import os
@@ -19,6 +20,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "outlier_tracks.json")
 PARENT_BYTES = os.path.join(ROOT, "tests", "golden", "triangulation_parent_bytes.npz")
+OUTLIER_PARENT_BYTES = os.path.join(ROOT, "tests", "golden", "outlier_parent_bytes.npz")
 OUTPUTS = ("status", "n_views", "mean_sq_err")
 
 
@@ -192,3 +194,35 @@ def test_triangulation_entries_return_the_parent_commit_s_bytes():
     for k in ("points", "status", "n_views", "mean_sq_err", "counts", "iterations", "initial_cost", "final_cost", "termination"):
         assert got[k].dtype == want["refine_" + k].dtype and np.array_equal(raw(got[k]), raw(want["refine_" + k])), k
     assert int(want["tri_counts"][0]) >= 300 and int(want["refine_counts"][0]) >= 300
+
+
+def half_flagged(batch):
+    """the flags of test_another_track_s_flag_changes_nothing"""
+    T = len(batch["track_ptr"]) - 1
+    flags = batch["point_estimated"].copy()
+    flags[np.random.Generator(np.random.PCG64(78)).permutation(T)[:T // 2]] = 0
+    return flags
+
+
+def parent_bytes_cases(batch):
+    """(name, scene): the batch, the batch half flagged, and the batch's tracks of one lane class alone (two classes stay empty)"""
+    lanes = np.array([tri.lane_class(int(n)) for n in np.diff(batch["track_ptr"].astype(np.int64))])
+    yield "all", batch
+    yield "half", dict(batch, point_estimated=half_flagged(batch))
+    for g in (4, 16, 64):
+        yield "lanes%d" % g, permuted(batch, np.flatnonzero(lanes == g))
+
+
+def test_outlier_rule_returns_the_parent_commit_s_bytes(batch):
+    """recorded on an MI355X from a library built before the scene slab, the checks and the lane-class launcher moved to csrc/track_scene.hpp
+    (tools/make_track_scene_golden.py)"""
+    want = np.load(OUTLIER_PARENT_BYTES)
+    sizes = {}
+    for name, scene in parent_bytes_cases(batch):
+        got = run(scene)
+        sizes[name] = len(got["status"])
+        for k in OUTPUTS + ("counts",):
+            assert got[k].dtype == want[name + "_" + k].dtype and np.array_equal(raw(got[k]), raw(want[name + "_" + k])), (name, k)
+    T = sizes["all"]
+    assert min(sizes.values()) >= 20 and sizes["lanes4"] + sizes["lanes16"] + sizes["lanes64"] == T
+    assert int(want["half_counts"][1]) >= T // 2 and int(want["all_counts"][1]) == 1
