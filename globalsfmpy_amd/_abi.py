@@ -315,6 +315,7 @@ def load_library():
     declare_track_signatures(lib)
     declare_ba_signatures(lib)
     declare_ba6_signatures(lib)
+    declare_ba7_signatures(lib)
     _lib = lib
     return lib
 
@@ -396,3 +397,21 @@ def declare_ba6_signatures(lib):
     lib.gsfm_ba6_step_check.restype = C.c_int
     lib.gsfm_ba6_time_kernels.argtypes = [C.c_void_p, _DP, _DP, _DP, C.c_double, C.c_int32, _DP]; lib.gsfm_ba6_time_kernels.restype = C.c_int
     lib.gsfm_ba6_problem_destroy.argtypes = [C.c_void_p]; lib.gsfm_ba6_problem_destroy.restype = None
+
+
+def declare_ba7_signatures(lib):
+    """include/gsfm_ba7.h (the options and the summary are gsfm_ba.h's)"""
+    u8p, u64p, i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    lib.gsfm_ba7_abi_version.restype = C.c_int
+    lib.gsfm_ba7_options_default.argtypes = [C.POINTER(BaOptions)]; lib.gsfm_ba7_options_default.restype = None
+    lib.gsfm_ba7_problem_create.argtypes = [C.c_uint32, _DP, u8p, u8p, C.c_uint64, u64p, _U32P, _DP, u8p, C.POINTER(C.c_void_p)]
+    lib.gsfm_ba7_problem_create.restype = C.c_int
+    lib.gsfm_ba7_set_loss.argtypes = [C.c_void_p, C.POINTER(LossNode), C.c_int32]; lib.gsfm_ba7_set_loss.restype = C.c_int
+    lib.gsfm_ba7_solve.argtypes = [C.c_void_p, _DP, _DP, _DP, _DP, C.POINTER(BaOptions), C.POINTER(BaSummary)]; lib.gsfm_ba7_solve.restype = C.c_int
+    lib.gsfm_ba7_residuals.argtypes = [C.c_void_p] + [_DP] * 6; lib.gsfm_ba7_residuals.restype = C.c_int
+    lib.gsfm_ba7_linearize.argtypes = [C.c_void_p] + [_DP] * 11; lib.gsfm_ba7_linearize.restype = C.c_int
+    lib.gsfm_ba7_schur_matvec.argtypes = [C.c_void_p, _DP, C.c_double, C.POINTER(BaOptions), _DP]; lib.gsfm_ba7_schur_matvec.restype = C.c_int
+    lib.gsfm_ba7_step_check.argtypes = [C.c_void_p, _DP, _DP, _DP, _DP, C.c_double, C.POINTER(BaOptions)] + [_DP] * 9 + [i32p]
+    lib.gsfm_ba7_step_check.restype = C.c_int
+    lib.gsfm_ba7_time_kernels.argtypes = [C.c_void_p, _DP, _DP, _DP, _DP, C.c_double, C.c_int32, _DP]; lib.gsfm_ba7_time_kernels.restype = C.c_int
+    lib.gsfm_ba7_problem_destroy.argtypes = [C.c_void_p]; lib.gsfm_ba7_problem_destroy.restype = None

@@ -23,6 +23,7 @@
 #include "outlier_tracks.hpp"
 #include "solver_ba.hpp"
 #include "solver_ba6.hpp"
+#include "solver_ba7.hpp"
 
 // =============================================================================================
 extern "C" {

@@ -16,6 +16,7 @@
 #include "../../include/gsfm_tracks.h"
 #include "../../include/gsfm_ba.h"
 #include "../../include/gsfm_ba6.h"
+#include "../../include/gsfm_ba7.h"
 
 namespace gsfm {
 
@@ -196,6 +197,8 @@ void FlattenTracks(const theia::Reconstruction& rec, FlatTracks* out) {
     const double u = pp == tr.principal_point.end() ? 0.0 : pp->second[0], w = pp == tr.principal_point.end() ? 0.0 : pp->second[1];
     double f = fo == tr.focal.end() ? 0.0 : fo->second;
     if (f == 0.0) f = 1.2 * u;
+    const auto fe = rec.focal_length.find(v);
+    if (fe != rec.focal_length.end()) f = fe->second;   // a focal length a bundle adjustment estimated
     out->intrinsics[3 * c] = f; out->intrinsics[3 * c + 1] = u; out->intrinsics[3 * c + 2] = w;
     const auto o = rec.orientation.find(v);
     const auto p = rec.position.find(v);
@@ -405,9 +408,48 @@ BundleAdjustmentStats BundleAdjustCameraPositionsAndPoints(const std::string& lo
   return stats;
 }
 
-BundleAdjustmentStats BundleAdjustment(const std::string& loss_function, double loss_width, int max_num_iterations, theia::Reconstruction* rec) {
+namespace {
+const struct { const char* name; int bit; } kIntrinsicsBits[] = {
+    {"FOCAL_LENGTH", (int)OptimizeIntrinsicsType::FOCAL_LENGTH}, {"ASPECT_RATIO", (int)OptimizeIntrinsicsType::ASPECT_RATIO}, {"SKEW", (int)OptimizeIntrinsicsType::SKEW},
+    {"PRINCIPAL_POINTS", (int)OptimizeIntrinsicsType::PRINCIPAL_POINTS}, {"RADIAL_DISTORTION", (int)OptimizeIntrinsicsType::RADIAL_DISTORTION},
+    {"TANGENTIAL_DISTORTION", (int)OptimizeIntrinsicsType::TANGENTIAL_DISTORTION}};
+}  // namespace
+
+bool ParseOptimizeIntrinsicsType(const std::string& text, int* mask, std::string* error) {
+  *mask = (int)OptimizeIntrinsicsType::NONE;
+  if (text.empty()) { if (error) *error = "intrinsics_to_optimize is empty (NONE, ALL, or names joined by '|')"; return false; }
+  std::stringstream ss(text);
+  std::string item;
+  bool first = true;
+  int m = 0;
+  while (std::getline(ss, item, '|')) {
+    if (first && item == "NONE") return true;
+    if (first && item == "ALL") { *mask = (int)OptimizeIntrinsicsType::ALL; return true; }
+    first = false;
+    int bit = 0;
+    for (const auto& b : kIntrinsicsBits) if (item == b.name) bit = b.bit;
+    if (!bit) { if (error) *error = "intrinsics_to_optimize: no intrinsic parameter named '" + item + "'"; return false; }
+    m |= bit;
+  }
+  *mask = m;
+  return true;
+}
+
+std::string OptimizeIntrinsicsTypeNames(int mask) {
+  std::string out;
+  for (const auto& b : kIntrinsicsBits) if (mask & b.bit) out += (out.empty() ? "" : "|") + std::string(b.name);
+  return out.empty() ? "NONE" : out;
+}
+
+BundleAdjustmentStats BundleAdjustment(const std::string& loss_function, double loss_width, int max_num_iterations, int intrinsics_to_optimize,
+                                       theia::Reconstruction* rec) {
   BundleAdjustmentStats stats;
   stats.max_num_iterations = max_num_iterations;
+  const int unsupported = intrinsics_to_optimize & ~(int)OptimizeIntrinsicsType::FOCAL_LENGTH;
+  if (unsupported)   // holding what the caller asked to move, without a word, is not an option
+    throw std::invalid_argument("BundleAdjustment: intrinsics_to_optimize asks for " + OptimizeIntrinsicsTypeNames(unsupported) +
+                                ", which the device bundle adjustment does not optimise (supported: NONE, FOCAL_LENGTH)");
+  const bool focal = intrinsics_to_optimize == (int)OptimizeIntrinsicsType::FOCAL_LENGTH;
   gsfm_loss_node loss{};
   if (loss_function == "TRIVIAL") loss.kind = GSFM_LOSS_TRIVIAL;
   else if (loss_function == "HUBER") loss.kind = GSFM_LOSS_HUBER;
@@ -424,26 +466,43 @@ BundleAdjustmentStats BundleAdjustment(const std::string& loss_function, double 
     point_estimated[t] = rec->track_estimated[t];
     for (int k = 0; k < 3; ++k) points[3 * t + k] = rec->track_point[t][k];
   }
-  gsfm_ba6_problem* problem = nullptr;
-  gsfm_status st = gsfm_ba6_problem_create((uint32_t)N, f.intrinsics.data(), f.cam_estimated.data(), T, f.track_ptr.data(), f.obs_cam.data(), f.obs_xy.data(),
-                                           point_estimated.data(), &problem);
-  if (st != GSFM_OK) throw std::runtime_error(std::string("BundleAdjustment: ") + gsfm_last_error());
   gsfm_ba_options o;
-  gsfm_ba6_options_default(&o);
-  o.max_num_iterations = max_num_iterations;
   gsfm_ba_summary s;
-  st = gsfm_ba6_set_loss(problem, &loss, 1);
-  if (st == GSFM_OK) st = gsfm_ba6_solve(problem, f.rot_aa.data(), f.cam_pos.data(), points.data(), &o, &s);
-  gsfm_ba6_problem_destroy(problem);
+  gsfm_status st;
+  std::vector<double> focal_length(N, 0.0);
+  if (focal) {
+    for (size_t c = 0; c < N; ++c) focal_length[c] = f.intrinsics[3 * c];
+    gsfm_ba7_problem* problem = nullptr;
+    st = gsfm_ba7_problem_create((uint32_t)N, f.intrinsics.data(), f.cam_estimated.data(), nullptr, T, f.track_ptr.data(), f.obs_cam.data(), f.obs_xy.data(),
+                                 point_estimated.data(), &problem);
+    if (st != GSFM_OK) throw std::runtime_error(std::string("BundleAdjustment: ") + gsfm_last_error());
+    gsfm_ba7_options_default(&o);
+    o.max_num_iterations = max_num_iterations;
+    st = gsfm_ba7_set_loss(problem, &loss, 1);
+    if (st == GSFM_OK) st = gsfm_ba7_solve(problem, f.rot_aa.data(), f.cam_pos.data(), focal_length.data(), points.data(), &o, &s);
+    gsfm_ba7_problem_destroy(problem);
+  } else {
+    gsfm_ba6_problem* problem = nullptr;
+    st = gsfm_ba6_problem_create((uint32_t)N, f.intrinsics.data(), f.cam_estimated.data(), T, f.track_ptr.data(), f.obs_cam.data(), f.obs_xy.data(),
+                                 point_estimated.data(), &problem);
+    if (st != GSFM_OK) throw std::runtime_error(std::string("BundleAdjustment: ") + gsfm_last_error());
+    gsfm_ba6_options_default(&o);
+    o.max_num_iterations = max_num_iterations;
+    st = gsfm_ba6_set_loss(problem, &loss, 1);
+    if (st == GSFM_OK) st = gsfm_ba6_solve(problem, f.rot_aa.data(), f.cam_pos.data(), points.data(), &o, &s);
+    gsfm_ba6_problem_destroy(problem);
+  }
   if (st != GSFM_OK) throw std::runtime_error(std::string("BundleAdjustment: ") + gsfm_last_error());
   for (size_t c = 0; c < N; ++c)
     if (f.cam_estimated[c]) {
       rec->orientation[f.views[c]] = Eigen::Vector3d(f.rot_aa[3 * c], f.rot_aa[3 * c + 1], f.rot_aa[3 * c + 2]);
       rec->position[f.views[c]] = Eigen::Vector3d(f.cam_pos[3 * c], f.cam_pos[3 * c + 1], f.cam_pos[3 * c + 2]);
+      if (focal) rec->focal_length[f.views[c]] = focal_length[c];
     }
   for (size_t t = 0; t < T; ++t)
     if (point_estimated[t]) rec->track_point[t] = Eigen::Vector3d(points[3 * t], points[3 * t + 1], points[3 * t + 2]);
   stats.ran = true;
+  stats.focal_lengths_free = focal;
   stats.usable = s.termination != GSFM_TERM_FAILURE;
   stats.termination = s.termination; stats.num_iterations = s.num_iterations; stats.num_successful_steps = s.num_successful_steps;
   stats.num_unsuccessful_steps = s.num_unsuccessful_steps; stats.num_cg_iterations = s.num_cg_iterations;

@@ -17,6 +17,7 @@
 #include "../../include/gsfm/GSfM_nonlinear_rotation_estimator.hpp"
 #include "../../include/gsfm/evaluation.hpp"
 #include "../../include/gsfm/view_graph.hpp"
+#include "../../include/gsfm_ba7.h"
 
 namespace py = pybind11;
 using namespace theia;
@@ -121,6 +122,9 @@ struct ReconstructionEstimatorOptions {
   double max_reprojection_error_in_pixels = 5.0;             // :115; the outlier rule after a bundle adjustment (the YAML's max_reprojection_error_pixels)
   int num_retriangulation_iterations = 1;                    // :237; the pipeline's structure loop runs 1 + this many times
   bool refine_camera_positions_and_points_after_position_estimation = true;   // :229; the partial adjustment of the loop's first pass
+  // :242; which intrinsics BundleAdjustment() moves (the YAML's intrinsics_to_optimize; the reference's flags.yaml sets FOCAL_LENGTH, its
+  // flags_1dsfm.yaml NONE).  NONE and FOCAL_LENGTH run on the device; any other bit makes BundleAdjustment() fail with a message.
+  gsfm::OptimizeIntrinsicsType intrinsics_to_optimize = gsfm::OptimizeIntrinsicsType::NONE;
 };
 struct ReconstructionBuilderOptions {
   int num_threads = 1;
@@ -275,13 +279,25 @@ class GlobalReconstructionEstimator {
   }
   gsfm::OutlierTracksStats outlier_;     // of the last BundleAdjustmentAndRemoveOutlierPoints (zeros when the adjustment was not usable)
   // Theia's BundleAdjustment (the solve of BundleAdjustmentAndRemoveOutlierPoints; SetOutlierTracksToUnestimated is not part of it): all
-  // estimated views and tracks, orientations, positions and points move, intrinsics are held; loss and iteration rule as above.  The new
-  // orientations and positions are written back to the reconstruction.
+  // estimated views and tracks, orientations, positions and points move; loss and iteration rule as above.  The intrinsics follow
+  // options.intrinsics_to_optimize: NONE holds them, FOCAL_LENGTH moves every estimated view's focal length too (include/gsfm_ba7.h) and
+  // writes it to the reconstruction, where the later calls (the outlier rule, EstimateStructure, the next adjustment) read it; with any
+  // other bit nothing runs, the reconstruction is untouched and the call returns false with LastError() naming the unsupported bits.  The
+  // new orientations and positions are written back to the reconstruction.
   bool BundleAdjustment() {
     if (!reconstruction_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
     int iterations = 100;
     if (reconstruction_->NumViews() >= options_.min_cameras_for_iterative_solver) iterations = (int)(iterations * 1.5);
-    bundle_ = gsfm::BundleAdjustment(options_.bundle_adjustment_loss_function_type, options_.bundle_adjustment_robust_loss_width, iterations, reconstruction_);
+    error_.clear();
+    try {
+      bundle_ = gsfm::BundleAdjustment(options_.bundle_adjustment_loss_function_type, options_.bundle_adjustment_robust_loss_width, iterations,
+                                       (int)options_.intrinsics_to_optimize, reconstruction_);
+    } catch (const std::invalid_argument& e) {
+      bundle_ = gsfm::BundleAdjustmentStats();
+      bundle_.usable = false;
+      error_ = e.what();
+      return false;
+    }
     return bundle_.usable;
   }
   gsfm::BundleAdjustmentStats bundle_;   // of the last bundle adjustment, either kind
@@ -329,6 +345,7 @@ py::dict bundle_dict(const gsfm::BundleAdjustmentStats& st) {
   d["num_cg_iterations"] = st.num_cg_iterations; d["max_num_iterations"] = st.max_num_iterations;
   d["num_observations"] = st.num_observations; d["num_cameras"] = st.num_cameras; d["num_points"] = st.num_points;
   d["initial_cost"] = st.initial_cost; d["final_cost"] = st.final_cost; d["t_total_ms"] = st.t_total_ms;
+  d["focal_lengths_free"] = st.focal_lengths_free;
   return d;
 }
 
@@ -374,6 +391,15 @@ void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions
   get("num_retriangulation_iterations", options.reconstruction_estimator_options.num_retriangulation_iterations);
   get("refine_camera_positions_and_points_after_position_estimation",
       options.reconstruction_estimator_options.refine_camera_positions_and_points_after_position_estimation);
+  // bind :199-200: a bitmask of names joined by '|' (StringToOptimizeIntrinsicsType); an absent key leaves NONE
+  std::string intrinsics;
+  get("intrinsics_to_optimize", intrinsics);
+  if (cfg.contains("intrinsics_to_optimize") && !cfg["intrinsics_to_optimize"].is_none()) {
+    int mask = 0;
+    std::string error;
+    if (!gsfm::ParseOptimizeIntrinsicsType(intrinsics, &mask, &error)) throw std::invalid_argument(flagfile + ": " + error);
+    options.reconstruction_estimator_options.intrinsics_to_optimize = (gsfm::OptimizeIntrinsicsType)mask;
+  }
 }
 
 }  // namespace
@@ -448,8 +474,30 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
     py::print("[" + std::to_string(out[0]) + ", " + std::to_string(out[1]) + ", " + std::to_string(out[2]) + "]");
   });
 
+  py::enum_<gsfm::OptimizeIntrinsicsType>(m, "OptimizeIntrinsicsType", py::arithmetic())   // Theia's names and values (a bitmask)
+      .value("NONE", gsfm::OptimizeIntrinsicsType::NONE)
+      .value("FOCAL_LENGTH", gsfm::OptimizeIntrinsicsType::FOCAL_LENGTH)
+      .value("ASPECT_RATIO", gsfm::OptimizeIntrinsicsType::ASPECT_RATIO)
+      .value("SKEW", gsfm::OptimizeIntrinsicsType::SKEW)
+      .value("PRINCIPAL_POINTS", gsfm::OptimizeIntrinsicsType::PRINCIPAL_POINTS)
+      .value("RADIAL_DISTORTION", gsfm::OptimizeIntrinsicsType::RADIAL_DISTORTION)
+      .value("TANGENTIAL_DISTORTION", gsfm::OptimizeIntrinsicsType::TANGENTIAL_DISTORTION)
+      .value("ALL", gsfm::OptimizeIntrinsicsType::ALL);
+  m.def("StringToOptimizeIntrinsicsType", [](const std::string& text) {
+    int mask = 0;
+    std::string error;
+    if (!gsfm::ParseOptimizeIntrinsicsType(text, &mask, &error)) throw std::invalid_argument(error);
+    return mask;
+  });
+  m.def("ba7_abi_version", [] { return GSFM_BA7_ABI_VERSION; });   // the header this module was compiled against
+
   py::class_<ReconstructionEstimatorOptions>(m, "ReconstructionEstimatorOptions")
       .def(py::init<>())
+      .def_property("intrinsics_to_optimize", [](const ReconstructionEstimatorOptions& o) { return py::cast(o.intrinsics_to_optimize); },
+                    [](ReconstructionEstimatorOptions& o, int mask) {   // an enum value, or an | of them (an int)
+                      if (mask & ~(int)gsfm::OptimizeIntrinsicsType::ALL) throw std::invalid_argument("intrinsics_to_optimize: no such bit");
+                      o.intrinsics_to_optimize = (gsfm::OptimizeIntrinsicsType)mask;
+                    })
       .def_readwrite("num_threads", &ReconstructionEstimatorOptions::num_threads)
       .def_readwrite("min_num_two_view_inliers", &ReconstructionEstimatorOptions::min_num_two_view_inliers)
       .def_readwrite("rotation_filtering_max_difference_degrees", &ReconstructionEstimatorOptions::rotation_filtering_max_difference_degrees)
@@ -478,6 +526,15 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def("NumTracks", &Reconstruction::NumTracks)
       .def("NumViews", &Reconstruction::NumViews)
       .def("NumEstimatedTracks", &Reconstruction::NumEstimatedTracks)
+      // the focal length a bundle adjustment with FOCAL_LENGTH estimated for the view, or None (FlattenedTracks() shows what is in use)
+      .def("ViewFocalLength", [](const Reconstruction& r, ViewId v) -> py::object {
+        const auto it = r.focal_length.find(v);
+        return it == r.focal_length.end() ? py::object(py::none()) : py::object(py::float_(it->second));
+      })
+      .def("SetViewFocalLength", [](Reconstruction& r, ViewId v, double f) {
+        if (!(f > 0.0) || !std::isfinite(f)) throw std::invalid_argument("a focal length must be finite and positive");
+        r.focal_length[v] = f;
+      })
       // a track is addressed by its index in tracks.txt (Theia's TrackId of a 1DSfM dataset); Track(id)->Point(), IsEstimated(), NumViews()
       .def("TrackPoint", [](const Reconstruction& r, size_t t) {
         if (t >= (size_t)r.NumTracks()) throw py::index_error("no such track");

@@ -833,3 +833,96 @@ def bundle_adjust(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, point
         return prob.solve(rot_aa, cam_pos, points, **options)
     finally:
         prob.close()
+
+
+class FocalBundleProblem(_BundleProblemBase):
+    """The full bundle adjustment with free focal lengths (include/gsfm_ba7.h): Theia's GlobalReconstructionEstimator::BundleAdjustment with
+    intrinsics_to_optimize = FOCAL_LENGTH on the device; a seventh coordinate per camera, the reduced 7 x 7-block camera system solved by PCG.
+    The arguments are FullBundleProblem's and focal_free (N flags or None: every camera's focal length is free); column 0 of intrinsics is not
+    read: the focal lengths (N, pixels) are a start value of solve().  A camera with focal_free = 0 keeps the focal length given to solve()."""
+    _prefix = "gsfm_ba7_"
+
+    def __init__(self, intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated=None, point_estimated=None, focal_free=None):
+        lib = _abi.load_library()
+        (K,), tp, oc, xy, ce, pe, _ = _track_arrays((("intrinsics", intrinsics),), track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated, per=_PER_ENTRY)
+        n, T = K.shape[0], tp.shape[0] - 1
+        ff = None
+        if focal_free is not None:
+            ff = np.ascontiguousarray(np.asarray(focal_free) != 0, dtype=np.uint8).reshape(-1)
+            if ff.shape[0] != n:
+                raise ValueError("focal_free needs one flag per entry")
+        h = C.c_void_p()
+        st = lib.gsfm_ba7_problem_create(n, _p(K), _p(ce), _p(ff), T, _p(tp), _p(oc), _p(xy), _p(pe), C.byref(h))
+        _raise_if_failed(lib, "gsfm_ba7_problem_create", st)
+        self._adopt(lib, h, n, T, int(oc.shape[0]))
+
+    def _point7(self, rot_aa, cam_pos, focal, points):
+        c, p = self._point(cam_pos, points)
+        return np.array(rot_aa, dtype=np.float64, order="C").reshape(self.n_cams, 3), c, np.array(focal, dtype=np.float64, order="C").reshape(self.n_cams), p
+
+    def solve(self, rot_aa, cam_pos, focal, points, **options):
+        """Returns (orientations N x 3, camera positions N x 3, focal lengths N, points T x 3, summary dict); inactive and unestimated rows
+        and held focal lengths are returned as given."""
+        w, c, f, p = self._point7(rot_aa, cam_pos, focal, points)
+        o, s = self._options(options), _abi.BaSummary()
+        self._check(self._lib.gsfm_ba7_solve(self._h, _p(w), _p(c), _p(f), _p(p), C.byref(o), C.byref(s)), "solve")
+        return w, c, f, p, s.as_dict()
+
+    def residuals(self, rot_aa, cam_pos, focal, points):
+        """(r: n_obs x 2, rho: n_obs); zeros for an unused observation"""
+        w, c, f, p = self._point7(rot_aa, cam_pos, focal, points)
+        r, rho = np.zeros((self.n_obs, 2)), np.zeros(self.n_obs)
+        self._check(self._lib.gsfm_ba7_residuals(self._h, _p(w), _p(c), _p(f), _p(p), _p(r), _p(rho)), "residuals")
+        return r, rho
+
+    def linearize(self, rot_aa, cam_pos, focal, points):
+        """dict(cost, grad_rot N x 3, grad_pos N x 3, grad_focal N, grad_point T x 3, diag_cam N x 7 x 7 (w, o, f), diag_point T x 3 x 3)"""
+        w, c, f, p = self._point7(rot_aa, cam_pos, focal, points)
+        cost = np.zeros(1)
+        gr, gc, gf, gp = np.zeros((self.n_cams, 3)), np.zeros((self.n_cams, 3)), np.zeros(self.n_cams), np.zeros((self.n_tracks, 3))
+        dc, dp = np.zeros((self.n_cams, 7, 7)), np.zeros((self.n_tracks, 3, 3))
+        st = self._lib.gsfm_ba7_linearize(self._h, _p(w), _p(c), _p(f), _p(p), _p(cost), _p(gr), _p(gc), _p(gf), _p(gp), _p(dc), _p(dp))
+        self._check(st, "linearize")
+        return {"cost": float(cost[0]), "grad_rot": gr, "grad_pos": gc, "grad_focal": gf, "grad_point": gp, "diag_cam": dc, "diag_point": dp}
+
+    def schur_matvec(self, v, radius=1e4, **options):
+        """y = Sc v (N x 7, per camera w, o, f) for the last linearize / step_check, damped at `radius`"""
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(self.n_cams, 7)
+        y = np.zeros((self.n_cams, 7))
+        o = self._options(options)
+        self._check(self._lib.gsfm_ba7_schur_matvec(self._h, _p(v), float(radius), C.byref(o), _p(y)), "schur_matvec")
+        return y
+
+    def step_check(self, rot_aa, cam_pos, focal, points, radius=1e4, **options):
+        """gsfm_ba7_step_check: dict(rhs, y_cam (N x 7), y_point, delta_rot, delta_pos, delta_focal, delta_point, j_delta (n_obs x 2),
+        model_cost_change, dg, jd2, cg_rel, cg_iterations, stalled)"""
+        w, c, f, p = self._point7(rot_aa, cam_pos, focal, points)
+        o = self._options(options)
+        N, T = self.n_cams, self.n_tracks
+        rhs, yc, yp = np.zeros((N, 7)), np.zeros((N, 7)), np.zeros((T, 3))
+        dr, dc, df, dp, jd = np.zeros((N, 3)), np.zeros((N, 3)), np.zeros(N), np.zeros((T, 3)), np.zeros((self.n_obs, 2))
+        scal, info = np.zeros(4), np.zeros(2, dtype=np.int32)
+        st = self._lib.gsfm_ba7_step_check(self._h, _p(w), _p(c), _p(f), _p(p), float(radius), C.byref(o), _p(rhs), _p(yc), _p(yp), _p(dr), _p(dc), _p(df),
+                                           _p(dp), _p(jd), _p(scal), _p(info))
+        self._check(st, "step_check")
+        return {"rhs": rhs, "y_cam": yc, "y_point": yp, "delta_rot": dr, "delta_pos": dc, "delta_focal": df, "delta_point": dp, "j_delta": jd,
+                "model_cost_change": scal[0], "dg": scal[1], "jd2": scal[2], "cg_rel": scal[3], "cg_iterations": int(info[0]), "stalled": bool(info[1])}
+
+    def time_kernels(self, rot_aa, cam_pos, focal, points, radius=1e4, reps=10):
+        """mean device microseconds of the kernels of one linearisation and one Schur product (gsfm_ba7_time_kernels)"""
+        w, c, f, p = self._point7(rot_aa, cam_pos, focal, points)
+        out = np.zeros(8)
+        self._check(self._lib.gsfm_ba7_time_kernels(self._h, _p(w), _p(c), _p(f), _p(p), float(radius), int(reps), _p(out)), "time_kernels")
+        return dict(zip(("camera_records", "lin_tracks", "lin_cameras", "cost", "point_pass", "camera_pass", "preconditioner", "quadratic_form"), out))
+
+
+def bundle_adjust_focal(rot_aa, cam_pos, focal, intrinsics, track_ptr, obs_cam, obs_xy, points, cam_estimated=None, point_estimated=None, focal_free=None,
+                        loss=None, **options):
+    """One call: FocalBundleProblem(...).set_loss(loss).solve(rot_aa, cam_pos, focal, points, **options).  Returns (rot_aa, cam_pos, focal,
+    points, summary dict)."""
+    prob = FocalBundleProblem(intrinsics, track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated, focal_free)
+    try:
+        prob.set_loss(loss)
+        return prob.solve(rot_aa, cam_pos, focal, points, **options)
+    finally:
+        prob.close()

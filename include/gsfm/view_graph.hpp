@@ -60,6 +60,9 @@ class Reconstruction {
   std::shared_ptr<const gsfm::Tracks1DSfM> tracks;
   std::vector<Eigen::Vector3d> track_point;
   std::vector<uint8_t> track_estimated;
+  // The estimated focal length per view, in pixels: empty until a bundle adjustment with free focal lengths writes it (BundleAdjustment with
+  // FOCAL_LENGTH).  FlattenTracks takes a view's entry in place of the EXIF / 1.2 x rule, so every later call sees the adjusted value.
+  std::unordered_map<ViewId, double> focal_length;
   int NumTracks() const;
   int NumEstimatedTracks() const;
   int NumViews() const { return (int)views.size(); }
@@ -151,8 +154,8 @@ void CollectEdgeMatches(const Tracks1DSfM& tracks, const theia::ViewGraph& view_
 // TrackEstimator with bundle_adjustment = false), on the device: gsfm_tracks_triangulate under the definition of include/gsfm_tracks.h ----
 // The reconstruction's tracks as that entry point takes them.  Cameras: every view that has keypoints, ascending by view id; a camera is
 // estimated when the reconstruction holds an orientation AND a position for it (SetReconstructionFromEstimatedPoses), others carry zeros.
-// Intrinsics f u v: the EXIF focal of list.txt, else 1.2 x the principal point's x (the rule of CollectEdgeMatches), and the principal
-// point of coords.txt.  Tracks and their observations in the order of tracks.txt.
+// Intrinsics f u v: the reconstruction's estimated focal length of the view when it has one (Reconstruction::focal_length), else the EXIF
+// focal of list.txt, else 1.2 x the principal point's x (the rule of CollectEdgeMatches), and the principal point of coords.txt.  Tracks and their observations in the order of tracks.txt.
 struct FlatTracks {
   std::vector<theia::ViewId> views;                  // camera index -> view id
   std::vector<double> rot_aa, cam_pos, intrinsics;   // 3 per camera
@@ -226,13 +229,32 @@ struct BundleAdjustmentStats {
   int termination = -1, num_iterations = 0, num_successful_steps = 0, num_unsuccessful_steps = 0, num_cg_iterations = 0, max_num_iterations = 0;
   uint64_t num_observations = 0, num_cameras = 0, num_points = 0;
   double initial_cost = 0.0, final_cost = 0.0, t_total_ms = 0.0;
+  bool focal_lengths_free = false;                   // BundleAdjustment with FOCAL_LENGTH
 };
 BundleAdjustmentStats BundleAdjustCameraPositionsAndPoints(const std::string& loss_function, double loss_width, int max_num_iterations,
                                                            theia::Reconstruction* reconstruction);
-// GlobalReconstructionEstimator::BundleAdjustment (the solve of BundleAdjustmentAndRemoveOutlierPoints; intrinsics_to_optimize = NONE) on the
-// device: gsfm_ba6_solve under the definition of include/gsfm_ba6.h, over all estimated views and tracks.  As above, and the orientations of
-// the estimated views are written back as well.
-BundleAdjustmentStats BundleAdjustment(const std::string& loss_function, double loss_width, int max_num_iterations, theia::Reconstruction* reconstruction);
+// Theia's OptimizeIntrinsicsType (sfm/bundle_adjustment/bundle_adjustment.h): a bitmask, with Theia's names and values.
+// (unscoped, so that values combine with | as Theia's do; in a namespace of its own to keep NONE and ALL out of gsfm)
+namespace optimize_intrinsics {
+enum Type : int {
+  NONE = 0x00, FOCAL_LENGTH = 0x01, ASPECT_RATIO = 0x02, SKEW = 0x04, PRINCIPAL_POINTS = 0x08, RADIAL_DISTORTION = 0x10, TANGENTIAL_DISTORTION = 0x20,
+  ALL = 0x3f
+};
+}
+using OptimizeIntrinsicsType = optimize_intrinsics::Type;
+// The flag string of the reference's StringToOptimizeIntrinsicsType: names joined by '|' without spaces; a first name of NONE or ALL decides
+// alone.  false (and *error) for an empty string or a name that is none of the enum's -- the reference aborts there.
+bool ParseOptimizeIntrinsicsType(const std::string& text, int* mask, std::string* error);
+// the names of the mask's bits joined by '|' (NONE for 0)
+std::string OptimizeIntrinsicsTypeNames(int mask);
+// GlobalReconstructionEstimator::BundleAdjustment (the solve of BundleAdjustmentAndRemoveOutlierPoints) on the device, over all estimated views
+// and tracks.  As above, and the orientations of the estimated views are written back as well.  intrinsics_to_optimize:
+//   NONE          gsfm_ba6_solve under the definition of include/gsfm_ba6.h: the intrinsics FlattenTracks gives are held;
+//   FOCAL_LENGTH  gsfm_ba7_solve under the definition of include/gsfm_ba7.h: the focal length of every estimated view moves too, from the
+//                 value FlattenTracks gives, and is written to Reconstruction::focal_length (stats.focal_lengths_free);
+//   any other bit throws std::invalid_argument naming the unsupported bits before any device call: the reconstruction is untouched.
+BundleAdjustmentStats BundleAdjustment(const std::string& loss_function, double loss_width, int max_num_iterations, int intrinsics_to_optimize,
+                                       theia::Reconstruction* reconstruction);
 #endif
 
 // two_views.txt of scripts/read_colmap_database.py:52-133 as AddColmapMatchesToReconstructionBuilder reads it

@@ -57,7 +57,7 @@
  * forcing sequence from 1000 views on and a direct Schur solver below.  (2) No inner iterations.  (3) Points are inhomogeneous 3-vectors;
  * Theia optimises the homogeneous 4-vector.  (4) p is formed with the matrix R where Theia rotates with AngleAxisRotatePoint, and the
  * orientation Jacobian is the closed form above where Ceres differentiates automatically.  (5) The gauge projection above.  (6) Intrinsics
- * are held (every flag file of the reference's pipeline sets intrinsics_to_optimize = NONE).
+ * are held (intrinsics_to_optimize = NONE, what the reference's flags_1dsfm.yaml sets; its flags.yaml sets FOCAL_LENGTH: gsfm_ba7.h).
  */
 #ifndef GSFM_BA6_H_
 #define GSFM_BA6_H_
