@@ -103,7 +103,8 @@ __device__ __forceinline__ void mv_col_body(const ColMatvecArgs& a, Stop stop_af
   // plane-major: the slot-contiguous reads of one row are conflict-free; two buffers, so one barrier per iteration suffices (a buffer is
   // written again two iterations later, after the barrier every lane passes once it has finished reading it)
   __shared__ double slots[2][EPL][3][RB];
-  __shared__ uint32_t wtot[2][EPL][RB / 64];   // per wavefront: number of slots of its 64 rows
+  static_assert(RB / 64 == 8, "the cross-wave prefix reads the eight wave totals as two 16-byte words");
+  __shared__ __attribute__((aligned(16))) uint32_t wtot[2][EPL][RB / 64];   // per wavefront: number of slots of its 64 rows
   const ColWg w = a.L.wg[blockIdx.x];
   const uint32_t r = threadIdx.x, wave = r >> 6;
   double y0 = 0.0, y1 = 0.0, y2 = 0.0;
@@ -155,7 +156,15 @@ __device__ __forceinline__ void mv_col_body(const ColMatvecArgs& a, Stop stop_af
 #pragma unroll
     for (int k = 0; k < EPL; ++k) {
       uint32_t s1 = inc[k];
-      for (uint32_t v = 0; v < wave; ++v) s1 += wtot[buf][k][v];
+      // (the eight wave totals in two 16-byte reads, those of the earlier waves added under a mask: one LDS round trip for every wave; read one by
+      // one, wave 7 went through seven dependent ones before its first slot, and the workgroup's next barrier waits for the last wave)
+      const uint4 t0 = *reinterpret_cast<const uint4*>(&wtot[buf][k][0]), t1 = *reinterpret_cast<const uint4*>(&wtot[buf][k][4]);
+      s1 += (wave > 0 ? t0.x : 0u) + (wave > 1 ? t0.y : 0u) + (wave > 2 ? t0.z : 0u) + (wave > 3 ? t0.w : 0u)
+          + (wave > 4 ? t1.x : 0u) + (wave > 5 ? t1.y : 0u) + (wave > 6 ? t1.z : 0u);
+      // Not unrolled: a row has about one slot per sub-chunk (C5), and unrolled eight-fold this loop alone took 48 of the kernel's 74 vector
+      // registers -- six waves per SIMD, three workgroups per CU.  Rolled, the kernel needs 37 and four workgroups fit (the gain is the fourth
+      // workgroup: the rolled loop held to three measures like the unrolled one, profiles/k3c_lookahead_ab.json).
+#pragma unroll 1
       for (uint32_t t = s1 - cnt[k]; t < s1; ++t) { y0 += slots[buf][k][0][t]; y1 += slots[buf][k][1][t]; y2 += slots[buf][k][2][t]; }
     }
   }

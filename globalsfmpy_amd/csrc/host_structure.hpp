@@ -300,7 +300,8 @@ bool build_colsort_host(uint32_t n_cams, uint32_t n_rows, const std::vector<uint
   if (L.k16_mode != 0) { L.k16.resize(n_pos); L.kbase.resize(n_sub * (SUB / 64)); L.kdel.resize(n_pos); }
   std::atomic<uint64_t> k16_escapes{0};
   L.wg.resize((size_t)nblk * nch);
-  // (graded only where the tasks outnumber the chip's resident workgroups several times over -- K2c holds 512, K3c 1024: with a single round,
+  // (graded only where the tasks outnumber the chip's resident workgroups several times over -- K2c holds 512, K3c 1024 (four workgroups per CU
+  // at its 37 vector registers; it held 768, three per CU, as long as its slot loop was unrolled to 74 registers): with a single round,
   // as on one rank's share of a sharded problem (400 tasks), the kernel takes as long as its LARGEST task, and grading made K3c 33 -> 40 us there)
   const bool graded = nch > 1 && (size_t)nblk * nch >= (size_t)1280;
   parallel_run(std::max(1, std::min<int>(n_threads, (int)nblk)), [&](int t, int T) {

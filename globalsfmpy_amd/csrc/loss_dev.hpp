@@ -177,6 +177,20 @@ __device__ __forceinline__ double loss_magsac_value(const DevLossNode& n, double
   return n.inverse ? 1.0 / weight : n.aux[5] - weight;
 }
 
+// The same value for LM_MAGSAC, i.e. nu = 3 and not inverted AT COMPILE TIME (loss_mode, solver_launch.hpp, chooses LM_MAGSAC for nothing
+// else): the expression of loss_magsac_value's nu = 3 side, operation for operation -- the same bits -- without the table pointer.  With the
+// table side present, the block the two sides join at began with a wait for EVERY load the lane had in flight, also on the exp side: in
+// K2c's fused trial evaluation that drained the prefetched streams of the next sub-chunk once per role-0 entry.
+__device__ __forceinline__ double loss_magsac3_value(const DevLossNode& n, double sq) {
+#pragma clang fp contract(off)   // (as loss_magsac_value)
+  const double ssm2 = n.aux[1];
+  if (sq > n.aux[6]) sq = n.aux[6];
+  long x = (long)rint(1000.0 * sq / ssm2);
+  if (x > (long)n.table_len - 1) x = (long)n.table_len - 1;
+  const double weight = n.aux[4] * (exp(-1e-3 * (double)x) - n.aux[7]);
+  return n.aux[5] - weight;
+}
+
 // Kernel specialisations.  LM_MAGSAC = ONE MAGSACWeightBasedLoss leaf with nu = 3, not inverted (the pipeline's default,
 // scripts/sfm_pipeline.py:136); the nu = 4 / 9 and inverse variants run through the general program.
 enum { LM_PROGRAM = 0, LM_SIMPLE = 1, LM_MAGSAC = 2 };
@@ -254,7 +268,7 @@ __device__ __forceinline__ Rho3 loss_eval(const DevLoss* __restrict__ loss, doub
 
 template <int LM>
 __device__ __forceinline__ double loss_value(const DevLoss* __restrict__ loss, double s) {
-  if (LM == LM_MAGSAC) return loss_magsac_value(loss->nodes[0], s);
+  if (LM == LM_MAGSAC) return loss_magsac3_value(loss->nodes[0], s);
   return loss_eval<LM>(loss, s).r0;  // the unused derivatives are dead code for the simple leaves
 }
 
@@ -280,7 +294,7 @@ __device__ __forceinline__ Rho3 loss_eval(const LossView<LM>& v, double s) {
 }
 template <int LM>
 __device__ __forceinline__ double loss_value(const LossView<LM>& v, double s) {
-  if (LM == LM_MAGSAC) return loss_magsac_value(v.n, s);
+  if (LM == LM_MAGSAC) return loss_magsac3_value(v.n, s);
   return loss_eval<LM>(v, s).r0;
 }
 // K2's fast path (see lin_rows_fast): only for LM_SIMPLE / LM_MAGSAC
