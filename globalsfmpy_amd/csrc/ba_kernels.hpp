@@ -168,7 +168,7 @@ __device__ __forceinline__ void ba6_refine_inv3(const double* m, double* X, doub
 }
 // A point whose damped block is badly conditioned -- max |C~| max |C~^-1| above GSFM_BA_DD_COND, as it is for a block that lost rank beyond
 // the Tukey cut and is held up by the damping alone -- is "flagged": k_ba_prep_points refines its inverse to a pair (Cinv: the refined X,
-// Cfix[0..8]: the correction, Cfix[9] = 1) and k_ba_point_pass / k_ba_cam_precond run its sums in double-double, as ba6_kernels.hpp does for
+// Cfix[0..8]: the correction, Cfix[9] = 1) and k_ba_point_pass / k_ba_cam_precond run its sums in double-double, as full_ba_kernels.hpp does for
 // every point (DESIGN.md sections 16, 17).  Every other point keeps the plain fp64 path and its bytes.
 #define GSFM_BA_DD_COND 1e5
 #define GSFM_BA_FIX_DOUBLES 10

@@ -1,4 +1,4 @@
-// The device scalars of a Euclidean problem (solver_pos.hpp, solver_ba.hpp, solver_ba6.hpp): scal[slot] is written by a reduction over the
+// The device scalars of a Euclidean problem (solver_pos.hpp, solver_ba.hpp, solver_full_ba.hpp): scal[slot] is written by a reduction over the
 // GSFM_POS_PARTS partial sums in part, in a fixed order, and read back by a copy that is waited for.  Everything is enqueued on the
 // problem's stream.
 #pragma once

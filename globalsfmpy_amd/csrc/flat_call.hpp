@@ -22,7 +22,7 @@ struct FlatLayout {
   }
 };
 
-// A problem's slab (solver_pos.hpp, solver_ba.hpp, solver_ba6.hpp): take(ptr, count) lays the array out and, given the committed slab,
+// A problem's slab (solver_pos.hpp, solver_ba.hpp, solver_full_ba.hpp): take(ptr, count) lays the array out and, given the committed slab,
 // points ptr into it; the same list of takes serves both passes
 struct SlabTake {
   FlatLayout L;

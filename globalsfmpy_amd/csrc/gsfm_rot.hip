@@ -22,8 +22,7 @@
 #include "track_refine.hpp"
 #include "outlier_tracks.hpp"
 #include "solver_ba.hpp"
-#include "solver_ba6.hpp"
-#include "solver_ba7.hpp"
+#include "solver_full_ba.hpp"
 
 // =============================================================================================
 extern "C" {

@@ -1,5 +1,5 @@
 // The host control loops of the Euclidean solvers -- positions (solver_pos.hpp), positions and points (solver_ba.hpp), orientations, positions
-// and points (solver_ba6.hpp) -- once: lm_loop, Ceres 1.14's TrustRegionMinimizer + LevenbergMarquardtStrategy restated from
+// and points (solver_full_ba.hpp) -- once: lm_loop, Ceres 1.14's TrustRegionMinimizer + LevenbergMarquardtStrategy restated from
 // oracle/ref_solver.cpp::lm_solve for Euclidean parameters (the radius rule is trust_region.hpp's), and pcg_loop, the driver of their
 // preconditioned conjugate gradients.  Plain arithmetic over a few callables, no HIP: tests/cpp/lm_loop_test.cpp builds this header with the
 // host compiler alone and drives every branch with scripted scalars.  The rotation solver's LmSolve (solver_lm.hpp: forcing schedule,

@@ -1,5 +1,5 @@
 // Host side of the bundle adjustment of camera positions and points (include/gsfm_ba.h), and what it shares with the full bundle adjustment
-// (solver_ba6.hpp): the problem's common part (BaProblem: sizes, host structure of ba_structure.hpp, structure arrays, the vectors of the
+// (solver_full_ba.hpp): the problem's common part (BaProblem: sizes, host structure of ba_structure.hpp, structure arrays, the vectors of the
 // step), the operations that lm_loop.hpp's Levenberg-Marquardt loop runs (BaLm), argument checks, set_loss, solve, residuals and kernel
 // timing; the checks of the track arrays, the lane classes with their launcher and the one-leaf loss are track_scene.hpp's.  Its own: the
 // Schur-complement PCG (ba_pcg, on lm_loop.hpp's driver) and the step.  The kernels are in ba_kernels.hpp; the vector kernels of the PCG
@@ -20,7 +20,7 @@
 
 struct BaStep { int cg = 0; bool stalled = false; double cg_rel = 0.0; };
 
-// What both bundle adjustments have.  A camera is one node of 3 doubles here and two (angle-axis vector, centre) in solver_ba6.hpp.
+// What both bundle adjustments have.  A camera is one node of 3 doubles here and two or three (angle-axis vector, centre, intrinsics) in solver_full_ba.hpp.
 struct BaProblem {
   int device = 0;
   FlatCall mem;
@@ -32,7 +32,7 @@ struct BaProblem {
   BaStructure st;                            // host copy of the active sets
   std::vector<uint8_t> h_active;             // n_nodes
   gsfm::DevLossNode leaf;
-  // device arrays (ba_place / b6_place): the structure
+  // device arrays (ba_place / fba_place): the structure
   uint32_t *order = nullptr, *obs_cam = nullptr, *crow_ptr = nullptr, *cobs = nullptr, *ctrk = nullptr;
   uint64_t* track_ptr = nullptr;
   double2* obs_xy = nullptr;
@@ -52,7 +52,7 @@ struct BaProblem {
   // where the two solvers differ, for the code they share:
   virtual void cost(const double* at, double* r_out, double* rho_out) = 0;          // cost of the point `at` into scal[BS_COST]
   virtual void linearize() = 0;                                                     // linearisation at x
-  virtual int step(double radius, const gsfm_ba_options& o, BaStep* out) = 0;       // one LM step's linear algebra (ba_step / b6_step)
+  virtual int step(double radius, const gsfm_ba_options& o, BaStep* out) = 0;       // one LM step's linear algebra (ba_step / fba_step)
 };
 
 struct gsfm_ba_problem : BaProblem {
@@ -69,7 +69,7 @@ namespace {
 using gsfm::BaDev;
 using gsfm::BaSlots;
 
-// the device scalars of both solvers (solver_ba6.hpp's further ones follow BS_N)
+// the device scalars of both solvers (solver_full_ba.hpp's further ones follow BS_N)
 enum { BS_RZ0 = PCG_RZ0, BS_RZA = PCG_RZA, BS_RZB = PCG_RZB, BS_PAP = 3, BS_DV = 4, BS_VV = 5, BS_STEP2 = 6, BS_DG = 7, BS_DLD = 8, BS_COST = 9,
        BS_GMAX = 10, BS_XNORM2 = 11, BS_SUMD = 12 /* 3 */, BS_SUMX = 15 /* 3 */, BS_N = 18 };
 
@@ -90,7 +90,7 @@ BaDev ba_dev(const gsfm_ba_problem* P) {
 inline dim3 ba_grid(size_t n) { return dim3((unsigned)std::max<size_t>(1, (n + 255) / 256)); }
 inline dim3 ba_row_grid(uint32_t n_cams) { return dim3(std::max(1u, (n_cams + 3) / 4)); }
 
-// a point-side kernel over every track: one launch per lane class, the long tracks first (track_scene.hpp's launcher).  a: BaDev or Ba6Dev
+// a point-side kernel over every track: one launch per lane class, the long tracks first (track_scene.hpp's launcher).  a: BaDev or FbaDev
 template <typename Dev, typename K, typename... Args>
 void ba_tracks(const BaProblem* P, const Dev& a, K k4, K k16, K k64, Args... args) {
   for_lane_classes(P->cb, [&](auto G, uint64_t n_slots, uint64_t offset, dim3 grid, dim3 block) {
@@ -257,7 +257,7 @@ bool ba_needs_points(const gsfm_ba_problem* P, const double* cam_pos, const doub
 }
 
 // ---- problem creation ----
-// The checks of the track arrays (track_scene.hpp), on the host before any device call.  nodes_per_cam: 1, or 2 for the full bundle adjustment.
+// The checks of the track arrays (track_scene.hpp), on the host before any device call.  nodes_per_cam: 1, or 2 or 3 for the full bundle adjustment.
 int ba_check_tracks(uint32_t n_cams, int nodes_per_cam, uint64_t n_tracks, const uint64_t* track_ptr, const uint32_t* obs_cam, const double* obs_xy,
                     const char* entry) {
   if (int st = track_arrays_check(n_cams, n_tracks, track_ptr, obs_cam, obs_xy, TrackLimit::observations_and_nodes, (uint64_t)nodes_per_cam * n_cams,
@@ -286,7 +286,7 @@ void ba_init(BaProblem* P, uint32_t n_cams, int nodes_per_cam, const uint8_t* ca
 
 inline hipError_t ba_up(hipStream_t s, void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess; }
 
-// The slab: committed, placed (place: ba_place / b6_place), its zeroed part cleared, the structure arrays uploaded
+// The slab: committed, placed (place: ba_place / fba_place), its zeroed part cleared, the structure arrays uploaded
 template <typename Pb, typename Place>
 int ba_commit_upload(Pb* P, Place place, const char* who, const uint64_t* track_ptr, const uint32_t* order, const uint32_t* obs_cam, const double* obs_xy,
                      size_t* zeroed) {

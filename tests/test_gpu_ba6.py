@@ -106,7 +106,7 @@ def test_step_under_tukey_and_geman_mcclure(sname, lname, radius):
     [t-tukey-1e10]: beyond the cut scene t also leaves points with ONE observation inside it, a rank-2 block held up by the damping alone,
     for which the Schur-Jacobi preconditioner (built from the plain-fp64 half of the inverse) came out indefinite.  Until this test existed
     its failed Cholesky made r.M^-1 r NaN and the solver returned y_c = 0 as a converged step (true residual 1.0, model cost change 1.4e12 x
-    its bound); such a row is now summed again through the pair inverse in double-double (k_ba6_cam_precond), and a PCG that breaks down
+    its bound); such a row is now summed again through the pair inverse in double-double (k_fba_cam_precond), and a PCG that breaks down
     reports a stall.  On an MI355X: 720 PCG iterations to 1.2e-15, J~ delta 0.819 of its bound, model cost change 0.003."""
     _step(sname, lname, radius)
 
@@ -190,7 +190,7 @@ def test_noise_free_observations_recover_the_generator_scene(sname):
 @pytest.mark.parametrize("name", sorted(R.CASES))
 def test_noisy_solve_matches_the_reference(name):
     """The far starts (rejected steps, points whose damped blocks are nearly singular) are what the point solve's double-double pieces are for
-    (ba6_kernels.hpp)."""
+    (full_ba_kernels.hpp)."""
     sc = R.scene(R.CASES[name][0])
     w0, c0, p0 = R.split(sc, R.case_start(name))
     lo, hi = R.case_solve(name, False), R.case_solve(name, True)

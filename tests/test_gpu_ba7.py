@@ -6,8 +6,10 @@ ratio (DESIGN.md section 19 records them).  Every start perturbs the focal lengt
 
 Scene t (ba_reference.scene_t placed at ba7_reference's near start) puts all of camera 4's observations and both of track 5's beyond a Tukey
 cut of 10 px: a 7 x 7 camera block that is the damping alone, and points left with one observation inside the cut, for which the plain-fp64
-preconditioner block comes out indefinite at radius 1e10 (k_ba7_cam_precond sums such a row again, as k_ba6_cam_precond does).
+preconditioner block comes out indefinite at radius 1e10 (k_fba_cam_precond sums such a row again, at either camera dimension).
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -108,7 +110,7 @@ def test_step_against_refined_hp_solution(sname, radius):
 @pytest.mark.parametrize("sname,lname,radius", [("t", "tukey", 1e4), ("t", "tukey", 1e10), ("a", "geman", 1e4)])
 def test_step_under_tukey_and_geman_mcclure(sname, lname, radius):
     """Scene t under Tukey: a camera (all 7 coordinates) and a point whose blocks are the damping alone; [t-tukey-1e10] is the case
-    k_ba7_cam_precond's second tier exists for (test_gpu_ba6.py's test of the same name).
+    k_fba_cam_precond's second tier exists for (test_gpu_ba6.py's test of the same name).
 
     [t-tukey-1e10], at the default options like every case here, is also what gsfm_ba7_options_default's stall rule comes from.  More than
     half of the scene's observations are beyond the cut and the damping is 1e-16 to 1e-10 of the blocks; the preconditioned reduced system
@@ -124,7 +126,7 @@ def test_step_under_tukey_and_geman_mcclure(sname, lname, radius):
 @pytest.mark.parametrize("radius", [1e4, 1e10])
 def test_preconditioner_applied_to_the_right_hand_side_matches_the_hp_blocks(radius):
     """Scene t under Tukey, per camera: after ONE PCG iteration y_c = alpha M^-1 rhs with one scalar alpha for all cameras, so y_c / alpha is
-    k_ba7_cam_precond's block inverse applied to the row's right-hand side -- rows that take its second tier (the plain-fp64 block
+    k_fba_cam_precond's block inverse applied to the row's right-hand side -- rows that take its second tier (the plain-fp64 block
     indefinite) included.  Compared row by row with the hp tier's Schur-Jacobi block solved in long double.  alpha is the median of the
     entrywise quotients (a least-squares fit would carry the ill-conditioned rows' errors into every row).
     Bound per row: MARGIN x the larger of the fp64 tier's own deviation (its block, solved by elimination in float64) and
@@ -377,3 +379,22 @@ def test_argument_and_loss_errors():
     assert np.isnan(out[2][inactive]) and out[4]["termination"] in (0, 1, 2)
     with pytest.raises(ValueError):
         FocalBundleProblem(sc["intrinsics"], sc["track_ptr"], sc["obs_cam"], sc["obs_xy"], focal_free=np.ones(5))
+
+
+@pytest.mark.parametrize("name", ["a_near", "a_far", "a_near_mixed"])
+def test_focal_solve_keeps_the_bytes_of_the_commit_before_the_shared_kernel_family(name):
+    """gsfm_ba7_solve under Huber 10 from case_start (a_near_mixed: a_near with the MIXED focal mask): the bytes and counts recorded on an
+    MI355X from a library built from the commit before the 6- and 7-coordinate solvers became one kernel family and one host template
+    (tools/make_full_ba_parent_golden.py, tests/golden/ba7_solve_parent_bytes.npz).  The far start takes rejected steps."""
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ba7_solve_parent_bytes.npz"))
+    case = "a_near" if name == "a_near_mixed" else name
+    sc = R.scene(R.CASES[case][0], MIXED if name == "a_near_mixed" else None)
+    w1, c1, f1, p1, s = _problem(sc, LOSSES["huber"][0]).solve(*_start(sc, R.case_start(case)))
+    counts = [s["termination"], s["num_iterations"], s["num_successful_steps"], s["num_unsuccessful_steps"], s["num_cg_iterations"]]
+    print(name, counts, "final cost %.17g" % s["final_cost"])
+    if name == "a_far":
+        assert str(gold["far_case"]) == name and gold[name + "_counts"][3] > 0
+    for key, got in (("rot", w1), ("cam", c1), ("focal", f1), ("points", p1)):
+        assert got.tobytes() == gold[name + "_" + key].tobytes(), key
+    assert s["final_cost"] == gold[name + "_final_cost"][0]
+    assert counts == list(gold[name + "_counts"])

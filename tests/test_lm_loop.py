@@ -1,5 +1,5 @@
 """CPU check of the host control loops of the position and bundle solvers (csrc/lm_loop.hpp: lm_loop and pcg_loop, used by solver_pos.hpp,
-solver_ba.hpp and solver_ba6.hpp): the host compiler alone builds tests/cpp/lm_loop_test.cpp against the header, which is part of the check.
+solver_ba.hpp and solver_full_ba.hpp): the host compiler alone builds tests/cpp/lm_loop_test.cpp against the header, which is part of the check.
 The program drives the Levenberg-Marquardt loop with scripted operations (every ending, five invalid steps, the radii against
 trust_region.hpp bit for bit, statuses) and the PCG driver with scripted r.M^-1 r sequences under both settings of its breakdown flag."""
 import os
