@@ -9,7 +9,10 @@ positions), then the script's structure loop, 1 + num_retriangulation_iterations
     BundleAdjustmentAndRemoveOutlierPoints()                 BundleAdjustment(), then SetOutlierTracksToUnestimated(max_reprojection_error_in_pixels,
                                                              min_triangulation_angle_degrees) when the solution is usable
 and the PLY with the estimated tracks' points and the estimated camera positions.
-usage: reconstruction_pipeline.py <dataset_dir with EGs.txt, cc.txt, tracks.txt, coords.txt, list.txt> [flags.yaml]"""
+With use1DSfM=False the script's COLMAP branch: the view graph and the matches come from two_views.txt (AddColmapMatchesToReconstructionBuilder),
+CheckView() builds the tracks from the matches on the device (Theia's TrackBuilder, include/gsfm_tracks.h), and the same calls follow.
+usage: reconstruction_pipeline.py <dataset_dir with EGs.txt, cc.txt, tracks.txt, coords.txt, list.txt> [flags.yaml]
+       reconstruction_pipeline.py --colmap <dataset_dir with two_views.txt and images/> [flags.yaml] [images wildcard]"""
 import os
 import sys
 
@@ -21,14 +24,21 @@ import GlobalSfMpy as sfm  # noqa: E402
 from globalsfmpy_amd.loss_functions import HuberLoss  # noqa: E402
 
 
-def run_pipeline(dataset_dir, flagfile=None):
+def run_pipeline(dataset_dir, flagfile=None, use1DSfM=True, images_wildcard=None):
     """(reconstruction, reconstruction estimator, passes): per pass of the structure loop the structure summary, the estimated-track counts
     around the outlier step, and the summaries of the adjustments"""
     opts = sfm.ReconstructionBuilderOptions()
     if flagfile:
         sfm.load_1DSFM_config(flagfile, opts)
-    scene, graph, edge_cov = sfm.Reconstruction(), sfm.ViewGraph(), sfm.MapEdgesCovariance()
-    sfm.Read1DSFM(dataset_dir, scene, graph, edge_cov)
+    if use1DSfM:
+        scene, graph, edge_cov = sfm.Reconstruction(), sfm.ViewGraph(), sfm.MapEdgesCovariance()
+        sfm.Read1DSFM(dataset_dir, scene, graph, edge_cov)
+    else:   # sfm_pipeline.py:39-52
+        builder = sfm.ReconstructionBuilder(opts, sfm.FeaturesAndMatchesDatabase(os.path.join(dataset_dir, "database")))
+        sfm.AddColmapMatchesToReconstructionBuilder(os.path.join(dataset_dir, "two_views.txt"),
+                                                    images_wildcard or os.path.join(dataset_dir, "images", "*.JPG"), builder)
+        builder.CheckView()   # no tracks yet: built from the matches
+        graph, scene = builder.get_view_graph(), builder.get_reconstruction()
     solver = sfm.GlobalReconstructionEstimator(opts.reconstruction_estimator_options)
     solver.FilterInitialViewGraphAndCalibrateCameras(graph, scene)
     assert solver.EstimateGlobalRotations(HuberLoss(0.1)), solver.LastError()
@@ -57,8 +67,13 @@ def run_pipeline(dataset_dir, flagfile=None):
 
 
 if __name__ == "__main__":
-    dataset = sys.argv[1]
-    scene, solver, passes = run_pipeline(dataset, sys.argv[2] if len(sys.argv) > 2 else None)
+    argv = [a for a in sys.argv[1:] if a != "--colmap"]
+    dataset = argv[0]
+    scene, solver, passes = run_pipeline(dataset, argv[1] if len(argv) > 1 else None, use1DSfM="--colmap" not in sys.argv,
+                                         images_wildcard=argv[2] if len(argv) > 2 else None)
+    if scene.LastTrackBuildSummary():
+        print("tracks from matches: %(tracks)d tracks of %(features)d features (%(small)d small, %(inconsistent)d inconsistent features dropped)"
+              % scene.LastTrackBuildSummary())
     for i, record in enumerate(passes):
         print("pass %d: triangulated %d of %d unestimated tracks; bundle adjustment %s; %d outlier tracks removed, %d tracks estimated"
               % (i, record["structure"]["num_estimated"], record["structure"]["num_tracks"],

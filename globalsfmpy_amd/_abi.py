@@ -174,6 +174,11 @@ class TrackRefineOptions(C.Structure):
     ]
 
 
+class TrackBuildOptions(C.Structure):
+    """gsfm_tracks_build_options (include/gsfm_tracks.h)"""
+    _fields_ = [("min_track_length", C.c_int32), ("max_track_length", C.c_int32), ("hash_capacity_log2", C.c_int32)]
+
+
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 ALL_REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 LOSS_CALLBACK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_double, C.POINTER(C.c_double))
@@ -361,6 +366,11 @@ def declare_track_signatures(lib):
     lib.gsfm_tracks_outlier_tracks.argtypes = [C.c_uint32, _DP, _DP, _DP, C.POINTER(C.c_uint8), C.c_uint64, u64p, _U32P, _DP, _DP, C.POINTER(C.c_uint8),
                                                C.c_double, C.c_double, i32p, i32p, _DP, u64p, _DP]
     lib.gsfm_tracks_outlier_tracks.restype = C.c_int
+    lib.gsfm_tracks_build_default_options.argtypes = [C.POINTER(TrackBuildOptions)]
+    lib.gsfm_tracks_build_default_options.restype = None
+    for build in (lib.gsfm_tracks_build, lib.gsfm_tracks_build_sequential):
+        build.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, u64p, _DP, C.POINTER(TrackBuildOptions), u64p, _U32P, _DP, u64p, u64p, u64p, _DP]
+        build.restype = C.c_int
 
 
 def declare_ba_signatures(lib):

@@ -21,6 +21,7 @@
 #include "triangulate.hpp"
 #include "track_refine.hpp"
 #include "outlier_tracks.hpp"
+#include "track_build.hpp"
 #include "solver_ba.hpp"
 #include "solver_full_ba.hpp"
 
@@ -401,6 +402,25 @@ gsfm_status gsfm_tracks_launch_order(uint64_t n_tracks, const uint64_t* track_pt
     tri_bucket(n_tracks, track_ptr, order_out, class_begin_out);
     return GSFM_OK;
   });
+}
+
+void gsfm_tracks_build_default_options(gsfm_tracks_build_options* o) {
+  o->min_track_length = 2; o->max_track_length = 1000; o->hash_capacity_log2 = 0;
+}
+
+gsfm_status gsfm_tracks_build(uint32_t n_views, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j, const uint64_t* match_ptr,
+                              const double* matches, const gsfm_tracks_build_options* options, uint64_t* track_ptr_out, uint32_t* obs_view_out,
+                              double* obs_xy_out, uint64_t* n_tracks, uint64_t* n_obs, uint64_t* counts_out, double* kernel_ms) {
+  return guarded("the track builder", tracks_build_impl, n_views, n_edges, edge_i, edge_j, match_ptr, matches, options, track_ptr_out, obs_view_out,
+                 obs_xy_out, n_tracks, n_obs, counts_out, kernel_ms);
+}
+
+gsfm_status gsfm_tracks_build_sequential(uint32_t n_views, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j,
+                                         const uint64_t* match_ptr, const double* matches, const gsfm_tracks_build_options* options,
+                                         uint64_t* track_ptr_out, uint32_t* obs_view_out, double* obs_xy_out, uint64_t* n_tracks, uint64_t* n_obs,
+                                         uint64_t* counts_out, double* kernel_ms) {
+  return guarded("the sequential track builder", tracks_build_sequential_impl, n_views, n_edges, edge_i, edge_j, match_ptr, matches, options,
+                 track_ptr_out, obs_view_out, obs_xy_out, n_tracks, n_obs, counts_out, kernel_ms);
 }
 
 int64_t gsfm_rot_count_components(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j) {

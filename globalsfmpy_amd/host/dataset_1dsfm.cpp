@@ -178,6 +178,76 @@ void CollectEdgeMatches(const Tracks1DSfM& tr, const theia::ViewGraph& vg, EdgeM
   }
 }
 
+TrackBuildStats BuildTracksFromMatches(const EdgeMatches& em, int min_track_length, int max_track_length, Tracks1DSfM* out) {
+  *out = Tracks1DSfM();
+  TrackBuildStats stats;
+  stats.min_track_length = min_track_length; stats.max_track_length = max_track_length;
+  const size_t E = em.edges.size();
+  const uint64_t M = em.match_ptr.empty() ? 0 : em.match_ptr.back();
+  stats.num_matches = (size_t)M;
+  // dense view index = rank of the view id; intrinsics from the first edge naming the view
+  std::vector<theia::ViewId> views;
+  for (const auto& e : em.edges) { views.push_back(e.first); views.push_back(e.second); }
+  std::sort(views.begin(), views.end());
+  views.erase(std::unique(views.begin(), views.end()), views.end());
+  std::unordered_map<theia::ViewId, uint32_t> index;
+  for (size_t c = 0; c < views.size(); ++c) index[views[c]] = (uint32_t)c;
+  std::vector<uint32_t> edge_i(E), edge_j(E);
+  for (size_t e = 0; e < E; ++e) {
+    const theia::ViewId v[2] = {em.edges[e].first, em.edges[e].second};
+    edge_i[e] = index.at(v[0]); edge_j[e] = index.at(v[1]);
+    for (int s = 0; s < 2; ++s) {
+      if (out->principal_point.count(v[s])) continue;
+      const double* k = &em.intrinsics[6 * e + 3 * s];
+      const auto ff = em.first_focal.find(v[s]);
+      out->focal[v[s]] = ff == em.first_focal.end() ? k[0] : ff->second;
+      out->principal_point[v[s]] = Eigen::Vector2d(k[1], k[2]);
+    }
+  }
+  if (M == 0) { stats.built = true; return stats; }
+  std::vector<uint64_t> track_ptr(M + 1);
+  std::vector<uint32_t> obs_view(2 * M);
+  std::vector<double> obs_xy(4 * M);
+  gsfm_tracks_build_options o;
+  gsfm_tracks_build_default_options(&o);
+  o.min_track_length = min_track_length; o.max_track_length = max_track_length;
+  uint64_t T = 0, O = 0;
+  const gsfm_status st = gsfm_tracks_build((uint32_t)views.size(), E, edge_i.data(), edge_j.data(), em.match_ptr.data(), em.matches.data(), &o, track_ptr.data(),
+                                           obs_view.data(), obs_xy.data(), &T, &O, stats.counts, &stats.kernel_ms);
+  if (st == GSFM_ERR_NO_DEVICE) throw NoDeviceError(std::string("BuildTracksFromMatches: ") + gsfm_last_error());
+  if (st != GSFM_OK) throw std::runtime_error(std::string("BuildTracksFromMatches: ") + gsfm_last_error());
+  stats.built = true;
+  stats.num_tracks = (size_t)T; stats.num_observations = (size_t)O;
+  // Keypoints in feature-id order: a feature's id is the rank of its first endpoint, so walking the endpoints in the caller's order and numbering
+  // a kept feature at its first hit gives each view's kept features in ascending id.  (-0.0 + 0.0 = +0.0: one key for both zeros.)
+  struct Key {
+    uint32_t view; uint64_t x, y;
+    bool operator==(const Key& k) const { return view == k.view && x == k.x && y == k.y; }
+  };
+  struct KeyHash {
+    size_t operator()(const Key& k) const { uint64_t h = (k.x * 0x9e3779b97f4a7c15ull) ^ (k.y + 0xbf58476d1ce4e5b9ull + (k.x << 6)); return (size_t)((h ^ (h >> 31)) * 0x94d049bb133111ebull + k.view); }
+  };
+  auto bits = [](double v) { v += 0.0; uint64_t b; std::memcpy(&b, &v, 8); return b; };
+  std::unordered_map<Key, int, KeyHash> keypoint;   // a kept feature -> its keypoint index in its view, -1 until numbered
+  keypoint.reserve((size_t)O);
+  for (uint64_t k = 0; k < O; ++k) keypoint.emplace(Key{obs_view[k], bits(obs_xy[2 * k]), bits(obs_xy[2 * k + 1])}, -1);
+  for (size_t e = 0; e < E; ++e)
+    for (uint64_t m = em.match_ptr[e]; m < em.match_ptr[e + 1]; ++m)
+      for (int s = 0; s < 2; ++s) {
+        const double x = em.matches[4 * m + 2 * s], y = em.matches[4 * m + 2 * s + 1];
+        const auto it = keypoint.find(Key{s ? edge_j[e] : edge_i[e], bits(x), bits(y)});
+        if (it == keypoint.end() || it->second >= 0) continue;
+        auto& list = out->keypoints[s ? em.edges[e].second : em.edges[e].first];
+        it->second = (int)list.size();
+        list.emplace_back(x, y);
+      }
+  out->tracks.resize((size_t)T);
+  for (uint64_t t = 0; t < T; ++t)
+    for (uint64_t k = track_ptr[t]; k < track_ptr[t + 1]; ++k)
+      out->tracks[t].emplace_back(views[obs_view[k]], keypoint.at(Key{obs_view[k], bits(obs_xy[2 * k]), bits(obs_xy[2 * k + 1])}));
+  return stats;
+}
+
 #ifndef GSFM_USE_REAL_THEIA
 void FlattenTracks(const theia::Reconstruction& rec, FlatTracks* out) {
   *out = FlatTracks();
@@ -660,6 +730,8 @@ bool ReadColmapTwoViews(const std::string& path, const std::vector<std::string>&
     for (double& v : b) if (!(fin >> v)) { if (error) *error = "two_views.txt ends inside a feature list"; return false; }
     theia::ViewId i = view_id(n1), j = view_id(n2);
     if (i == j) continue;
+    out->matches.first_focal.emplace(i, f1);   // (emplace keeps the first line's value)
+    out->matches.first_focal.emplace(j, f2);
     theia::TwoViewInfo info;
     info.focal_length_1 = f1; info.focal_length_2 = f2;
     info.num_homography_inliers = info.num_verified_matches = info.visibility_score = (int)num;

@@ -128,6 +128,8 @@ struct ReconstructionEstimatorOptions {
 };
 struct ReconstructionBuilderOptions {
   int num_threads = 1;
+  int min_track_length = 2;      // reconstruction_builder.h: what CheckView()'s track builder drops (fewer features) ...
+  int max_track_length = 1000;   // ... and where it refuses a union (the YAML's min_track_length / max_track_length)
   ReconstructionEstimatorOptions reconstruction_estimator_options;
 };
 struct FeaturesAndMatchesDatabase {  // bind :166-170 wraps a RocksDB store; only its path matters to the rotation stage
@@ -377,6 +379,8 @@ void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions
   auto get = [&](const char* k, auto& dst) { if (cfg.contains(k) && !cfg[k].is_none()) dst = cfg[k].cast<std::decay_t<decltype(dst)>>(); };
   get("num_threads", options.num_threads);
   options.reconstruction_estimator_options.num_threads = options.num_threads;
+  get("min_track_length", options.min_track_length);   // bind :189-190
+  get("max_track_length", options.max_track_length);
   get("min_num_inliers_for_valid_match", options.reconstruction_estimator_options.min_num_two_view_inliers);
   get("post_rotation_filtering_degrees", options.reconstruction_estimator_options.rotation_filtering_max_difference_degrees);
   get("refine_relative_translations_after_rotation_estimation", options.reconstruction_estimator_options.refine_relative_translations_after_rotation_estimation);
@@ -518,6 +522,8 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
   py::class_<ReconstructionBuilderOptions>(m, "ReconstructionBuilderOptions")
       .def(py::init<>())
       .def_readwrite("num_threads", &ReconstructionBuilderOptions::num_threads)
+      .def_readwrite("min_track_length", &ReconstructionBuilderOptions::min_track_length)
+      .def_readwrite("max_track_length", &ReconstructionBuilderOptions::max_track_length)
       .def_readwrite("reconstruction_estimator_options", &ReconstructionBuilderOptions::reconstruction_estimator_options);
   m.def("load_1DSFM_config", &load_1dsfm_config);
 
@@ -526,6 +532,18 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def("NumTracks", &Reconstruction::NumTracks)
       .def("NumViews", &Reconstruction::NumViews)
       .def("NumEstimatedTracks", &Reconstruction::NumEstimatedTracks)
+      // what CheckView()'s track builder reported (gsfm_tracks_build's counts by name); None when the tracks were not built from matches
+      .def("LastTrackBuildSummary", [](const Reconstruction& r) -> py::object {
+        if (!r.track_build) return py::none();
+        const gsfm::TrackBuildStats& s = *r.track_build;
+        static const char* names[7] = {"features", "components", "small", "inconsistent", "degenerate", "replayed", "tracks"};
+        py::dict d;
+        d["built"] = s.built; d["error"] = s.error;
+        for (int k = 0; k < 7; ++k) d[names[k]] = s.counts[k];
+        d["num_matches"] = s.num_matches; d["num_tracks"] = s.num_tracks; d["num_observations"] = s.num_observations;
+        d["min_track_length"] = s.min_track_length; d["max_track_length"] = s.max_track_length; d["kernel_ms"] = s.kernel_ms;
+        return d;
+      })
       // the focal length a bundle adjustment with FOCAL_LENGTH estimated for the view, or None (FlattenedTracks() shows what is in use)
       .def("ViewFocalLength", [](const Reconstruction& r, ViewId v) -> py::object {
         const auto it = r.focal_length.find(v);
@@ -619,8 +637,34 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
         b->view_graph = b->owned_view_graph.get();
         return b;
       }))
-      .def("CheckView", [](ReconstructionBuilder& b) {  // views of the graph become views of the reconstruction
-        for (ViewId v : b.view_graph->ViewIds()) b.reconstruction->views.insert(v);
+      // views of the graph become views of the reconstruction; a reconstruction that has matches and no tracks gets its tracks built from
+      // them (src/GSfM_reconstruction_builder.cpp:441-444 -> Theia's TrackBuilder): the COLMAP branch.  Read1DSFM's tracks are left alone.
+      .def("CheckView", [](ReconstructionBuilder& b) {
+        Reconstruction* rec = b.reconstruction;
+        for (ViewId v : b.view_graph->ViewIds()) rec->views.insert(v);
+        if (rec->NumTracks() != 0 || !rec->matches) return;
+        auto tracks = std::make_shared<gsfm::Tracks1DSfM>();
+        auto stats = std::make_shared<gsfm::TrackBuildStats>();
+        try {
+          py::gil_scoped_release release;
+          *stats = gsfm::BuildTracksFromMatches(*rec->matches, b.options.min_track_length, b.options.max_track_length, tracks.get());
+        } catch (const gsfm::NoDeviceError& e) {
+          // Without a device nothing after this call runs either.  The reconstruction stays as the ingestion left it -- views and matches, no
+          // tracks -- and says so: a warning here, built = false in LastTrackBuildSummary().  Every other failure of the builder is raised.
+          stats->built = false; stats->error = e.what();
+          stats->min_track_length = b.options.min_track_length; stats->max_track_length = b.options.max_track_length;
+          rec->track_build = stats;
+          if (PyErr_WarnEx(PyExc_RuntimeWarning, (std::string("CheckView: no tracks were built from the matches: ") + e.what()).c_str(), 1) < 0) throw py::error_already_set();
+          return;
+        }
+        for (const auto& kv : tracks->keypoints) {
+          const auto name = rec->view_names.find(kv.first);
+          tracks->names[kv.first] = name == rec->view_names.end() ? std::to_string(kv.first) : name->second;
+        }
+        rec->track_point.clear();
+        rec->track_estimated.clear();
+        rec->tracks = tracks;
+        rec->track_build = stats;
       })
       // reference_internal: the (options, database) form owns both objects, so they must keep the builder alive
       .def("get_view_graph", [](ReconstructionBuilder& b) { return b.view_graph; }, py::return_value_policy::reference_internal)

@@ -569,6 +569,40 @@ def track_launch_order(track_ptr):
     return order, begin
 
 
+TRACK_BUILD_COUNTS = ("features", "components", "small", "inconsistent", "degenerate", "replayed", "tracks")
+
+
+def build_tracks(n_views, edge_i, edge_j, match_ptr, matches, min_track_length=2, max_track_length=1000, hash_capacity_log2=0, sequential=False):
+    """gsfm_tracks_build: tracks from two-view matches (Theia's TrackBuilder under the definition of include/gsfm_tracks.h) on the device.
+    edge_i, edge_j: the E view pairs; match_ptr: E + 1 offsets into matches (rows of x1 y1 x2 y2 in pixels, in the order of Theia's
+    AddFeatureCorrespondence calls).  hash_capacity_log2: the feature table's size, 0 = automatic (a test's handle on the probe chains).
+    sequential=True: gsfm_tracks_build_sequential, the same definition as sequential host code (no device).
+    Returns dict(track_ptr T + 1, obs_view, obs_xy O x 2, counts (dict of TRACK_BUILD_COUNTS), kernel_ms)."""
+    lib = _abi.load_library()
+    ei = np.ascontiguousarray(edge_i, dtype=np.uint32).reshape(-1)
+    ej = np.ascontiguousarray(edge_j, dtype=np.uint32).reshape(-1)
+    mp = np.ascontiguousarray(match_ptr, dtype=np.uint64).reshape(-1)
+    m = np.ascontiguousarray(matches, dtype=np.float64).reshape(-1, 4)
+    E = ei.shape[0]
+    if ej.shape[0] != E or mp.shape[0] != E + 1:
+        raise ValueError("edge_i, edge_j and match_ptr must describe the same edges")
+    if int(mp.max()) > m.shape[0]:
+        raise ValueError("match_ptr points past the end of matches")
+    M = int(mp[-1])
+    opt = _abi.TrackBuildOptions()
+    lib.gsfm_tracks_build_default_options(C.byref(opt))
+    opt.min_track_length, opt.max_track_length, opt.hash_capacity_log2 = int(min_track_length), int(max_track_length), int(hash_capacity_log2)
+    track_ptr, obs_view, obs_xy = np.zeros(M + 1, dtype=np.uint64), np.zeros(2 * M, dtype=np.uint32), np.zeros((2 * M, 2))
+    n_tracks, n_obs, counts, ms = C.c_uint64(0), C.c_uint64(0), np.zeros(7, dtype=np.uint64), C.c_double(0)
+    name = "gsfm_tracks_build_sequential" if sequential else "gsfm_tracks_build"
+    st = getattr(lib, name)(int(n_views), E, _p(ei), _p(ej), _p(mp), _p(m), C.byref(opt), _p(track_ptr), _p(obs_view), _p(obs_xy), C.byref(n_tracks),
+                            C.byref(n_obs), _p(counts), C.byref(ms))
+    _raise_if_failed(lib, name, st)
+    T, O = int(n_tracks.value), int(n_obs.value)
+    return {"track_ptr": track_ptr[:T + 1].copy(), "obs_view": obs_view[:O].copy(), "obs_xy": obs_xy[:O].copy(),
+            "counts": {k: int(v) for k, v in zip(TRACK_BUILD_COUNTS, counts)}, "kernel_ms": ms.value}
+
+
 class PositionProblem(ProblemBase):
     """Camera positions from relative translations (include/gsfm_pos.h): the reference's EstimatePositions with BASELINE residuals
     r = (c_j - c_i) / |c_j - c_i| - R(aa_i)^T t_ij on the device.  rel_t: E x 3 position_2 of each view pair (frame of camera i);

@@ -3,6 +3,7 @@
 // EGs.txt / covariance_rot.txt codecs, the post-rotation edge filter and the evaluation metrics.
 #pragma once
 #include <cstdint>
+#include <stdexcept>
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
@@ -12,7 +13,7 @@
 
 #include "compat.hpp"
 
-namespace gsfm { struct EdgeMatches; struct Tracks1DSfM; }
+namespace gsfm { struct EdgeMatches; struct Tracks1DSfM; struct TrackBuildStats; }
 
 namespace theia {
 
@@ -63,6 +64,8 @@ class Reconstruction {
   // The estimated focal length per view, in pixels: empty until a bundle adjustment with free focal lengths writes it (BundleAdjustment with
   // FOCAL_LENGTH).  FlattenTracks takes a view's entry in place of the EXIF / 1.2 x rule, so every later call sees the adjusted value.
   std::unordered_map<ViewId, double> focal_length;
+  // What the track builder reported when CheckView() built the tracks from the matches (the COLMAP branch); empty otherwise.
+  std::shared_ptr<const gsfm::TrackBuildStats> track_build;
   int NumTracks() const;
   int NumEstimatedTracks() const;
   int NumViews() const { return (int)views.size(); }
@@ -146,8 +149,29 @@ struct EdgeMatches {
   std::vector<double> matches;           // x1 y1 x2 y2
   std::vector<double> intrinsics;        // f1 u1 v1 f2 u2 v2
   std::vector<double> rotation, position;
+  // COLMAP ingestion only: per view the focal length of the first two_views.txt line that names it
+  std::unordered_map<theia::ViewId, double> first_focal;
 };
 void CollectEdgeMatches(const Tracks1DSfM& tracks, const theia::ViewGraph& view_graph, EdgeMatches* out);
+
+// ---- Tracks from the matches (the COLMAP branch: src/GSfM_reconstruction_builder.cpp:423-444 -> Theia's TrackBuilder), on the device:
+// gsfm_tracks_build under the definition of include/gsfm_tracks.h ----
+// Every match of `matches` is one AddFeatureCorrespondence, in the order of the flattened arrays (edges by sorted ViewIdPair, an edge's matches
+// as listed); dense view index = rank of the ViewId among the views the edges name.  Fills `out` as Read1DSFMTracks fills it for a 1DSfM dataset:
+// keypoints per view = the view's features that a track kept, in feature-id order; tracks as (view, keypoint index) in the entry's order; focal =
+// EdgeMatches::first_focal where it has the view, else that of the first edge naming it; principal point = that of the first edge naming the view.
+// names stay empty (the caller has them).  Throws when matches exist and no device is usable (NoDeviceError: there is no CPU fallback) or the
+// device call fails (std::runtime_error).
+struct NoDeviceError : std::runtime_error { using std::runtime_error::runtime_error; };
+struct TrackBuildStats {
+  bool built = false;            // CheckView(): false when no device was usable; `error` then says why and the reconstruction has no tracks
+  std::string error;
+  size_t num_matches = 0, num_tracks = 0, num_observations = 0;
+  uint64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};   // features, components, small, inconsistent, degenerate, replayed, tracks
+  int min_track_length = 2, max_track_length = 1000;
+  double kernel_ms = 0.0;
+};
+TrackBuildStats BuildTracksFromMatches(const EdgeMatches& matches, int min_track_length, int max_track_length, Tracks1DSfM* out);
 
 #ifndef GSFM_USE_REAL_THEIA
 // ---- EstimateStructure without the per-track refinement (src/GSfM_global_reconstruction_estimator.cpp:621-636 -> Theia's

@@ -195,6 +195,70 @@ gsfm_status gsfm_tracks_outlier_tracks(uint32_t n_cams, const double* rot_aa, co
                                        double max_reprojection_error_pixels, double min_triangulation_angle_degrees, int32_t* status_out,
                                        int32_t* n_views_out, double* mean_sq_err_out, uint64_t* counts_out, double* kernel_ms);
 
+/* ---- Tracks from two-view matches: gsfm_tracks_build ----
+ *
+ * Restates Theia's TrackBuilder (sfm/track_builder.cc over math/graph/connected_components.h), which the reference's COLMAP branch runs when
+ * the reconstruction has no tracks: every inlier match of every view pair is one AddFeatureCorrespondence, BuildTracks turns the connected
+ * components into tracks.
+ *
+ * Input: n_edges view pairs (edge_i[e], edge_j[e], both < n_views and different), the CSR match_ptr[n_edges + 1] (match_ptr[0] = 0,
+ * non-decreasing), matches (n_matches x 4: x1 y1 of view edge_i, x2 y2 of view edge_j, pixels), n_matches = match_ptr[n_edges], in the
+ * caller's order: match m stands for the m-th call of AddFeatureCorrespondence.
+ *
+ *   endpoints   endpoint 2m is the first feature of match m (view edge_i, x1 y1), endpoint 2m + 1 its second (view edge_j, x2 y2).
+ *   features    two endpoints are the same feature when they have the same view and equal coordinates, compared as doubles: -0.0 equals 0.0.
+ *               A coordinate that is not finite is GSFM_ERR_INVALID_ARG.  A feature's representative is its smallest endpoint index; the
+ *               feature's id is the rank of its representative among all representatives: Theia's FindOrInsert numbering for this order
+ *               of calls.  The feature's pixel is its representative's, bit for bit (so of -0.0 and 0.0 the first one met).
+ *   components  each match joins its two features.  The plain components are those of that graph; a component's label is its smallest
+ *               feature id.  Theia refuses a union that would make a component larger than max_track_length (connected_components.h:87-108:
+ *               nothing happens when both features share a root or when the two sizes add up to more than the maximum), in call order.
+ *               A plain component of at most max_track_length features never met a refusal and is final.  The matches of every larger
+ *               plain component are replayed in the caller's order under that rule -- on the host, sequentially: the path is rare with
+ *               the reference's max_track_length of 1000 -- and the pieces they end in take its place, each labelled by its smallest
+ *               feature id.  That gives Theia's components for the same order of calls.
+ *   tracks      walking the final components by ascending label:
+ *                 fewer than min_track_length features: dropped, counted `small` (before any duplicate removal, as in Theia);
+ *                 its features in ascending feature id; a feature whose view already occurs earlier in the track is dropped, counted
+ *                 `inconsistent`.  DEPARTURE: Theia keeps whichever feature of a view its unordered_set yields first;
+ *                 fewer than two observations left: the track is dropped, counted `degenerate` (Theia would abort in AddTrack).  Since a
+ *                 match joins two views this needs a component of one feature, that is min_track_length <= 1 and a refused union;
+ *                 otherwise a track: its observations are (view, pixel) of the kept features in that order.
+ * Outputs (the caller provides the capacity: n_matches + 1 offsets, 2 n_matches observations): track_ptr_out (CSR, track_ptr_out[0] = 0),
+ * obs_view_out, obs_xy_out (x y per observation), *n_tracks, *n_obs; optional (NULL: not returned) counts_out[7] = features, final
+ * components, small, inconsistent, degenerate, replayed (the plain components larger than max_track_length), tracks; kernel_ms (device time
+ * of the kernels, the waits of the host's looks at the component rounds included).
+ * The output is a pure function of the input arrays: two calls return the same bytes, whatever lane wins a hash slot or an atomic.
+ *
+ * Options (NULL: the defaults): min_track_length 2, max_track_length 1000 (both Theia's and the reference's flag files'), both >= 1;
+ * hash_capacity_log2: the feature table has 2^hash_capacity_log2 slots, 0 = automatic (the smallest power of two >= 4 n_matches, at least
+ * 2^10).  It exists so that a test can force long probe chains: a capacity below the number of endpoints (2 n_matches), or above 2^31, is
+ * GSFM_ERR_INVALID_ARG, not a hang.
+ *
+ * Device memory about 300 B per match.  Arguments are checked on the host before any device call (GSFM_ERR_INVALID_ARG: a NULL required
+ * pointer, match_ptr[0] != 0, a match_ptr that decreases, a view index >= n_views, an edge from a view to itself, more than 2^29 matches,
+ * a coordinate that is not finite, an option out of range); no matches: GSFM_OK with no track and no device call; otherwise without a
+ * device GSFM_ERR_NO_DEVICE: there is no host fallback.
+ *
+ * gsfm_tracks_build_sequential is the same definition as plain sequential host code (hash map, union-find with the refusal rule over all
+ * matches, no device is touched): the replay above is its union rule; it is the host baseline of tools/time_track_build.py and a test
+ * reference.  hash_capacity_log2 is checked and otherwise ignored; kernel_ms is 0. */
+typedef struct {
+  int32_t min_track_length;    /* 2 */
+  int32_t max_track_length;    /* 1000 */
+  int32_t hash_capacity_log2;  /* 0: automatic */
+} gsfm_tracks_build_options;
+
+void gsfm_tracks_build_default_options(gsfm_tracks_build_options* options);
+
+gsfm_status gsfm_tracks_build(uint32_t n_views, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j, const uint64_t* match_ptr,
+                              const double* matches, const gsfm_tracks_build_options* options, uint64_t* track_ptr_out, uint32_t* obs_view_out,
+                              double* obs_xy_out, uint64_t* n_tracks, uint64_t* n_obs, uint64_t* counts_out, double* kernel_ms);
+gsfm_status gsfm_tracks_build_sequential(uint32_t n_views, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j,
+                                         const uint64_t* match_ptr, const double* matches, const gsfm_tracks_build_options* options,
+                                         uint64_t* track_ptr_out, uint32_t* obs_view_out, double* obs_xy_out, uint64_t* n_tracks, uint64_t* n_obs,
+                                         uint64_t* counts_out, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
