@@ -127,6 +127,17 @@ class PosSummary(C.Structure):
         return d
 
 
+class PospSummary(C.Structure):
+    """gsfm_posp_summary (include/gsfm_posp.h)"""
+    _fields_ = [("pos", PosSummary), ("num_observations_used", C.c_uint64), ("num_active_points", C.c_uint64)]
+
+    def as_dict(self):
+        d = self.pos.as_dict()
+        d["num_observations_used"] = self.num_observations_used
+        d["num_active_points"] = self.num_active_points
+        return d
+
+
 class BaOptions(C.Structure):
     """gsfm_ba_options (include/gsfm_ba.h)"""
     _fields_ = [
@@ -321,6 +332,7 @@ def load_library():
     declare_ba_signatures(lib)
     declare_ba6_signatures(lib)
     declare_ba7_signatures(lib)
+    declare_posp_signatures(lib)
     _lib = lib
     return lib
 
@@ -389,6 +401,25 @@ def declare_ba_signatures(lib):
     lib.gsfm_ba_step_check.restype = C.c_int
     lib.gsfm_ba_time_kernels.argtypes = [C.c_void_p, _DP, _DP, C.c_double, C.c_int32, _DP]; lib.gsfm_ba_time_kernels.restype = C.c_int
     lib.gsfm_ba_problem_destroy.argtypes = [C.c_void_p]; lib.gsfm_ba_problem_destroy.restype = None
+
+
+def declare_posp_signatures(lib):
+    """include/gsfm_posp.h (the options are gsfm_pos.h's)"""
+    u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    lib.gsfm_posp_abi_version.restype = C.c_int
+    lib.gsfm_posp_problem_create.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, _DP, _DP, _DP, _DP, C.c_uint64, u64p, _U32P, _DP, C.c_double,
+                                             C.POINTER(C.c_void_p)]
+    lib.gsfm_posp_problem_create.restype = C.c_int
+    lib.gsfm_posp_set_loss.argtypes = [C.c_void_p, C.POINTER(LossNode), C.c_int32]; lib.gsfm_posp_set_loss.restype = C.c_int
+    lib.gsfm_posp_set_loss_callback.argtypes = [C.c_void_p, LOSS_CALLBACK_FN, C.c_void_p]; lib.gsfm_posp_set_loss_callback.restype = C.c_int
+    lib.gsfm_posp_solve.argtypes = [C.c_void_p, _DP, _DP, C.c_int32, C.POINTER(PosOptions), C.POINTER(PospSummary)]; lib.gsfm_posp_solve.restype = C.c_int
+    lib.gsfm_posp_residuals.argtypes = [C.c_void_p] + [_DP] * 7; lib.gsfm_posp_residuals.restype = C.c_int
+    lib.gsfm_posp_linearize.argtypes = [C.c_void_p] + [_DP] * 7; lib.gsfm_posp_linearize.restype = C.c_int
+    lib.gsfm_posp_schur_matvec.argtypes = [C.c_void_p, _DP, C.c_double, C.POINTER(PosOptions), _DP]; lib.gsfm_posp_schur_matvec.restype = C.c_int
+    lib.gsfm_posp_step_check.argtypes = [C.c_void_p, _DP, _DP, C.c_int32, C.c_double, C.POINTER(PosOptions)] + [_DP] * 6 + [i32p]
+    lib.gsfm_posp_step_check.restype = C.c_int
+    lib.gsfm_posp_time_kernels.argtypes = [C.c_void_p, _DP, _DP, C.c_double, C.c_int32, _DP]; lib.gsfm_posp_time_kernels.restype = C.c_int
+    lib.gsfm_posp_problem_destroy.argtypes = [C.c_void_p]; lib.gsfm_posp_problem_destroy.restype = None
 
 
 def declare_ba6_signatures(lib):

@@ -24,6 +24,7 @@
 #include "track_build.hpp"
 #include "solver_ba.hpp"
 #include "solver_full_ba.hpp"
+#include "solver_pos_points.hpp"
 
 // =============================================================================================
 extern "C" {

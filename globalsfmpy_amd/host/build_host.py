@@ -24,7 +24,7 @@ def main():
     force = "--force" in sys.argv
     import pybind11
     cxx = os.environ.get("CXX", "g++")
-    inc = [os.path.join(ROOT, "include", "gsfm", f) for f in os.listdir(os.path.join(ROOT, "include", "gsfm"))] + [os.path.join(ROOT, "include", "gsfm_rot.h"), os.path.join(ROOT, "include", "gsfm_pos.h"), os.path.join(ROOT, "include", "gsfm_tracks.h")]
+    inc = [os.path.join(ROOT, "include", "gsfm", f) for f in os.listdir(os.path.join(ROOT, "include", "gsfm"))] + [os.path.join(ROOT, "include", "gsfm_rot.h"), os.path.join(ROOT, "include", "gsfm_pos.h"), os.path.join(ROOT, "include", "gsfm_posp.h"), os.path.join(ROOT, "include", "gsfm_tracks.h")]
     common = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-fvisibility=default"]
     link = ["-L" + PKG, "-lgsfm_rot", "-Wl,-rpath,$ORIGIN"]
     est = os.path.join(PKG, "libgsfm_estimator.so")

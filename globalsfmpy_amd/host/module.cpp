@@ -14,6 +14,7 @@
 #include <memory>
 
 #include "../../include/gsfm/GSfM_nonlinear_position_estimator.hpp"
+#include "../../include/gsfm/position_track_selection.hpp"
 #include "../../include/gsfm/GSfM_nonlinear_rotation_estimator.hpp"
 #include "../../include/gsfm/evaluation.hpp"
 #include "../../include/gsfm/view_graph.hpp"
@@ -125,6 +126,9 @@ struct ReconstructionEstimatorOptions {
   // :242; which intrinsics BundleAdjustment() moves (the YAML's intrinsics_to_optimize; the reference's flags.yaml sets FOCAL_LENGTH, its
   // flags_1dsfm.yaml NONE).  NONE and FOCAL_LENGTH run on the device; any other bit makes BundleAdjustment() fail with a message.
   gsfm::OptimizeIntrinsicsType intrinsics_to_optimize = gsfm::OptimizeIntrinsicsType::NONE;
+  // reconstruction_estimator_options.h: what the position stage's estimator is built with (the YAML's position_estimation_min_num_tracks_per_view
+  // and position_estimation_robust_loss_width; GlobalReconstructionEstimator.PositionEstimator() hands them over with the reconstruction)
+  GSfMNonlinearPositionEstimator::Options nonlinear_position_estimator_options;
 };
 struct ReconstructionBuilderOptions {
   int num_threads = 1;
@@ -259,6 +263,12 @@ class GlobalReconstructionEstimator {
                                          refined ? &r : nullptr, only_unestimated);
     structure_refine_asked_ = refine;
     return structure_;
+  }
+  // reference :565-603 up to the solve: the position estimator over this estimator's options and reconstruction (the reference's
+  // EstimatePosition builds it the same way and then calls EstimatePositions on the view graph's edges and the estimated orientations)
+  GSfMNonlinearPositionEstimator* PositionEstimator() {
+    if (!reconstruction_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
+    return new GSfMNonlinearPositionEstimator(options_.nonlinear_position_estimator_options, *reconstruction_);
   }
   // Theia's BundleAdjustCameraPositionsAndPoints: positions and points move, orientations and intrinsics are held; the loss of
   // bundle_adjustment_loss_function_type / _width; 100 iterations, x 1.5 from min_cameras_for_iterative_solver views on (Theia's
@@ -395,6 +405,8 @@ void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions
   get("num_retriangulation_iterations", options.reconstruction_estimator_options.num_retriangulation_iterations);
   get("refine_camera_positions_and_points_after_position_estimation",
       options.reconstruction_estimator_options.refine_camera_positions_and_points_after_position_estimation);
+  get("position_estimation_min_num_tracks_per_view", options.reconstruction_estimator_options.nonlinear_position_estimator_options.min_num_points_per_view);   // bind :228-230
+  get("position_estimation_robust_loss_width", options.reconstruction_estimator_options.nonlinear_position_estimator_options.robust_loss_width);
   // bind :199-200: a bitmask of names joined by '|' (StringToOptimizeIntrinsicsType); an absent key leaves NONE
   std::string intrinsics;
   get("intrinsics_to_optimize", intrinsics);
@@ -434,8 +446,39 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
 
   // reference src/GSfM_nonlinear_position_estimator.cpp on the device (include/gsfm_pos.h): fills `positions` in place; the view held
   // constant is positions->begin() of the map, as in the reference (FixedView() tells which)
+  py::class_<GSfMNonlinearPositionEstimator::Options>(m, "NonlinearPositionEstimatorOptions")
+      .def(py::init<>())
+      .def_readwrite("num_threads", &GSfMNonlinearPositionEstimator::Options::num_threads)
+      .def_readwrite("max_num_iterations", &GSfMNonlinearPositionEstimator::Options::max_num_iterations)
+      .def_readwrite("robust_loss_width", &GSfMNonlinearPositionEstimator::Options::robust_loss_width)
+      .def_readwrite("min_num_points_per_view", &GSfMNonlinearPositionEstimator::Options::min_num_points_per_view)
+      .def_readwrite("point_to_camera_weight", &GSfMNonlinearPositionEstimator::Options::point_to_camera_weight)
+      .def_readwrite("rays_from_reconstruction_orientation", &GSfMNonlinearPositionEstimator::Options::rays_from_reconstruction_orientation);
+  // include/gsfm/position_track_selection.hpp: the tracks of the point-to-camera constraints and their weight, on a track CSR over view ids
+  m.def("SelectTracksForPositionEstimation", [](const std::vector<uint32_t>& positioned_views, const std::vector<uint64_t>& track_ptr,
+                                                const std::vector<uint32_t>& obs_view, int min_num_points_per_view) {
+    if (track_ptr.empty() || track_ptr[0] != 0 || track_ptr.back() != obs_view.size()) throw std::invalid_argument("track_ptr does not describe obs_view");
+    for (size_t t = 0; t + 1 < track_ptr.size(); ++t) if (track_ptr[t + 1] < track_ptr[t]) throw std::invalid_argument("track_ptr decreases");
+    const gsfm::PositionTrackSelection sel = gsfm::SelectTracksForPositionEstimation(positioned_views, track_ptr.size() - 1, track_ptr.data(), obs_view.data(),
+                                                                                      min_num_points_per_view);
+    py::dict d, credits;
+    for (const auto& kv : sel.credits) credits[py::int_(kv.first)] = kv.second;
+    d["tracks"] = sel.tracks; d["credits"] = credits; d["num_point_to_camera_constraints"] = sel.num_point_to_camera_constraints;
+    return d;
+  });
+  m.def("PointToCameraWeight", &gsfm::PointToCameraWeight);
   py::class_<GSfMNonlinearPositionEstimator>(m, "NonlinearPositionEstimator")
       .def(py::init<>())
+      .def(py::init<const GSfMNonlinearPositionEstimator::Options&>())
+      .def(py::init<const GSfMNonlinearPositionEstimator::Options&, const Reconstruction&>(), py::keep_alive<1, 3>())   // the reference's constructor
+      .def_property_readonly("options", [](GSfMNonlinearPositionEstimator& e) { return e.MutableEstimatorOptions(); }, py::return_value_policy::reference_internal)
+      .def("LastPointConstraints", [](const GSfMNonlinearPositionEstimator& e) {
+        const GSfMNonlinearPositionEstimator::PointConstraints& p = e.LastPointConstraints();
+        py::dict d;
+        d["num_tracks"] = p.num_tracks; d["num_constraints"] = p.num_constraints; d["num_observations_used"] = p.num_observations_used;
+        d["num_active_points"] = p.num_active_points; d["weight"] = p.weight;
+        return d;
+      })
       .def(py::init([](int max_num_iterations, double robust_loss_width) {
              GSfMNonlinearPositionEstimator::Options o;
              o.max_num_iterations = max_num_iterations; o.robust_loss_width = robust_loss_width;
@@ -518,7 +561,8 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def_readwrite("max_reprojection_error_in_pixels", &ReconstructionEstimatorOptions::max_reprojection_error_in_pixels)
       .def_readwrite("num_retriangulation_iterations", &ReconstructionEstimatorOptions::num_retriangulation_iterations)
       .def_readwrite("refine_camera_positions_and_points_after_position_estimation",
-                     &ReconstructionEstimatorOptions::refine_camera_positions_and_points_after_position_estimation);
+                     &ReconstructionEstimatorOptions::refine_camera_positions_and_points_after_position_estimation)
+      .def_readwrite("nonlinear_position_estimator_options", &ReconstructionEstimatorOptions::nonlinear_position_estimator_options);
   py::class_<ReconstructionBuilderOptions>(m, "ReconstructionBuilderOptions")
       .def(py::init<>())
       .def_readwrite("num_threads", &ReconstructionBuilderOptions::num_threads)
@@ -692,6 +736,9 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
         return refine_stats_dict(st);
       })
       .def("FilterRelativeTranslation", &GlobalReconstructionEstimator::FilterRelativeTranslation, py::call_guard<py::gil_scoped_release>())
+      // the position stage's estimator with this estimator's nonlinear_position_estimator_options and its reconstruction (the tracks of the
+      // point-to-camera constraints); the caller runs EstimatePositions(view_graph edges, orientations, positions, loss)
+      .def("PositionEstimator", &GlobalReconstructionEstimator::PositionEstimator, py::return_value_policy::take_ownership, py::keep_alive<0, 1>())
       .def("EstimateStructure", [](GlobalReconstructionEstimator& e, bool refine, bool only_unestimated) {
         gsfm::EstimateStructureStats st;
         { py::gil_scoped_release release; st = e.EstimateStructure(refine, only_unestimated); }

@@ -787,6 +787,124 @@ def bundle_adjust_positions_and_points(rot_aa, cam_pos, intrinsics, track_ptr, o
         prob.close()
 
 
+class PointPositionProblem(_BundleProblemBase):
+    """Camera positions from relative translations AND feature tracks (include/gsfm_posp.h): PositionProblem's edges plus, per track, one
+    point tied to every camera that sees it by the direction residual w_p ((X - c) / |X - c| - ray); the points are eliminated and the
+    reduced camera system is solved by PCG.  edge_i / edge_j / rel_t / rot_aa: as PositionProblem; ray_rot_aa: N x 3 orientations the
+    feature rays are rotated by (None: rot_aa); intrinsics: N x 3 (f u v); track_ptr / obs_cam / obs_xy: the track CSR of triangulate_tracks
+    (track_ptr None: no tracks).  A new problem has Ceres' NULL loss; set_loss takes PositionProblem's native losses."""
+    _prefix = "gsfm_posp_"
+
+    def __init__(self, n_cams, edge_i, edge_j, rel_t, rot_aa, ray_rot_aa=None, intrinsics=None, track_ptr=None, obs_cam=None, obs_xy=None,
+                 point_to_camera_weight=0.5):
+        lib = _abi.load_library()
+        n = int(n_cams)
+        ei = np.ascontiguousarray(edge_i, dtype=np.uint32)
+        ej = np.ascontiguousarray(edge_j, dtype=np.uint32)
+        rel = np.ascontiguousarray(rel_t, dtype=np.float64).reshape(-1, 3)
+        rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(n, 3)
+        if not (ei.shape == ej.shape == (rel.shape[0],)):
+            raise ValueError("edge_i, edge_j and rel_t must describe the same edges")
+        if track_ptr is None:
+            track_ptr, obs_cam, obs_xy = np.zeros(1, np.uint64), np.zeros(0, np.uint32), np.zeros((0, 2))
+        ray = rot if ray_rot_aa is None else ray_rot_aa
+        K = np.zeros((n, 3)) if intrinsics is None else intrinsics
+        (ray, K), tp, oc, xy, _, _, _ = _track_arrays((("ray_rot_aa", ray), ("intrinsics", K)), track_ptr, obs_cam, obs_xy, per=_PER_ENTRY)
+        if ray.shape[0] != n:
+            raise ValueError("rot_aa, ray_rot_aa and intrinsics must describe the same cameras")
+        T = tp.shape[0] - 1
+        h = C.c_void_p()
+        st = lib.gsfm_posp_problem_create(n, ei.size, _p(ei), _p(ej), _p(rel), _p(rot), _p(ray), _p(K), T, _p(tp), _p(oc), _p(xy),
+                                          float(point_to_camera_weight), C.byref(h))
+        _raise_if_failed(lib, "gsfm_posp_problem_create", st)
+        self._adopt(lib, h, n, T, int(oc.shape[0]))
+        self.n_edges = int(ei.size)
+
+    def set_loss(self, loss):
+        """loss: None (Ceres' NULL loss), a list of (kind, p0, p1, p2) nodes or an object with .native_program(), as PositionProblem takes
+        them; an object with only .Evaluate (a host callback) is refused by the library."""
+        nodes = _loss_nodes(loss, "position problem with points", callback_ok=True)
+        if nodes is None:
+            self._check(self._lib.gsfm_posp_set_loss_callback(self._h, _abi.LOSS_CALLBACK_FN(), None), "set_loss_callback")
+        arr, n = _abi.make_program(nodes)
+        self._check(self._lib.gsfm_posp_set_loss(self._h, arr, n), "set_loss")
+
+    def default_options(self):
+        o = _abi.PosOptions()
+        self._lib.gsfm_pos_options_default(C.byref(o))
+        return o
+
+    def _point(self, cam_pos, points):
+        c = np.zeros((self.n_cams, 3)) if cam_pos is None else np.array(cam_pos, dtype=np.float64, order="C").reshape(self.n_cams, 3)
+        p = np.ones((self.n_tracks, 3)) if points is None else np.array(points, dtype=np.float64, order="C").reshape(self.n_tracks, 3)
+        return c, p
+
+    def solve(self, cam_pos=None, points=None, fixed_cam=0, **options):
+        """cam_pos / points: start values (None: the reference's, cameras at 0 and points at (1, 1, 1)).  fixed_cam: the camera held constant
+        (-1: none).  Returns (camera positions N x 3, points T x 3, summary dict); inactive rows are returned as given."""
+        c, p = self._point(cam_pos, points)
+        o, s = self._options(options), _abi.PospSummary()
+        self._check(self._lib.gsfm_posp_solve(self._h, _p(c), _p(p), int(fixed_cam), C.byref(o), C.byref(s)), "solve")
+        return c, p, s.as_dict()
+
+    def residuals(self, cam_pos, points):
+        """dict(r_edge E x 3, rho_edge E, r_obs n_obs x 3 (weighted), rho_obs n_obs, ray n_obs x 3); zeros for an observation that is not used"""
+        c, p = self._point(cam_pos, points)
+        E, O = self.n_edges, self.n_obs
+        out = {"r_edge": np.zeros((E, 3)), "rho_edge": np.zeros(E), "r_obs": np.zeros((O, 3)), "rho_obs": np.zeros(O), "ray": np.zeros((O, 3))}
+        self._check(self._lib.gsfm_posp_residuals(self._h, _p(c), _p(p), _p(out["r_edge"]), _p(out["rho_edge"]), _p(out["r_obs"]), _p(out["rho_obs"]),
+                                                  _p(out["ray"])), "residuals")
+        return out
+
+    def linearize(self, cam_pos, points):
+        """dict(cost, grad_cam N x 3, grad_point T x 3, diag_cam N x 3 x 3, diag_point T x 3 x 3), every camera of the edges active"""
+        c, p = self._point(cam_pos, points)
+        cost = np.zeros(1)
+        gc, gp = np.zeros((self.n_cams, 3)), np.zeros((self.n_tracks, 3))
+        dc, dp = np.zeros((self.n_cams, 3, 3)), np.zeros((self.n_tracks, 3, 3))
+        self._check(self._lib.gsfm_posp_linearize(self._h, _p(c), _p(p), _p(cost), _p(gc), _p(gp), _p(dc), _p(dp)), "linearize")
+        return {"cost": float(cost[0]), "grad_cam": gc, "grad_point": gp, "diag_cam": dc, "diag_point": dp}
+
+    def schur_matvec(self, v, radius=1e4, **options):
+        """y = Sc v (N x 3) for the last linearize / step_check (and its active set), damped at `radius`"""
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(self.n_cams, 3)
+        y = np.zeros((self.n_cams, 3))
+        o = self._options(options)
+        self._check(self._lib.gsfm_posp_schur_matvec(self._h, _p(v), float(radius), C.byref(o), _p(y)), "schur_matvec")
+        return y
+
+    def step_check(self, cam_pos, points, fixed_cam=0, radius=1e4, **options):
+        """gsfm_posp_step_check: dict(rhs, y_cam, y_point, delta_cam, delta_point, model_cost_change, dg, dld, cg_rel, cg_iterations, stalled)"""
+        c, p = self._point(cam_pos, points)
+        o = self._options(options)
+        N, T = self.n_cams, self.n_tracks
+        rhs, yc, yp, dc, dp = np.zeros((N, 3)), np.zeros((N, 3)), np.zeros((T, 3)), np.zeros((N, 3)), np.zeros((T, 3))
+        scal, info = np.zeros(4), np.zeros(2, dtype=np.int32)
+        st = self._lib.gsfm_posp_step_check(self._h, _p(c), _p(p), int(fixed_cam), float(radius), C.byref(o), _p(rhs), _p(yc), _p(yp), _p(dc), _p(dp),
+                                            _p(scal), _p(info))
+        self._check(st, "step_check")
+        return {"rhs": rhs, "y_cam": yc, "y_point": yp, "delta_cam": dc, "delta_point": dp, "model_cost_change": scal[0], "dg": scal[1],
+                "dld": scal[2], "cg_rel": scal[3], "cg_iterations": int(info[0]), "stalled": bool(info[1])}
+
+    def time_kernels(self, cam_pos, points, radius=1e4, reps=10):
+        """mean device microseconds of the kernels of one linearisation and one Schur product (gsfm_posp_time_kernels)"""
+        c, p = self._point(cam_pos, points)
+        out = np.zeros(7)
+        self._check(self._lib.gsfm_posp_time_kernels(self._h, _p(c), _p(p), float(radius), int(reps), _p(out)), "time_kernels")
+        return dict(zip(("rays", "lin_tracks", "lin_cameras", "cost_tracks", "point_pass", "camera_pass", "preconditioner"), out))
+
+
+def estimate_positions_with_points(n_cams, edge_i, edge_j, rel_t, rot_aa, intrinsics, track_ptr, obs_cam, obs_xy, point_to_camera_weight=0.5,
+                                   ray_rot_aa=None, cam_pos=None, points=None, fixed_cam=0, loss=None, **options):
+    """One call: PointPositionProblem(...).set_loss(loss).solve(cam_pos, points, fixed_cam, **options).  Returns (cam_pos, points, summary dict)."""
+    prob = PointPositionProblem(n_cams, edge_i, edge_j, rel_t, rot_aa, ray_rot_aa, intrinsics, track_ptr, obs_cam, obs_xy, point_to_camera_weight)
+    try:
+        prob.set_loss(loss)
+        return prob.solve(cam_pos, points, fixed_cam, **options)
+    finally:
+        prob.close()
+
+
 class FullBundleProblem(_BundleProblemBase):
     """The full bundle adjustment (include/gsfm_ba6.h): Theia's GlobalReconstructionEstimator::BundleAdjustment on the device, camera
     orientations, camera positions and points moving together (intrinsics held), the points eliminated and the reduced 6 x 6-block camera

@@ -333,6 +333,34 @@ def make_tracks(n_cams, n_tracks, seed, lengths=(2, 3, 4, 5, 8, 13), length_weig
             "obs_xy": obs_xy, "gt_points": gt, "is_outlier": is_out}
 
 
+def make_position_scene(n_cams, n_edges, n_tracks, seed, lengths=(2, 3, 4, 5, 8, 13), noise=0.0, outlier_frac=0.0, extent=10.0):
+    """A position graph and feature tracks over the same ground-truth cameras (include/gsfm_posp.h): make_position_graph(n_cams, n_edges, seed,
+    outlier_frac, noise, extent)'s dict plus intrinsics (N x 3: f u v), track_ptr, obs_cam, obs_xy and gt_points.  The points lie in a slab
+    4 .. 6 extent in front of the cameras (whose rotations are small, so every point is in front of every camera); a track's k-th observation
+    is taken by camera sigma[(a + k) mod n_cams] (make_tracks' rule: distinct cameras up to n_cams observations), its length drawn from
+    `lengths`; the pixels are the ground-truth projections with R = aa_to_matrix(rot_aa), plus N(0, (noise f)^2) per coordinate."""
+    g = make_position_graph(n_cams, n_edges, seed, outlier_frac=outlier_frac, noise=noise, extent=extent)
+    rng = np.random.Generator(np.random.PCG64([seed, 1]))
+    intrinsics = np.c_[rng.uniform(900.0, 1500.0, n_cams), rng.integers(500, 700, n_cams).astype(np.float64),
+                       rng.integers(350, 450, n_cams).astype(np.float64)]
+    lengths = np.asarray(lengths, dtype=np.int64)
+    length = lengths[rng.choice(lengths.size, size=n_tracks)]
+    track_ptr = np.concatenate([[0], np.cumsum(length)]).astype(np.uint64)
+    n_obs = int(track_ptr[-1])
+    gt = np.c_[extent * rng.uniform(-1.0, 1.0, (n_tracks, 2)), extent * rng.uniform(4.0, 6.0, n_tracks)]
+    sigma = rng.permutation(n_cams)
+    offset = rng.integers(0, n_cams, n_tracks)
+    track_of = np.repeat(np.arange(n_tracks, dtype=np.int64), length)
+    place = np.arange(n_obs, dtype=np.int64) - np.repeat(track_ptr[:-1].astype(np.int64), length)
+    obs_cam = sigma[(offset[track_of] + place) % n_cams].astype(np.uint32)
+    p = np.einsum("eij,ej->ei", aa_to_matrix(g["rot_aa"])[obs_cam], gt[track_of] - g["gt_pos"][obs_cam])
+    obs_xy = intrinsics[obs_cam, :1] * p[:, :2] / p[:, 2:] + intrinsics[obs_cam, 1:]
+    if noise > 0:
+        obs_xy = obs_xy + noise * intrinsics[obs_cam, :1] * rng.standard_normal((n_obs, 2))
+    g.update(intrinsics=intrinsics, track_ptr=track_ptr, obs_cam=obs_cam, obs_xy=np.ascontiguousarray(obs_xy), gt_points=gt)
+    return g
+
+
 def gauge_normalize(pos, fixed_cam):
     """Positions with translation and scale removed: subtract the fixed camera, divide by the RMS distance from it."""
     p = np.asarray(pos, dtype=np.float64) - np.asarray(pos, dtype=np.float64)[fixed_cam]
