@@ -383,6 +383,13 @@ def declare_track_signatures(lib):
     for build in (lib.gsfm_tracks_build, lib.gsfm_tracks_build_sequential):
         build.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, u64p, _DP, C.POINTER(TrackBuildOptions), u64p, _U32P, _DP, u64p, u64p, u64p, _DP]
         build.restype = C.c_int
+    u8p = C.POINTER(C.c_uint8)
+    lib.gsfm_tracks_select_good.argtypes = [C.c_uint32, _DP, _DP, _DP, u8p, C.c_uint64, u64p, _U32P, _DP, _DP, u8p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            u8p, i32p, _DP, u64p, _DP, _DP]
+    lib.gsfm_tracks_select_good.restype = C.c_int
+    lib.gsfm_tracks_select_good_from_statistics.argtypes = [C.c_uint32, u8p, C.c_uint64, u64p, _U32P, _DP, u8p, i32p, _DP, C.c_int32, C.c_int32, C.c_int32,
+                                                            u8p, u64p]
+    lib.gsfm_tracks_select_good_from_statistics.restype = C.c_int
 
 
 def declare_ba_signatures(lib):

@@ -22,6 +22,7 @@
 #include "track_refine.hpp"
 #include "outlier_tracks.hpp"
 #include "track_build.hpp"
+#include "track_select.hpp"
 #include "solver_ba.hpp"
 #include "solver_full_ba.hpp"
 #include "solver_pos_points.hpp"
@@ -422,6 +423,27 @@ gsfm_status gsfm_tracks_build_sequential(uint32_t n_views, uint64_t n_edges, con
                                          uint64_t* counts_out, double* kernel_ms) {
   return guarded("the sequential track builder", tracks_build_sequential_impl, n_views, n_edges, edge_i, edge_j, match_ptr, matches, options,
                  track_ptr_out, obs_view_out, obs_xy_out, n_tracks, n_obs, counts_out, kernel_ms);
+}
+
+gsfm_status gsfm_tracks_select_good(uint32_t n_cams, const double* rot_aa, const double* cam_pos, const double* intrinsics,
+                                    const uint8_t* cam_estimated, uint64_t n_tracks, const uint64_t* track_ptr, const uint32_t* obs_cam,
+                                    const double* obs_xy, const double* points, const uint8_t* point_estimated,
+                                    int32_t long_track_length_threshold, int32_t image_grid_cell_size_pixels,
+                                    int32_t min_num_optimized_tracks_per_view, int32_t hash_capacity_log2, uint8_t* selected_out,
+                                    int32_t* n_views_out, double* mean_sq_err_out, uint64_t* counts_out, double* kernel_ms, double* top_up_out) {
+  return guarded("the track selection", select_good_impl, n_cams, rot_aa, cam_pos, intrinsics, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy,
+                 points, point_estimated, long_track_length_threshold, image_grid_cell_size_pixels, min_num_optimized_tracks_per_view,
+                 hash_capacity_log2, selected_out, n_views_out, mean_sq_err_out, counts_out, kernel_ms, top_up_out);
+}
+
+gsfm_status gsfm_tracks_select_good_from_statistics(uint32_t n_cams, const uint8_t* cam_estimated, uint64_t n_tracks, const uint64_t* track_ptr,
+                                                    const uint32_t* obs_cam, const double* obs_xy, const uint8_t* point_estimated,
+                                                    const int32_t* n_views, const double* mean_sq_err, int32_t long_track_length_threshold,
+                                                    int32_t image_grid_cell_size_pixels, int32_t min_num_optimized_tracks_per_view,
+                                                    uint8_t* selected_out, uint64_t* counts_out) {
+  return guarded("the sequential track selection", select_good_from_statistics_impl, n_cams, cam_estimated, n_tracks, track_ptr, obs_cam, obs_xy,
+                 point_estimated, n_views, mean_sq_err, long_track_length_threshold, image_grid_cell_size_pixels,
+                 min_num_optimized_tracks_per_view, selected_out, counts_out);
 }
 
 int64_t gsfm_rot_count_components(uint32_t n_cams, uint64_t n_edges, const uint32_t* edge_i, const uint32_t* edge_j) {

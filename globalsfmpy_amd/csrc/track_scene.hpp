@@ -1,5 +1,5 @@
 // The front end of the entries over cameras and a track CSR (track_ptr, obs_cam, obs_xy): both triangulation entries (triangulate.hpp, track_refine.hpp),
-// gsfm_tracks_outlier_tracks (outlier_tracks.hpp), gsfm_tracks_launch_order (gsfm_rot.hip), the creation of both bundle problems (solver_ba.hpp, solver_full_ba.hpp).
+// gsfm_tracks_outlier_tracks (outlier_tracks.hpp), gsfm_tracks_select_good (track_select.hpp), gsfm_tracks_launch_order (gsfm_rot.hip), the creation of both bundle problems (solver_ba.hpp, solver_full_ba.hpp).
 // Plain C++ first (tests/cpp/track_scene_test.cpp builds it with the host compiler alone): lane classes, launch order, the checks of the track arrays.  Under
 // hipcc: the scene in a one-shot call's slab (TrackScene), the launcher over the lane classes, the one-leaf loss of the three reprojection solvers.
 #pragma once

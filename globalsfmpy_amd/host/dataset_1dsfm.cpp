@@ -433,8 +433,36 @@ OutlierTracksStats SetOutlierTracksToUnestimated(double max_error_pixels, double
   return stats;
 }
 
+TrackSelectionStats SelectGoodTracksForBundleAdjustment(const theia::Reconstruction& rec, int long_track_length_threshold, int image_grid_cell_size_pixels,
+                                                        int min_num_optimized_tracks_per_view, std::vector<uint8_t>* tracks_to_optimize) {
+  TrackSelectionStats stats;
+  stats.long_track_length_threshold = long_track_length_threshold; stats.image_grid_cell_size_pixels = image_grid_cell_size_pixels;
+  stats.min_num_optimized_tracks_per_view = min_num_optimized_tracks_per_view;
+  tracks_to_optimize->clear();
+  if (!rec.tracks || rec.tracks->tracks.empty()) return stats;
+  FlatTracks f;
+  FlattenTracks(rec, &f);
+  const size_t T = f.track_ptr.size() - 1;
+  std::vector<uint8_t> point_estimated(T, 0);
+  std::vector<double> points(3 * T, 0.0);
+  for (size_t t = 0; t < T && t < rec.track_estimated.size(); ++t) {
+    point_estimated[t] = rec.track_estimated[t];
+    for (int k = 0; k < 3; ++k) points[3 * t + k] = rec.track_point[t][k];
+  }
+  tracks_to_optimize->assign(T, 0);
+  double top_up[2] = {0.0, 0.0};
+  const gsfm_status st = gsfm_tracks_select_good((uint32_t)f.views.size(), f.rot_aa.data(), f.cam_pos.data(), f.intrinsics.data(), f.cam_estimated.data(), T,
+                                                 f.track_ptr.data(), f.obs_cam.data(), f.obs_xy.data(), points.data(), point_estimated.data(),
+                                                 long_track_length_threshold, image_grid_cell_size_pixels, min_num_optimized_tracks_per_view, 0,
+                                                 tracks_to_optimize->data(), nullptr, nullptr, stats.counts, &stats.kernel_ms, top_up);
+  if (st != GSFM_OK) throw std::runtime_error(std::string("SelectGoodTracksForBundleAdjustment: ") + gsfm_last_error());
+  stats.ran = true;
+  stats.num_deficient_items = (uint64_t)top_up[0]; stats.replay_ms = top_up[1];
+  return stats;
+}
+
 BundleAdjustmentStats BundleAdjustCameraPositionsAndPoints(const std::string& loss_function, double loss_width, int max_num_iterations,
-                                                           theia::Reconstruction* rec) {
+                                                           theia::Reconstruction* rec, const std::vector<uint8_t>* tracks_to_optimize) {
   BundleAdjustmentStats stats;
   stats.max_num_iterations = max_num_iterations;
   gsfm_loss_node loss{};
@@ -453,6 +481,8 @@ BundleAdjustmentStats BundleAdjustCameraPositionsAndPoints(const std::string& lo
     point_estimated[t] = rec->track_estimated[t];
     for (int k = 0; k < 3; ++k) points[3 * t + k] = rec->track_point[t][k];
   }
+  if (tracks_to_optimize)   // the subset: the other estimated tracks stay out of the problem and keep their points
+    for (size_t t = 0; t < T; ++t) if (t >= tracks_to_optimize->size() || !(*tracks_to_optimize)[t]) point_estimated[t] = 0;
   gsfm_ba_problem* problem = nullptr;
   gsfm_status st = gsfm_ba_problem_create((uint32_t)N, f.rot_aa.data(), f.intrinsics.data(), f.cam_estimated.data(), T, f.track_ptr.data(), f.obs_cam.data(),
                                           f.obs_xy.data(), point_estimated.data(), &problem);
@@ -512,7 +542,7 @@ std::string OptimizeIntrinsicsTypeNames(int mask) {
 }
 
 BundleAdjustmentStats BundleAdjustment(const std::string& loss_function, double loss_width, int max_num_iterations, int intrinsics_to_optimize,
-                                       theia::Reconstruction* rec) {
+                                       theia::Reconstruction* rec, const std::vector<uint8_t>* tracks_to_optimize) {
   BundleAdjustmentStats stats;
   stats.max_num_iterations = max_num_iterations;
   const int unsupported = intrinsics_to_optimize & ~(int)OptimizeIntrinsicsType::FOCAL_LENGTH;
@@ -536,6 +566,8 @@ BundleAdjustmentStats BundleAdjustment(const std::string& loss_function, double 
     point_estimated[t] = rec->track_estimated[t];
     for (int k = 0; k < 3; ++k) points[3 * t + k] = rec->track_point[t][k];
   }
+  if (tracks_to_optimize)   // the subset: the other estimated tracks stay out of the problem and keep their points
+    for (size_t t = 0; t < T; ++t) if (t >= tracks_to_optimize->size() || !(*tracks_to_optimize)[t]) point_estimated[t] = 0;
   gsfm_ba_options o;
   gsfm_ba_summary s;
   gsfm_status st;

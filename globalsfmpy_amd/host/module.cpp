@@ -126,6 +126,12 @@ struct ReconstructionEstimatorOptions {
   // :242; which intrinsics BundleAdjustment() moves (the YAML's intrinsics_to_optimize; the reference's flags.yaml sets FOCAL_LENGTH, its
   // flags_1dsfm.yaml NONE).  NONE and FOCAL_LENGTH run on the device; any other bit makes BundleAdjustment() fail with a message.
   gsfm::OptimizeIntrinsicsType intrinsics_to_optimize = gsfm::OptimizeIntrinsicsType::NONE;
+  // :282-300; both bundle adjustments hand the solver the tracks of Theia's SelectGoodTracksForBundleAdjustment only (gsfm_tracks_select_good);
+  // Theia's header defaults (the reference's flag files say 100 tracks per view)
+  bool subsample_tracks_for_bundle_adjustment = false;
+  int track_subset_selection_long_track_length_threshold = 10;
+  int track_selection_image_grid_cell_size_pixels = 100;
+  int min_num_optimized_tracks_per_view = 200;
   // reconstruction_estimator_options.h: what the position stage's estimator is built with (the YAML's position_estimation_min_num_tracks_per_view
   // and position_estimation_robust_loss_width; GlobalReconstructionEstimator.PositionEstimator() hands them over with the reconstruction)
   GSfMNonlinearPositionEstimator::Options nonlinear_position_estimator_options;
@@ -277,10 +283,24 @@ class GlobalReconstructionEstimator {
     if (!reconstruction_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
     int iterations = 100;
     if (reconstruction_->NumViews() >= options_.min_cameras_for_iterative_solver) iterations = (int)(iterations * 1.5);
+    // Theia :690-704: with subsample_tracks_for_bundle_adjustment the adjuster is given the selected tracks only; no flag changes and the
+    // points outside the subset keep their bytes
+    std::vector<uint8_t> subset;
+    const bool subsample = SelectTracks(&subset);
     bundle_ = gsfm::BundleAdjustCameraPositionsAndPoints(options_.bundle_adjustment_loss_function_type, options_.bundle_adjustment_robust_loss_width,
-                                                         iterations, reconstruction_);
+                                                         iterations, reconstruction_, subsample ? &subset : nullptr);
     return bundle_.usable;
   }
+  // subsample_tracks_for_bundle_adjustment set: the selection over the reconstruction as it stands, true; unset: nothing runs, false
+  bool SelectTracks(std::vector<uint8_t>* subset) {
+    selection_ = gsfm::TrackSelectionStats();
+    if (!options_.subsample_tracks_for_bundle_adjustment) return false;
+    selection_ = gsfm::SelectGoodTracksForBundleAdjustment(*reconstruction_, options_.track_subset_selection_long_track_length_threshold,
+                                                           options_.track_selection_image_grid_cell_size_pixels, options_.min_num_optimized_tracks_per_view,
+                                                           subset);
+    return selection_.ran;
+  }
+  gsfm::TrackSelectionStats selection_;   // of the last bundle adjustment, either kind (ran = false when the option is unset)
   // bind_src/GlobalSfMpy.cpp:591-608: BundleAdjustment(); an unusable solution returns at once and removes nothing; otherwise Theia's
   // SetOutlierTracksToUnestimated with max_reprojection_error_in_pixels and min_triangulation_angle_degrees (gsfm_tracks_outlier_tracks).
   bool BundleAdjustmentAndRemoveOutlierPoints() {
@@ -302,6 +322,13 @@ class GlobalReconstructionEstimator {
     if (reconstruction_->NumViews() >= options_.min_cameras_for_iterative_solver) iterations = (int)(iterations * 1.5);
     error_.clear();
     try {
+      // Theia :649-663: with subsample_tracks_for_bundle_adjustment every estimated track that was not chosen becomes unestimated first
+      // (SetTracksInViewsToUnestimated: it stays so, the outlier rule and the retriangulation see it), then what is left is adjusted.
+      // The intrinsics are looked at first, so that an unsupported bit still leaves the reconstruction untouched.
+      std::vector<uint8_t> subset;
+      if (((int)options_.intrinsics_to_optimize & ~(int)gsfm::OptimizeIntrinsicsType::FOCAL_LENGTH) == 0 && SelectTracks(&subset))
+        for (size_t t = 0; t < reconstruction_->track_estimated.size(); ++t)
+          if (t >= subset.size() || !subset[t]) reconstruction_->track_estimated[t] = 0;
       bundle_ = gsfm::BundleAdjustment(options_.bundle_adjustment_loss_function_type, options_.bundle_adjustment_robust_loss_width, iterations,
                                        (int)options_.intrinsics_to_optimize, reconstruction_);
     } catch (const std::invalid_argument& e) {
@@ -361,6 +388,17 @@ py::dict bundle_dict(const gsfm::BundleAdjustmentStats& st) {
   return d;
 }
 
+py::dict selection_dict(const gsfm::TrackSelectionStats& st) {
+  static const char* const names[6] = {"tracks_with_items", "cells", "selected_by_cell", "cameras_topped_up", "selected_by_top_up", "selected"};
+  py::dict d;
+  d["ran"] = st.ran;
+  for (int k = 0; k < 6; ++k) d[names[k]] = st.counts[k];
+  d["long_track_length_threshold"] = st.long_track_length_threshold; d["image_grid_cell_size_pixels"] = st.image_grid_cell_size_pixels;
+  d["min_num_optimized_tracks_per_view"] = st.min_num_optimized_tracks_per_view;
+  d["num_deficient_items"] = st.num_deficient_items; d["kernel_ms"] = st.kernel_ms; d["replay_ms"] = st.replay_ms;
+  return d;
+}
+
 py::dict outlier_dict(const gsfm::OutlierTracksStats& st) {
   py::dict d;
   d["num_examined"] = st.num_examined; d["num_removed"] = st.num_removed; d["kernel_ms"] = st.kernel_ms;
@@ -405,6 +443,10 @@ void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions
   get("num_retriangulation_iterations", options.reconstruction_estimator_options.num_retriangulation_iterations);
   get("refine_camera_positions_and_points_after_position_estimation",
       options.reconstruction_estimator_options.refine_camera_positions_and_points_after_position_estimation);
+  get("subsample_tracks_for_bundle_adjustment", options.reconstruction_estimator_options.subsample_tracks_for_bundle_adjustment);   // bind :261-270
+  get("track_subset_selection_long_track_length_threshold", options.reconstruction_estimator_options.track_subset_selection_long_track_length_threshold);
+  get("track_selection_image_grid_cell_size_pixels", options.reconstruction_estimator_options.track_selection_image_grid_cell_size_pixels);
+  get("min_num_optimized_tracks_per_view", options.reconstruction_estimator_options.min_num_optimized_tracks_per_view);
   get("position_estimation_min_num_tracks_per_view", options.reconstruction_estimator_options.nonlinear_position_estimator_options.min_num_points_per_view);   // bind :228-230
   get("position_estimation_robust_loss_width", options.reconstruction_estimator_options.nonlinear_position_estimator_options.robust_loss_width);
   // bind :199-200: a bitmask of names joined by '|' (StringToOptimizeIntrinsicsType); an absent key leaves NONE
@@ -562,6 +604,10 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def_readwrite("num_retriangulation_iterations", &ReconstructionEstimatorOptions::num_retriangulation_iterations)
       .def_readwrite("refine_camera_positions_and_points_after_position_estimation",
                      &ReconstructionEstimatorOptions::refine_camera_positions_and_points_after_position_estimation)
+      .def_readwrite("subsample_tracks_for_bundle_adjustment", &ReconstructionEstimatorOptions::subsample_tracks_for_bundle_adjustment)
+      .def_readwrite("track_subset_selection_long_track_length_threshold", &ReconstructionEstimatorOptions::track_subset_selection_long_track_length_threshold)
+      .def_readwrite("track_selection_image_grid_cell_size_pixels", &ReconstructionEstimatorOptions::track_selection_image_grid_cell_size_pixels)
+      .def_readwrite("min_num_optimized_tracks_per_view", &ReconstructionEstimatorOptions::min_num_optimized_tracks_per_view)
       .def_readwrite("nonlinear_position_estimator_options", &ReconstructionEstimatorOptions::nonlinear_position_estimator_options);
   py::class_<ReconstructionBuilderOptions>(m, "ReconstructionBuilderOptions")
       .def(py::init<>())
@@ -757,6 +803,9 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
            py::call_guard<py::gil_scoped_release>())
       .def("BundleAdjustment", &GlobalReconstructionEstimator::BundleAdjustment, py::call_guard<py::gil_scoped_release>())
       .def("LastBundleAdjustmentSummary", [](const GlobalReconstructionEstimator& e) { return bundle_dict(e.bundle_); })
+      // the track selection of the last bundle adjustment, either kind: ran (false when subsample_tracks_for_bundle_adjustment is unset), the
+      // six counts of gsfm_tracks_select_good by name, the three parameters, kernel_ms
+      .def("LastTrackSelection", [](const GlobalReconstructionEstimator& e) { return selection_dict(e.selection_); })
       .def("LastStructureSummary", [](const GlobalReconstructionEstimator& e) { return structure_dict(e.structure_, e.options_.bundle_adjust_tracks, e.structure_refine_asked_); })
       .def("LastSummary", [](const GlobalReconstructionEstimator& e) { return summary_dict(e.summary_); })
       .def("LastError", [](const GlobalReconstructionEstimator& e) { return e.error_; });
@@ -882,6 +931,19 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
     d["rounds"] = st.rounds; d["views_removed"] = st.views_removed; d["tracks_removed"] = st.tracks_removed;
     return d;
   });
+  // Theia's SelectGoodTracksForBundleAdjustment with its argument order; the chosen track ids as a sorted list where Theia fills an unordered_set
+  m.def("SelectGoodTracksForBundleAdjustment", [](const Reconstruction& rec, int long_track_length_threshold, int image_grid_cell_size_pixels,
+                                                  int min_num_optimized_tracks_per_view) {
+    std::vector<uint8_t> subset;
+    {
+      py::gil_scoped_release release;
+      gsfm::SelectGoodTracksForBundleAdjustment(rec, long_track_length_threshold, image_grid_cell_size_pixels, min_num_optimized_tracks_per_view, &subset);
+    }
+    std::vector<uint64_t> ids;
+    for (size_t t = 0; t < subset.size(); ++t) if (subset[t]) ids.push_back(t);
+    return ids;
+  }, py::arg("reconstruction"), py::arg("long_track_length_threshold") = 10, py::arg("image_grid_cell_size_pixels") = 100,
+  py::arg("min_num_optimized_tracks_per_view") = 200);
   // Theia's SetOutlierTracksToUnestimated, its name, argument order and return value (the number of tracks removed)
   m.def("SetOutlierTracksToUnestimated", [](double max_inlier_reprojection_error, double min_triangulation_angle_degrees, Reconstruction* rec) {
     return (int)gsfm::SetOutlierTracksToUnestimated(max_inlier_reprojection_error, min_triangulation_angle_degrees, rec).num_removed;

@@ -558,6 +558,51 @@ def outlier_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, poin
     return {"status": status, "n_views": n_views, "mean_sq_err": err, "counts": counts, "kernel_ms": ms.value}
 
 
+TRACK_SELECT_COUNTS = ("tracks_with_items", "cells", "selected_by_cell", "cameras_topped_up", "selected_by_top_up", "selected")
+
+
+def select_good_tracks(rot_aa, cam_pos, intrinsics, track_ptr, obs_cam, obs_xy, points, cam_estimated=None, point_estimated=None,
+                       long_track_length_threshold=10, image_grid_cell_size_pixels=100, min_num_optimized_tracks_per_view=200, hash_capacity_log2=0):
+    """gsfm_tracks_select_good: the tracks a bundle adjustment is given (Theia's SelectGoodTracksForBundleAdjustment under the definition of
+    include/gsfm_tracks.h) on the device: per camera and grid cell the track with the smallest (min(length, threshold), mean squared
+    reprojection error), then every camera topped up to min_num_optimized_tracks_per_view tracks by ascending track index.  The cameras,
+    tracks, points and flags of outlier_tracks; the defaults are Theia's.  hash_capacity_log2: the cell table's size, 0 = automatic (a
+    test's handle on the probe chains).  Nothing is modified: the caller hands `selected != 0` (and its own flags) to a bundle solver.
+    Returns dict(selected (uint8: 0, 1 by a cell, 2 by the top-up), n_views, mean_sq_err, counts (dict of TRACK_SELECT_COUNTS), kernel_ms,
+    deficient_items (what the host downloaded for the top-up), replay_ms (the host's walk over them))."""
+    lib = _abi.load_library()
+    (rot, pos, K), tp, oc, xy, est, pest, pts = _track_arrays((("rot_aa", rot_aa), ("cam_pos", cam_pos), ("intrinsics", intrinsics)), track_ptr, obs_cam,
+                                                              obs_xy, cam_estimated, point_estimated, points=points)
+    T = tp.shape[0] - 1
+    selected, n_views, err = np.zeros(T, dtype=np.uint8), np.zeros(T, dtype=np.int32), np.zeros(T)
+    counts, ms, top_up = np.zeros(6, dtype=np.uint64), C.c_double(0), np.zeros(2)
+    st = lib.gsfm_tracks_select_good(rot.shape[0], _p(rot), _p(pos), _p(K), _p(est), T, _p(tp), _p(oc), _p(xy), _p(pts), _p(pest),
+                                     int(long_track_length_threshold), int(image_grid_cell_size_pixels), int(min_num_optimized_tracks_per_view),
+                                     int(hash_capacity_log2), _p(selected), _p(n_views), _p(err), _p(counts), C.byref(ms), _p(top_up))
+    _raise_if_failed(lib, "gsfm_tracks_select_good", st)
+    return {"selected": selected, "n_views": n_views, "mean_sq_err": err, "counts": {k: int(v) for k, v in zip(TRACK_SELECT_COUNTS, counts)},
+            "kernel_ms": ms.value, "deficient_items": int(top_up[0]), "replay_ms": float(top_up[1])}
+
+
+def select_good_tracks_from_statistics(n_cams, track_ptr, obs_cam, obs_xy, n_views, mean_sq_err, cam_estimated=None, point_estimated=None,
+                                       long_track_length_threshold=10, image_grid_cell_size_pixels=100, min_num_optimized_tracks_per_view=200):
+    """gsfm_tracks_select_good_from_statistics: the grid cells and the top-up of select_good_tracks as sequential host code (no device), given
+    n_views and mean_sq_err per track.  Returns dict(selected, counts (dict of TRACK_SELECT_COUNTS))."""
+    lib = _abi.load_library()
+    _, tp, oc, xy, est, pest, _ = _track_arrays((("cameras", np.zeros((int(n_cams), 3))),), track_ptr, obs_cam, obs_xy, cam_estimated, point_estimated)
+    T = tp.shape[0] - 1
+    nv = np.ascontiguousarray(n_views, dtype=np.int32).reshape(-1)
+    err = np.ascontiguousarray(mean_sq_err, dtype=np.float64).reshape(-1)
+    if nv.shape[0] != T or err.shape[0] != T:
+        raise ValueError("n_views and mean_sq_err need one entry per track")
+    selected, counts = np.zeros(T, dtype=np.uint8), np.zeros(6, dtype=np.uint64)
+    st = lib.gsfm_tracks_select_good_from_statistics(int(n_cams), _p(est), T, _p(tp), _p(oc), _p(xy), _p(pest), _p(nv), _p(err),
+                                                     int(long_track_length_threshold), int(image_grid_cell_size_pixels),
+                                                     int(min_num_optimized_tracks_per_view), _p(selected), _p(counts))
+    _raise_if_failed(lib, "gsfm_tracks_select_good_from_statistics", st)
+    return {"selected": selected, "counts": {k: int(v) for k, v in zip(TRACK_SELECT_COUNTS, counts)}}
+
+
 def track_launch_order(track_ptr):
     """gsfm_tracks_launch_order (host code): (order, class_begin) -- the tracks by lane class 4, 16, 64, longest first inside a class."""
     lib = _abi.load_library()

@@ -255,8 +255,26 @@ struct BundleAdjustmentStats {
   double initial_cost = 0.0, final_cost = 0.0, t_total_ms = 0.0;
   bool focal_lengths_free = false;                   // BundleAdjustment with FOCAL_LENGTH
 };
+// tracks_to_optimize (Theia's SelectGoodTracksForBundleAdjustment, below): one byte per track; the solver's point_estimated is
+// track_estimated AND tracks_to_optimize, and only those points are written back.  NULL: every estimated track, today's call byte for byte.
 BundleAdjustmentStats BundleAdjustCameraPositionsAndPoints(const std::string& loss_function, double loss_width, int max_num_iterations,
-                                                           theia::Reconstruction* reconstruction);
+                                                           theia::Reconstruction* reconstruction,
+                                                           const std::vector<uint8_t>* tracks_to_optimize = nullptr);
+// Theia's SelectGoodTracksForBundleAdjustment (sfm/select_good_tracks_for_bundle_adjustment.cc) on the device: gsfm_tracks_select_good under
+// the definition of include/gsfm_tracks.h, over FlattenTracks' arrays plus track_point / track_estimated.  tracks_to_optimize gets one byte
+// per track: 0, 1 (selected by a grid cell) or 2 (by the top-up).  Nothing in the reconstruction changes.  A reconstruction without tracks
+// gives an empty vector (ran = false).  Throws std::runtime_error when no device is usable (there is no CPU fallback), an argument is
+// refused or the device call fails.
+struct TrackSelectionStats {
+  bool ran = false;
+  uint64_t counts[6] = {0, 0, 0, 0, 0, 0};   // tracks with items, cells, selected by a cell, cameras topped up, selected by the top-up, selected
+  int long_track_length_threshold = 0, image_grid_cell_size_pixels = 0, min_num_optimized_tracks_per_view = 0;
+  uint64_t num_deficient_items = 0;          // what the host downloaded for the top-up
+  double kernel_ms = 0.0, replay_ms = 0.0;
+};
+TrackSelectionStats SelectGoodTracksForBundleAdjustment(const theia::Reconstruction& reconstruction, int long_track_length_threshold,
+                                                        int image_grid_cell_size_pixels, int min_num_optimized_tracks_per_view,
+                                                        std::vector<uint8_t>* tracks_to_optimize);
 // Theia's OptimizeIntrinsicsType (sfm/bundle_adjustment/bundle_adjustment.h): a bitmask, with Theia's names and values.
 // (unscoped, so that values combine with | as Theia's do; in a namespace of its own to keep NONE and ALL out of gsfm)
 namespace optimize_intrinsics {
@@ -277,8 +295,9 @@ std::string OptimizeIntrinsicsTypeNames(int mask);
 //   FOCAL_LENGTH  gsfm_ba7_solve under the definition of include/gsfm_ba7.h: the focal length of every estimated view moves too, from the
 //                 value FlattenTracks gives, and is written to Reconstruction::focal_length (stats.focal_lengths_free);
 //   any other bit throws std::invalid_argument naming the unsupported bits before any device call: the reconstruction is untouched.
+//   tracks_to_optimize: as for BundleAdjustCameraPositionsAndPoints.
 BundleAdjustmentStats BundleAdjustment(const std::string& loss_function, double loss_width, int max_num_iterations, int intrinsics_to_optimize,
-                                       theia::Reconstruction* reconstruction);
+                                       theia::Reconstruction* reconstruction, const std::vector<uint8_t>* tracks_to_optimize = nullptr);
 #endif
 
 // two_views.txt of scripts/read_colmap_database.py:52-133 as AddColmapMatchesToReconstructionBuilder reads it

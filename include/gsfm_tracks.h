@@ -259,6 +259,76 @@ gsfm_status gsfm_tracks_build_sequential(uint32_t n_views, uint64_t n_edges, con
                                          uint64_t* track_ptr_out, uint32_t* obs_view_out, double* obs_xy_out, uint64_t* n_tracks, uint64_t* n_obs,
                                          uint64_t* counts_out, double* kernel_ms);
 
+/* ---- The tracks a bundle adjustment is given: gsfm_tracks_select_good ----
+ *
+ * Restates Theia's SelectGoodTracksForBundleAdjustment (sfm/select_good_tracks_for_bundle_adjustment.cc), which the reference pipeline's
+ * BundleAdjustment() and BundleAdjustCameraPositionsAndPoints() call under subsample_tracks_for_bundle_adjustment: per view and cell of an
+ * image grid the best track, then every view topped up to a minimum number of tracks.  The bundle solvers take the result as point_estimated.
+ *
+ * Input: the cameras and tracks of gsfm_tracks_outlier_tracks, with the same meaning and the same host checks (rot_aa, cam_pos, intrinsics,
+ * cam_estimated, track_ptr, obs_cam, obs_xy, points, point_estimated), and long_track_length_threshold L >= 1, image_grid_cell_size_pixels
+ * S >= 1, min_num_optimized_tracks_per_view K >= 0 (Theia's header defaults: 10, 100, 200; the reference's flag files say 100 for K).
+ * An ITEM is one observation of an estimated track in an estimated camera.  A track that lists a camera twice cannot exist in Theia (a View
+ * holds one feature per track); here each such observation is an item of its own, in the device code and the sequential code alike.
+ *
+ *   1. statistics  per estimated track, over its observations in estimated cameras in the order given: n their count; mean = step 1 of
+ *                  gsfm_tracks_outlier_tracks, its text and its summation order unchanged: it equals that entry's mean_sq_err_out bit for
+ *                  bit.  There is no depth test (Theia's ComputeSqReprojectionError has none).  A track with n = 0 has no item and can never
+ *                  be selected.  The track's key is (min(n, L), mean), compared lexicographically, the mean by its bit pattern as an unsigned
+ *                  64-bit integer after every NaN has been replaced by 0x7ff8000000000000: means are >= +0, so bit order is numeric order,
+ *                  +inf comes after every finite value and NaN after +inf.  A SMALLER key is better -- the shorter truncated length first:
+ *                  Theia's CompareGridCellElements (element1.second < element2.second over TrackStatistics = pair<length, error>), literally.
+ *   2. grid cells  with inv = 1.0 / (double)S an item lies in the cell (camera, (int32)trunc(x inv), (int32)trunc(y inv)): one multiplication
+ *                  and a truncation toward zero, Eigen's cast<int>().  A coordinate that is not finite or has |x inv| >= 2^31 is
+ *                  GSFM_ERR_INVALID_ARG before any device call.  Per non-empty cell the item with the smallest key is chosen, equal keys
+ *                  going to the smallest track index; its track is selected, selected_out = 1.
+ *                  DEPARTURE: of equal keys Theia keeps the first in the hash-set order of the view's tracks.
+ *                  DEPARTURE: Theia's inv_grid_cell_size is a function-local static, so the first call's cell size holds for the whole
+ *                  process; here every call uses its own S.
+ *   3. top-up      the cameras in ascending index (DEPARTURE: Theia walks an unordered_set of views and its result depends on that order).
+ *                  For camera v: est = its number of items, opt = the number of those whose track is selected at that moment, the tracks
+ *                  earlier cameras' top-ups added included.  K = 0, opt >= K or opt = est: nothing happens.  Otherwise m = min(K - opt,
+ *                  est - opt) and the first m items of v whose track is not selected as v's turn begins, walked by ascending (track index,
+ *                  place in the track), are taken: their tracks are selected, selected_out = 2.
+ *                  This is the literal restatement: Theia's std::partial_sort over pair<TrackId, TrackStatistics> has no comparator, so it
+ *                  orders by track id first and the statistics never decide.  The evidently intended ranking by statistics is not built.
+ * Outputs: selected_out (n_tracks bytes, required): 0, 1 (by a cell) or 2 (by the top-up); 0 for every track not estimated on input.
+ * Optional (NULL: not returned): n_views_out, mean_sq_err_out (per track: n and mean of step 1, NaN where n = 0; both 0 for a track that is not
+ * estimated), counts_out[6] = tracks with n >= 1, non-empty cells, tracks selected by a cell, cameras that needed a top-up, tracks selected by
+ * the top-up, tracks selected in all; kernel_ms (device time of the kernels); top_up_out[2] = the number of items the host downloaded for
+ * step 3, the milliseconds its replay took.
+ * The output is a pure function of the input arrays: two calls return the same bytes, whatever lane wins a slot or an atomic.
+ *
+ * On the device: the statistics in the lane classes and the launch order of gsfm_tracks_outlier_tracks over the estimated tracks; step 2 in an
+ * open-addressing table of cells over all items (slots claimed by compare-and-swap, then three sweeps of integer atomic minima: truncated
+ * length, canonical mean bits among the items of that length, track index among those of both); est and opt per camera by integer atomics.
+ * A camera is deficient when K > 0, opt < K and opt < est after step 2; counts only grow during step 3, so no other camera can need a top-up.
+ * The items of the deficient cameras are compacted to a list the host downloads, sorts by (camera, track, place) and walks as step 3 says --
+ * step 3 is sequential across cameras by definition; the precedent is the max_track_length replay of gsfm_tracks_build.
+ * hash_capacity_log2: the cell table has 2^hash_capacity_log2 slots, 0 = automatic (the smallest power of two >= 2 x items, at least 2^10).
+ * It exists so that a test can force long probe chains: a capacity below the number of items, or above 2^31, is GSFM_ERR_INVALID_ARG, not a hang.
+ *
+ * Device memory 40 B per observation + 20 B per table slot + 53 B per track + O(n_cams).  GSFM_ERR_INVALID_ARG before any device call by the
+ * rules of gsfm_tracks_triangulate, and for NULL points, NULL selected_out, L < 1, S < 1, K < 0, 2^31 or more observations, a coordinate off
+ * the grid, a hash_capacity_log2 out of range.  No tracks, or none estimated: GSFM_OK with no device call.  Otherwise without a device
+ * GSFM_ERR_NO_DEVICE: there is no host fallback.
+ *
+ * gsfm_tracks_select_good_from_statistics runs steps 2 and 3 as plain sequential host code (a hash map of cells; no device is touched) on
+ * statistics it is given: n_views and mean_sq_err per track (read for the estimated tracks; a negative n_views there is
+ * GSFM_ERR_INVALID_ARG).  The items are decided by cam_estimated and point_estimated as above.  It writes selected_out and counts_out; it is
+ * the host baseline of tools/time_track_selection.py and a test reference. */
+gsfm_status gsfm_tracks_select_good(uint32_t n_cams, const double* rot_aa, const double* cam_pos, const double* intrinsics,
+                                    const uint8_t* cam_estimated, uint64_t n_tracks, const uint64_t* track_ptr, const uint32_t* obs_cam,
+                                    const double* obs_xy, const double* points, const uint8_t* point_estimated,
+                                    int32_t long_track_length_threshold, int32_t image_grid_cell_size_pixels,
+                                    int32_t min_num_optimized_tracks_per_view, int32_t hash_capacity_log2, uint8_t* selected_out,
+                                    int32_t* n_views_out, double* mean_sq_err_out, uint64_t* counts_out, double* kernel_ms, double* top_up_out);
+gsfm_status gsfm_tracks_select_good_from_statistics(uint32_t n_cams, const uint8_t* cam_estimated, uint64_t n_tracks, const uint64_t* track_ptr,
+                                                    const uint32_t* obs_cam, const double* obs_xy, const uint8_t* point_estimated,
+                                                    const int32_t* n_views, const double* mean_sq_err, int32_t long_track_length_threshold,
+                                                    int32_t image_grid_cell_size_pixels, int32_t min_num_optimized_tracks_per_view,
+                                                    uint8_t* selected_out, uint64_t* counts_out);
+
 #ifdef __cplusplus
 }
 #endif
