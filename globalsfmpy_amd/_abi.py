@@ -174,6 +174,44 @@ class BaSummary(C.Structure):
         return d
 
 
+ROT_L1L2_MAX_L1 = 8
+
+
+class RotL1L2Options(C.Structure):
+    """gsfm_rot_l1l2_options (include/gsfm_rot_l1l2.h)"""
+    _fields_ = [
+        ("max_num_l1_iterations", C.c_int32), ("max_num_irls_iterations", C.c_int32),
+        ("l1_step_convergence_threshold", C.c_double), ("irls_step_convergence_threshold", C.c_double),
+        ("irls_loss_parameter_sigma", C.c_double),
+        ("admm_initial_iterations", C.c_int32), ("max_cg_iterations", C.c_int32),
+        ("admm_rho", C.c_double), ("admm_alpha", C.c_double),
+        ("admm_absolute_tolerance", C.c_double), ("admm_relative_tolerance", C.c_double),
+        ("cg_relative_tolerance", C.c_double),
+        ("cg_check_interval", C.c_int32), ("cg_stall_iterations", C.c_int32),
+        ("verbose", C.c_int32), ("reserved_", C.c_int32),
+    ]
+
+
+class RotL1L2Summary(C.Structure):
+    """gsfm_rot_l1l2_summary (include/gsfm_rot_l1l2.h)"""
+    _fields_ = [
+        ("num_l1_iterations", C.c_int32), ("num_admm_iterations", C.c_int32 * ROT_L1L2_MAX_L1),
+        ("num_irls_iterations", C.c_int32), ("l1_converged", C.c_int32), ("irls_converged", C.c_int32),
+        ("num_cg_iterations", C.c_int32), ("num_linear_solves", C.c_int32), ("num_pcg_stalled_solves", C.c_int32),
+        ("nonfinite", C.c_int32),
+        ("num_edges_used", C.c_uint64),
+        ("l1_step", C.c_double * ROT_L1L2_MAX_L1), ("last_irls_step", C.c_double),
+        ("worst_accepted_cg_residual", C.c_double), ("t_total_ms", C.c_double), ("kernel_ms", C.c_double),
+    ]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        n = min(self.num_l1_iterations, ROT_L1L2_MAX_L1)
+        d["num_admm_iterations"] = [int(v) for v in self.num_admm_iterations[:n]]
+        d["l1_step"] = [float(v) for v in self.l1_step[:n]]
+        return d
+
+
 class TrackRefineOptions(C.Structure):
     """gsfm_tracks_refine_options (include/gsfm_tracks.h)"""
     _fields_ = [
@@ -333,8 +371,22 @@ def load_library():
     declare_ba6_signatures(lib)
     declare_ba7_signatures(lib)
     declare_posp_signatures(lib)
+    declare_rot_l1l2_signatures(lib)
     _lib = lib
     return lib
+
+
+def declare_rot_l1l2_signatures(lib):
+    """include/gsfm_rot_l1l2.h"""
+    opt = C.POINTER(RotL1L2Options)
+    lib.gsfm_rot_l1l2_abi_version.restype = C.c_int
+    lib.gsfm_rot_l1l2_options_default.argtypes = [opt]; lib.gsfm_rot_l1l2_options_default.restype = None
+    lib.gsfm_rot_l1l2_solve.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, _DP, _DP, C.c_int32, opt, C.POINTER(RotL1L2Summary)]
+    lib.gsfm_rot_l1l2_solve.restype = C.c_int
+    lib.gsfm_rot_l1l2_residuals.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, _DP, _DP, opt, _DP, _DP, _DP]
+    lib.gsfm_rot_l1l2_residuals.restype = C.c_int
+    lib.gsfm_rot_l1l2_laplacian_solve.argtypes = [C.c_uint32, C.c_uint64, _U32P, _U32P, _DP, C.c_int32, _DP, opt, _DP, _DP]
+    lib.gsfm_rot_l1l2_laplacian_solve.restype = C.c_int
 
 
 def declare_position_signatures(lib):

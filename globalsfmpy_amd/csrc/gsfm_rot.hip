@@ -26,6 +26,7 @@
 #include "solver_ba.hpp"
 #include "solver_full_ba.hpp"
 #include "solver_pos_points.hpp"
+#include "rot_l1l2.hpp"
 
 // =============================================================================================
 extern "C" {

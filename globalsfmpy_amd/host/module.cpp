@@ -16,6 +16,7 @@
 #include "../../include/gsfm/GSfM_nonlinear_position_estimator.hpp"
 #include "../../include/gsfm/position_track_selection.hpp"
 #include "../../include/gsfm/GSfM_nonlinear_rotation_estimator.hpp"
+#include "../../include/gsfm/robust_rotation_estimator.hpp"
 #include "../../include/gsfm/evaluation.hpp"
 #include "../../include/gsfm/view_graph.hpp"
 #include "../../include/gsfm_ba7.h"
@@ -105,8 +106,21 @@ class PyRotationEstimator : public RotationEstimator {
   }
 };
 
+// Theia's GlobalRotationEstimatorType (reconstruction_estimator_options.h), names and values
+enum class GlobalRotationEstimatorType { ROBUST_L1L2 = 0, NONLINEAR = 1, LINEAR = 2 };
+bool ParseGlobalRotationEstimatorType(const std::string& text, GlobalRotationEstimatorType* out) {
+  if (text == "ROBUST_L1L2") *out = GlobalRotationEstimatorType::ROBUST_L1L2;
+  else if (text == "NONLINEAR") *out = GlobalRotationEstimatorType::NONLINEAR;
+  else if (text == "LINEAR") *out = GlobalRotationEstimatorType::LINEAR;
+  else return false;
+  return true;
+}
+
 // --- light stand-ins for the pipeline objects sfm_pipeline.py passes around ---
 struct ReconstructionEstimatorOptions {
+  // :87 sets ROBUST_L1L2; the default here is NONLINEAR, what both of the reference's flag files choose (a departure: INTEGRATION.md).
+  // Read by EstimateGlobalRotationsFromOptions() only; the YAML's global_rotation_estimator.
+  GlobalRotationEstimatorType global_rotation_estimator_type = GlobalRotationEstimatorType::NONLINEAR;
   int num_threads = 1;                                       // reconstruction_estimator_options.h:99
   int min_num_two_view_inliers = 30;                         // :107
   double rotation_filtering_max_difference_degrees = 5.0;    // :122
@@ -172,6 +186,20 @@ py::dict edge_matches_dict(const gsfm::EdgeMatches& em) {
   return d;
 }
 
+py::dict l1l2_summary_dict(const gsfm_rot_l1l2_summary& s) {
+  py::dict d;
+  const int n = std::min<int>(s.num_l1_iterations, GSFM_ROT_L1L2_MAX_L1);
+  d["num_l1_iterations"] = s.num_l1_iterations;
+  d["num_admm_iterations"] = std::vector<int>(s.num_admm_iterations, s.num_admm_iterations + n);
+  d["l1_step"] = std::vector<double>(s.l1_step, s.l1_step + n);
+  d["num_irls_iterations"] = s.num_irls_iterations; d["last_irls_step"] = s.last_irls_step;
+  d["l1_converged"] = s.l1_converged; d["irls_converged"] = s.irls_converged;
+  d["num_cg_iterations"] = s.num_cg_iterations; d["num_linear_solves"] = s.num_linear_solves; d["num_pcg_stalled_solves"] = s.num_pcg_stalled_solves;
+  d["worst_accepted_cg_residual"] = s.worst_accepted_cg_residual; d["nonfinite"] = s.nonfinite; d["num_edges_used"] = s.num_edges_used;
+  d["t_total_ms"] = s.t_total_ms; d["kernel_ms"] = s.kernel_ms;
+  return d;
+}
+
 py::dict summary_dict(const gsfm_rot_summary& s) {
   py::dict d;
   d["termination"] = s.termination; d["num_iterations"] = s.num_iterations;
@@ -230,6 +258,35 @@ class GlobalReconstructionEstimator {
     const bool ok = est.EstimateRotationsWithSigmaConsensus(view_graph_->GetAllEdges(), &orientations_, loss, options_.num_threads, iters, sigma_max);
     summary_ = est.LastSummary(); error_ = est.LastError();
     return ok;
+  }
+  // The reference's argument-less EstimateGlobalRotations() (:397-438): the estimator options_.global_rotation_estimator_type names, from the
+  // spanning-tree start.  (The binding EstimateGlobalRotations(loss_func, rotation_error_type) keeps its name and meaning.)
+  bool EstimateGlobalRotationsFromOptions() {
+    if (!view_graph_) throw std::runtime_error("call FilterInitialViewGraphAndCalibrateCameras first");
+    error_.clear();
+    std::memset(&summary_, 0, sizeof(summary_));
+    std::memset(&l1l2_summary_, 0, sizeof(l1l2_summary_));
+    switch (options_.global_rotation_estimator_type) {
+      case GlobalRotationEstimatorType::ROBUST_L1L2: {
+        InitOrientations();
+        RobustRotationEstimator est{RobustRotationEstimator::Options()};
+        const bool ok = est.EstimateRotations(view_graph_->GetAllEdges(), &orientations_);
+        l1l2_summary_ = est.LastSummary(); error_ = est.LastError();
+        return ok;
+      }
+      case GlobalRotationEstimatorType::NONLINEAR: {
+        InitOrientations();
+        GSfMNonlinearRotationEstimator est;
+        const bool ok = est.EstimateRotations(view_graph_->GetAllEdges(), &orientations_);
+        summary_ = est.LastSummary(); error_ = est.LastError();
+        return ok;
+      }
+      case GlobalRotationEstimatorType::LINEAR:
+        error_ = "global_rotation_estimator_type LINEAR: the linear rotation estimator is not built in this library (ROBUST_L1L2 and NONLINEAR are)";
+        return false;
+    }
+    error_ = "global_rotation_estimator_type: no such estimator";
+    return false;
   }
   void FilterRotations() {  // :509-524
     FilterViewPairsFromOrientation(orientations_, options_.rotation_filtering_max_difference_degrees, view_graph_);
@@ -347,6 +404,7 @@ class GlobalReconstructionEstimator {
   Reconstruction* reconstruction_ = nullptr;
   OrientationMap orientations_;
   gsfm_rot_summary summary_{};
+  gsfm_rot_l1l2_summary l1l2_summary_{};   // of EstimateGlobalRotationsFromOptions() under ROBUST_L1L2
   std::string error_;
 };
 
@@ -449,6 +507,10 @@ void load_1dsfm_config(const std::string& flagfile, ReconstructionBuilderOptions
   get("min_num_optimized_tracks_per_view", options.reconstruction_estimator_options.min_num_optimized_tracks_per_view);
   get("position_estimation_min_num_tracks_per_view", options.reconstruction_estimator_options.nonlinear_position_estimator_options.min_num_points_per_view);   // bind :228-230
   get("position_estimation_robust_loss_width", options.reconstruction_estimator_options.nonlinear_position_estimator_options.robust_loss_width);
+  std::string rotation_estimator;   // bind :213-214 (StringToRotationEstimatorType); an absent key leaves this library's default, NONLINEAR
+  get("global_rotation_estimator", rotation_estimator);
+  if (!rotation_estimator.empty() && !ParseGlobalRotationEstimatorType(rotation_estimator, &options.reconstruction_estimator_options.global_rotation_estimator_type))
+    throw std::invalid_argument(flagfile + ": global_rotation_estimator: no such estimator '" + rotation_estimator + "' (ROBUST_L1L2, NONLINEAR, LINEAR)");
   // bind :199-200: a bitmask of names joined by '|' (StringToOptimizeIntrinsicsType); an absent key leaves NONE
   std::string intrinsics;
   get("intrinsics_to_optimize", intrinsics);
@@ -557,6 +619,28 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
       .def("LastSummary", [](const GSfMNonlinearRotationEstimator& e) { return summary_dict(e.LastSummary()); })
       .def("LastError", [](const GSfMNonlinearRotationEstimator& e) { return std::string(e.LastError()); });
 
+  py::class_<RobustRotationEstimator::Options>(m, "RobustRotationEstimatorOptions")
+      .def(py::init<>())
+      .def_readwrite("max_num_l1_iterations", &RobustRotationEstimator::Options::max_num_l1_iterations)
+      .def_readwrite("l1_step_convergence_threshold", &RobustRotationEstimator::Options::l1_step_convergence_threshold)
+      .def_readwrite("max_num_irls_iterations", &RobustRotationEstimator::Options::max_num_irls_iterations)
+      .def_readwrite("irls_step_convergence_threshold", &RobustRotationEstimator::Options::irls_step_convergence_threshold)
+      .def_readwrite("irls_loss_parameter_sigma", &RobustRotationEstimator::Options::irls_loss_parameter_sigma);
+  py::class_<RobustRotationEstimator, RotationEstimator>(m, "RobustRotationEstimator")
+      .def(py::init<>())
+      .def(py::init<const RobustRotationEstimator::Options&>())
+      .def("EstimateRotations", py::overload_cast<const EdgeMap&, OrientationMap*>(&RobustRotationEstimator::EstimateRotations),
+           py::call_guard<py::gil_scoped_release>())
+      .def("EstimateRotations", py::overload_cast<OrientationMap*>(&RobustRotationEstimator::EstimateRotations), py::call_guard<py::gil_scoped_release>())
+      .def("AddRelativeRotationConstraint", &RobustRotationEstimator::AddRelativeRotationConstraint)
+      .def("FixedView", &RobustRotationEstimator::FixedView)
+      .def("LastSummary", [](const RobustRotationEstimator& e) { return l1l2_summary_dict(e.LastSummary()); })
+      .def("LastError", [](const RobustRotationEstimator& e) { return std::string(e.LastError()); });
+  py::enum_<GlobalRotationEstimatorType>(m, "GlobalRotationEstimatorType")   // Theia's names and values
+      .value("ROBUST_L1L2", GlobalRotationEstimatorType::ROBUST_L1L2)
+      .value("NONLINEAR", GlobalRotationEstimatorType::NONLINEAR)
+      .value("LINEAR", GlobalRotationEstimatorType::LINEAR);
+
   m.def("test_loss_with_input_x", [](ceres::LossFunction* loss, double x) {  // bind :179-183
     double out[3] = {0, 0, 0};
     loss->Evaluate(x, out);
@@ -587,6 +671,7 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
                       if (mask & ~(int)gsfm::OptimizeIntrinsicsType::ALL) throw std::invalid_argument("intrinsics_to_optimize: no such bit");
                       o.intrinsics_to_optimize = (gsfm::OptimizeIntrinsicsType)mask;
                     })
+      .def_readwrite("global_rotation_estimator_type", &ReconstructionEstimatorOptions::global_rotation_estimator_type)
       .def_readwrite("num_threads", &ReconstructionEstimatorOptions::num_threads)
       .def_readwrite("min_num_two_view_inliers", &ReconstructionEstimatorOptions::min_num_two_view_inliers)
       .def_readwrite("rotation_filtering_max_difference_degrees", &ReconstructionEstimatorOptions::rotation_filtering_max_difference_degrees)
@@ -775,6 +860,8 @@ PYBIND11_MODULE(_GlobalSfMpy, m) {  // imported through the GlobalSfMpy.py shim 
            py::call_guard<py::gil_scoped_release>())
       .def("EstimateGlobalRotationsWithSigmaConsensus", &GlobalReconstructionEstimator::EstimateGlobalRotationsSigmaConsensus,
            py::call_guard<py::gil_scoped_release>())
+      .def("EstimateGlobalRotationsFromOptions", &GlobalReconstructionEstimator::EstimateGlobalRotationsFromOptions, py::call_guard<py::gil_scoped_release>())
+      .def("LastRobustRotationSummary", [](const GlobalReconstructionEstimator& e) { return l1l2_summary_dict(e.l1l2_summary_); })
       .def("FilterRotations", &GlobalReconstructionEstimator::FilterRotations)
       .def("OptimizePairwiseTranslations", [](GlobalReconstructionEstimator& e) {
         RefineRelativeTranslationsStats st;

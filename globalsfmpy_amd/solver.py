@@ -398,6 +398,74 @@ def orientations_from_maximum_spanning_tree(n_cams, edge_i, edge_j, rel_aa, weig
             "kernel_ms": ms.value}
 
 
+def _rot_l1l2_options(lib, kw):
+    o = _abi.RotL1L2Options()
+    lib.gsfm_rot_l1l2_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k) or k == "reserved_":
+            raise TypeError("unknown option %r of the robust rotation estimator" % k)
+        setattr(o, k, v)
+    return o
+
+
+def _rot_l1l2_edges(edge_i, edge_j, rel_aa):
+    ei = np.ascontiguousarray(edge_i, dtype=np.uint32).reshape(-1)
+    ej = np.ascontiguousarray(edge_j, dtype=np.uint32).reshape(-1)
+    rel = None if rel_aa is None else np.ascontiguousarray(rel_aa, dtype=np.float64).reshape(-1, 3)
+    if ej.shape[0] != ei.shape[0] or (rel is not None and rel.shape[0] != ei.shape[0]):
+        raise ValueError("edge_i, edge_j and rel_aa must describe the same edges")
+    return ei, ej, rel
+
+
+def estimate_rotations_robust_l1l2(n_cams, edge_i, edge_j, rel_aa, init_aa, fixed_cam=0, **options):
+    """gsfm_rot_l1l2_solve: Theia's RobustRotationEstimator (ROBUST_L1L2: L1 by ADMM, then IRLS) under the definition of
+    include/gsfm_rot_l1l2.h, on the device.  Edges are used as listed (i > j and repeated pairs allowed); init_aa: n_cams x 3 start
+    rotations; fixed_cam: the camera held constant.  options: the fields of gsfm_rot_l1l2_options.  Returns (rot_aa, summary dict)."""
+    lib = _abi.load_library()
+    n = int(n_cams)
+    ei, ej, rel = _rot_l1l2_edges(edge_i, edge_j, rel_aa)
+    rot = np.array(init_aa, dtype=np.float64, order="C").reshape(n, 3)
+    o = _rot_l1l2_options(lib, options)
+    s = _abi.RotL1L2Summary()
+    st = lib.gsfm_rot_l1l2_solve(n, ei.shape[0], _p(ei), _p(ej), _p(rel), _p(rot), int(fixed_cam), C.byref(o), C.byref(s))
+    _raise_if_failed(lib, "gsfm_rot_l1l2_solve", st)
+    return rot, s.as_dict()
+
+
+def robust_l1l2_residuals(n_cams, edge_i, edge_j, rel_aa, rot_aa, **options):
+    """gsfm_rot_l1l2_residuals (a testing aid): b_e = Log(R_j^T R_ij R_i) by the solve's edge sweep.  Returns dict(b (E x 3), sq, weight)."""
+    lib = _abi.load_library()
+    n = int(n_cams)
+    ei, ej, rel = _rot_l1l2_edges(edge_i, edge_j, rel_aa)
+    rot = np.ascontiguousarray(rot_aa, dtype=np.float64).reshape(n, 3)
+    E = ei.shape[0]
+    b, sq, w = np.empty((E, 3)), np.empty(E), np.empty(E)
+    o = _rot_l1l2_options(lib, options)
+    st = lib.gsfm_rot_l1l2_residuals(n, E, _p(ei), _p(ej), _p(rel), _p(rot), C.byref(o), _p(b), _p(sq), _p(w))
+    _raise_if_failed(lib, "gsfm_rot_l1l2_residuals", st)
+    return {"b": b, "sq": sq, "weight": w}
+
+
+def robust_l1l2_laplacian_solve(n_cams, edge_i, edge_j, rhs, weights=None, fixed_cam=0, **options):
+    """gsfm_rot_l1l2_laplacian_solve (a testing aid): x = L_w^-1 rhs on the free cameras by the solve's own structure, product and PCG.
+    weights: per edge, None = the unweighted form.  Returns (x (n_cams x 3), dict(cg_iterations, stalled, cg_rel, kernel_ms, product_ms, product_bytes))."""
+    lib = _abi.load_library()
+    n = int(n_cams)
+    ei, ej, _ = _rot_l1l2_edges(edge_i, edge_j, None)
+    b = np.ascontiguousarray(rhs, dtype=np.float64).reshape(n, 3)
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != ei.shape[0]:
+            raise ValueError("weights disagrees with the edges in length")
+    x, info = np.empty((n, 3)), np.zeros(6)
+    o = _rot_l1l2_options(lib, options)
+    st = lib.gsfm_rot_l1l2_laplacian_solve(n, ei.shape[0], _p(ei), _p(ej), _p(w), int(fixed_cam), _p(b), C.byref(o), _p(x), _p(info))
+    _raise_if_failed(lib, "gsfm_rot_l1l2_laplacian_solve", st)
+    return x, {"cg_iterations": int(info[0]), "stalled": bool(info[1]), "cg_rel": float(info[2]), "kernel_ms": float(info[3]),
+               "product_ms": float(info[4]), "product_bytes": float(info[5])}
+
+
 def filter_relative_translations(n_cams, edge_i, edge_j, rel_t, rot_aa, num_iterations=48, tolerance=0.1, seed=1, axes=None,
                                  want_projections=False):
     """gsfm_pos_filter_relative_translations: the 1DSfM filter of relative translations (Theia's FilterViewPairsFromRelativeTranslation
